@@ -9,8 +9,13 @@ already resident in HBM) and, for N > 1, the int16 PCM shards are collected on r
 at N>1 = configs[3]: 1024 utterances per GPU (8192 on 8 GPUs), gathered on rank 0 (tools/scale.sh runs 1/2/4/8).
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py ... --full                             (+ roofline, cpu_baseline and the other configs' legs)
+    python bench.py ... --dump-outputs DIR                 (+ the last timed step's PCM as DIR/pcm.npy)
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline figure
+(`value`, `ms_per_step`); everything else it measures -- the per-kernel event pass and `roofline`, `cpu_baseline`,
+the generic kernel, configs 3 / 4, ragged rows, the streaming legs, level 1, the decoder -- runs only with --full
+(the keys are null otherwise).
 """
 import argparse
 import json
@@ -191,6 +196,24 @@ class _DryDecoder:
         return 1.0
 
 
+DUMP_MAX_BYTES = 60_000_000          # --dump-outputs stays under 64 MB in all
+
+
+def dump_outputs(dirname, pcm):
+    """--dump-outputs: the (rows, T) int16 PCM the timed path handed its caller, as DIR/pcm.npy in float32 (exact).
+    Beyond DUMP_MAX_BYTES a fixed, seeded sample of rows is kept, in ascending order, and their indices go to
+    DIR/pcm_rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    a = pcm.detach().cpu().numpy()
+    keep = max(1, DUMP_MAX_BYTES // (a.shape[1] * 4 + 8))
+    if a.shape[0] > keep:
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+        a = a[rows]
+        np.save(os.path.join(dirname, "pcm_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(dirname, "pcm.npy"), a.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -201,6 +224,12 @@ def main():
     ap.add_argument("--latency-ticks", type=int, default=1500, help="streaming-latency leg: 1500 ticks = 60 s of stream time")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-latency", action="store_true", help="skip the streaming-latency leg (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: kernel-event pass + roofline, cpu_baseline "
+                         "(unless --no-cpu-baseline) and, at N = 1, the other configs' legs (unless --no-latency)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the PCM of the last one (what the caller receives: rank 0's "
+                         "gathered rows at N > 1) as DIR/pcm.npy, float32")
     args = ap.parse_args()
 
     if args.batch is None:
@@ -211,13 +240,14 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", os.environ.get("MASTER_PORT", "29533"), __file__,
                "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup),
-               "--batch", str(args.batch)] + (["--no-cpu-baseline"] if args.no_cpu_baseline else [])
+               "--batch", str(args.batch)] + (["--no-cpu-baseline"] if args.no_cpu_baseline else []) \
+            + (["--full"] if args.full else []) + (["--dump-outputs", args.dump_outputs] if args.dump_outputs else [])
         sys.exit(subprocess.call(cmd))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
 
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline and not DRY:      # before anything touches the GPU (the pool forks); N > 1: rank 0 too
+    if args.full and rank == 0 and not args.no_cpu_baseline and not DRY:   # before anything touches the GPU (the pool forks); N > 1: rank 0 too
         cpu = cpu_baseline()
 
     import numpy as np
@@ -258,6 +288,7 @@ def main():
         return "lpcnet_sample_pair_kernel (two utterances per workgroup)" if pair else info["kernel"]
     from dss_amd.distributed import gather_pcm     # the collective the world-size-2 gloo test covers (tests/test_cpu_distributed.py)
     gathered_rows = [0]
+    gathered = [None]                                           # --dump-outputs at N > 1: rank 0's (world * B, T) PCM, latest step
 
     def step():
         dec.reset_async()
@@ -266,6 +297,8 @@ def main():
             full = gather_pcm(out, world * B, dst=0)            # int16 shards as bytes, one RCCL gather, rank order
             if full is not None:
                 gathered_rows[0] = int(full.shape[0])
+                if args.dump_outputs:
+                    gathered[0] = full
 
     def fence():
         if world > 1:
@@ -285,16 +318,22 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
+    # what the timed path handed its caller in the last timed step, for output-by-output comparison of two builds
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gathered[0] if world > 1 else out)
+
     # dominant kernel: live HIP-event timing of the sample-rate kernel on its launch stream, separate pass
     # (events add a host sync per step, so they are kept out of the timed region above)
-    dec.enable_timing(True)
-    for _ in range(max(3, min(args.steps, 10))):
-        step()
-    sync()
-    k_ms, f_ms = dec.kernel_ms(0), dec.kernel_ms(1)
-    dec.enable_timing(False)
+    k_ms = f_ms = None
+    if args.full:
+        dec.enable_timing(True)
+        for _ in range(max(3, min(args.steps, 10))):
+            step()
+        sync()
+        k_ms, f_ms = dec.kernel_ms(0), dec.kernel_ms(1)
+        dec.enable_timing(False)
 
-    extras = rank == 0 and world == 1 and not args.no_latency and not DRY      # the other configs' legs: N = 1 only
+    extras = args.full and rank == 0 and world == 1 and not args.no_latency and not DRY   # the other configs' legs: N = 1 only
     # the kernel a model with skewed sparsity lands on: the generic sample-rate kernel, same batch, N=1 only
     generic = None
     if extras:
@@ -488,41 +527,44 @@ def main():
     if rank == 0:
         samples_per_step = world * B * FRAMES * FRAME
         value = samples_per_step * args.steps / dt
-        bps = 273218.5 if DRY else lpcnet.bytes_per_sample()     # ~273 kB per output sample
-        synth = B * (FRAMES - 2) * FRAME                         # samples the sample-rate kernel really computes per launch
-        # SURVEY.md 8(d) "algorithmic flops": 2 per weight touched (sparse blocks, diagonal, GRU B, the 8 visited dual-FC
-        # nodes) + the embedding adds; every one of them is a separate fp32 multiply or add (no FMA by contract)
-        macs = (bps - 2.5) / 4.0 - 16 - 3 * 1152
-        flops_per_sample = 2.0 * macs + 2 * 16 + 3 * 1152
-        achieved_tf = flops_per_sample * synth / (k_ms * 1e-3) / 1e12
-        alg_bytes_per_launch = bps * synth
-        hbm_equiv = alg_bytes_per_launch / (k_ms * 1e-3) / 1e9
-        roofline = {
-            "bound": "valu",                 # fp32 vector ALU without FMA; the kernel's real ceiling
-            "achieved": achieved_tf, "peak": FP32_NOFMA_PEAK_TF, "unit": "TFLOP/s", "frac": achieved_tf / FP32_NOFMA_PEAK_TF,
-            "traffic": traffic, "traffic_unit": "GB of HBM per launch (PMC, profiles/)",
-            "kernel": kernel_for(B), "kernel_ms": k_ms, "frame_kernels_ms": f_ms,
-            "algorithmic_flops_per_sample": flops_per_sample, "samples_per_launch": synth,
-            "frac_of_fma_peak": achieved_tf / FP32_VECTOR_PEAK_TF,
-            "note": "useful fp32 operations (SURVEY 8d algorithmic flops) per second of the sample-rate kernel, against the "
-                    "fp32 vector peak WITHOUT fused multiply-add (157.3/2 TFLOP/s): bit-exactness with the scalar C reference "
-                    "forbids FMA and MFMA.  Weights are resident in VGPRs/LDS, so HBM is not the bound (see "
-                    "roofline_hbm_equiv and traffic).",
-        }
-        if counters:
-            c = counters.get("derived", {})
-            roofline["valu_issue_utilisation"] = c.get("valu_issue_utilisation")
-            roofline["counters_from"] = f"profiles/{tag}_pmc_issue.json @ git {counters.get('git_sha', 'unknown')}"
-        hbm = {"bound": "hbm", "achieved": hbm_equiv, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": hbm_equiv / HBM_PEAK_GBS,
-               "algorithmic_bytes_per_sample": bps, "algorithmic_GB_per_launch": alg_bytes_per_launch / 1e9,
-               "hbm_traffic_frac_of_peak": (traffic / (k_ms * 1e-3) / HBM_PEAK_GBS) if traffic else None,
-               "note": "SURVEY 8(d) convention: weights touched once per output sample at fp32.  NOT a physical HBM figure -- "
-                       "those bytes are served from VGPRs/LDS, which is why it exceeds the HBM peak; the HBM traffic the "
-                       "counters see is hbm_traffic_frac_of_peak of peak."}
+        roofline = hbm = None
+        if args.full:                                            # needs the kernel-event pass above
+            bps = 273218.5 if DRY else lpcnet.bytes_per_sample()     # ~273 kB per output sample
+            synth = B * (FRAMES - 2) * FRAME                         # samples the sample-rate kernel really computes per launch
+            # SURVEY.md 8(d) "algorithmic flops": 2 per weight touched (sparse blocks, diagonal, GRU B, the 8 visited dual-FC
+            # nodes) + the embedding adds; every one of them is a separate fp32 multiply or add (no FMA by contract)
+            macs = (bps - 2.5) / 4.0 - 16 - 3 * 1152
+            flops_per_sample = 2.0 * macs + 2 * 16 + 3 * 1152
+            achieved_tf = flops_per_sample * synth / (k_ms * 1e-3) / 1e12
+            alg_bytes_per_launch = bps * synth
+            hbm_equiv = alg_bytes_per_launch / (k_ms * 1e-3) / 1e9
+            roofline = {
+                "bound": "valu",                 # fp32 vector ALU without FMA; the kernel's real ceiling
+                "achieved": achieved_tf, "peak": FP32_NOFMA_PEAK_TF, "unit": "TFLOP/s", "frac": achieved_tf / FP32_NOFMA_PEAK_TF,
+                "traffic": traffic, "traffic_unit": "GB of HBM per launch (PMC, profiles/)",
+                "kernel": kernel_for(B), "kernel_ms": k_ms, "frame_kernels_ms": f_ms,
+                "algorithmic_flops_per_sample": flops_per_sample, "samples_per_launch": synth,
+                "frac_of_fma_peak": achieved_tf / FP32_VECTOR_PEAK_TF,
+                "note": "useful fp32 operations (SURVEY 8d algorithmic flops) per second of the sample-rate kernel, against the "
+                        "fp32 vector peak WITHOUT fused multiply-add (157.3/2 TFLOP/s): bit-exactness with the scalar C reference "
+                        "forbids FMA and MFMA.  Weights are resident in VGPRs/LDS, so HBM is not the bound (see "
+                        "roofline_hbm_equiv and traffic).",
+            }
+            if counters:
+                c = counters.get("derived", {})
+                roofline["valu_issue_utilisation"] = c.get("valu_issue_utilisation")
+                roofline["counters_from"] = f"profiles/{tag}_pmc_issue.json @ git {counters.get('git_sha', 'unknown')}"
+            hbm = {"bound": "hbm", "achieved": hbm_equiv, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": hbm_equiv / HBM_PEAK_GBS,
+                   "algorithmic_bytes_per_sample": bps, "algorithmic_GB_per_launch": alg_bytes_per_launch / 1e9,
+                   "hbm_traffic_frac_of_peak": (traffic / (k_ms * 1e-3) / HBM_PEAK_GBS) if traffic else None,
+                   "note": "SURVEY 8(d) convention: weights touched once per output sample at fp32.  NOT a physical HBM figure -- "
+                           "those bytes are served from VGPRs/LDS, which is why it exceeds the HBM peak; the HBM traffic the "
+                           "counters see is hbm_traffic_frac_of_peak of peak."}
         line = {
             "metric": METRIC, "value": value, "unit": "samples/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic" if not DRY else "DRY RUN (DSS_BENCH_DRY=1): stand-in synthesiser on CPU, not a measurement",
+            "full": args.full,
             "config": {"workload": (f"configs[1]: LPCNet-only, batch={B}" if world == 1 else
                                     f"configs[3]: LPCNet batch={world * B} sharded over {world} GPUs, {B}")
                                    + " synthetic 1-s utterances per GPU (100x20 f32 features -> "

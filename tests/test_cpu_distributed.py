@@ -78,3 +78,30 @@ def test_bench_multi_gpu_branch_dry_run():
     assert cfg["gathered_bytes_per_step"] == 2 * 6 * 100 * 160 * 2          # both shards' int16 PCM arrived on rank 0
     assert line["value"] > 0 and abs(line["samples_per_s_per_gpu"] * 2 - line["value"]) < 1e-6 * line["value"]
     assert "DRY RUN" in line["data"]                          # and says so: not a measurement
+
+
+def test_bench_plain_and_full_lines_and_dump_outputs_dry_run(tmp_path):
+    """bench.py at N = 1 with the stand-in synthesiser: --steps sets the timed steps, a plain line carries the headline
+    fields and leaves the --full blocks null, --full fills the roofline, and --dump-outputs writes the last step's PCM
+    as float32, identically in two runs with the same arguments."""
+    import json
+    env = dict(os.environ, DSS_BENCH_DRY="1")
+
+    def run(*extra):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                              "--batch", "5", *extra], capture_output=True, text=True, env=env, timeout=300)
+        assert out.returncode == 0, out.stdout + out.stderr
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        return json.loads(lines[0])
+
+    plain = run("--dump-outputs", str(tmp_path / "a"))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in plain, k
+    assert plain["steps"] == 3 and plain["warmup"] == 1 and plain["ms_per_step"] > 0 and plain["full"] is False
+    assert plain["roofline"] is None and plain["cpu_baseline"] is None
+    full = run("--full", "--dump-outputs", str(tmp_path / "b"))
+    assert full["full"] is True and full["roofline"]["kernel_ms"] == 1.0
+    a, b = np.load(tmp_path / "a" / "pcm.npy"), np.load(tmp_path / "b" / "pcm.npy")
+    assert a.dtype == np.float32 and a.shape == (5, 100 * 160)
+    assert np.array_equal(a, b) and np.any(a != 0)
