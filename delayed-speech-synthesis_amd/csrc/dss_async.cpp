@@ -3,6 +3,8 @@
 // (Python hosts use PyTorch-ROCm's streams and events for the same purpose; these entry points are for hosts without it
 // and for memory kinds torch does not hand out.)
 #include <algorithm>
+#include <map>
+#include <mutex>
 
 #include "dss_host.h"
 
@@ -84,9 +86,68 @@ extern "C" void *dss_host_alloc(size_t bytes, int cached)
     return p;
 }
 
+// Blocks from dss_host_alloc_fine (base -> bytes): what a progressive call may take as its host buffers, with their sizes.
+static std::mutex g_fine_mu;
+static std::map<uintptr_t, size_t> g_fine;
+
+// Explicitly coherent (fine-grained) page-locked memory: the device's stores reach it while a kernel runs, so a progressive
+// vocoder call can hand PCM to the host frame by frame (dss_lpcnet_batch_synthesize_ragged_progress_dev).
+extern "C" void *dss_host_alloc_fine(size_t bytes)
+{
+    if (dss_ensure_device()) return nullptr;
+    void *p = nullptr;
+    if (hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocCoherent) != hipSuccess) {
+        dss_set_error("hipHostMalloc(%zu, coherent) failed", bytes);
+        return nullptr;
+    }
+    std::lock_guard<std::mutex> lk(g_fine_mu);
+    g_fine[(uintptr_t)p] = bytes ? bytes : 1;
+    return p;
+}
+
 extern "C" void dss_host_free(void *p)
 {
-    if (p) hipHostFree(p);
+    if (!p) return;
+    {
+        std::lock_guard<std::mutex> lk(g_fine_mu);
+        g_fine.erase((uintptr_t)p);
+    }
+    hipHostFree(p);
+}
+
+int dss_fine_host_view(void *p, size_t bytes, size_t align, const char *what, void **dev)
+{
+    if (!p) { dss_set_error("%s: null pointer", what); return DSS_EINVAL; }
+    if ((uintptr_t)p % align) { dss_set_error("%s: not %zu-byte aligned", what, align); return DSS_EINVAL; }
+    {
+        std::lock_guard<std::mutex> lk(g_fine_mu);
+        auto it = g_fine.upper_bound((uintptr_t)p);
+        const bool inside = it != g_fine.begin() && (--it, (uintptr_t)p + bytes <= it->first + it->second);
+        if (!inside) {
+            dss_set_error("%s: %zu bytes not inside a block from dss_host_alloc_fine (pageable, cached or too small)", what, bytes);
+            return DSS_EINVAL;
+        }
+    }
+    unsigned flags = 0;
+    if (hipHostGetFlags(&flags, p) != hipSuccess || (flags & hipHostMallocNonCoherent)) {
+        (void)hipGetLastError();
+        dss_set_error("%s: the runtime does not report coherent page-locked memory (flags 0x%x)", what, flags);
+        return DSS_EINVAL;
+    }
+    if (hipHostGetDevicePointer(dev, p, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        dss_set_error("%s: no device view of the page-locked block", what);
+        return DSS_EINVAL;
+    }
+    return DSS_OK;
+}
+
+// Acquire loads: a counter read here covers the PCM the device stored before it (the kernel's system-scope release).
+extern "C" int dss_progress_read(const int *host_frames_done, int n, int *out)
+{
+    if (!host_frames_done || !out || n < 0) { dss_set_error("dss_progress_read: null pointer or negative count"); return DSS_EINVAL; }
+    for (int i = 0; i < n; ++i) out[i] = __atomic_load_n(host_frames_done + i, __ATOMIC_ACQUIRE);
+    return DSS_OK;
 }
 
 // Device -> page-locked host memory as a KERNEL (16-byte stores straight into the mapped host pages), not as a DMA copy.

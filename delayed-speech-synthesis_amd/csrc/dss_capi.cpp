@@ -945,7 +945,7 @@ static int check_batch_shape(dss_lpcnet_batch *b, int n_utts, int n_frames, int 
 // frame-rate network, then the persistent sample-rate kernel, on stream s; b->d.slot_of / count_of select the
 // uniform (NULL) or the ragged form
 static int run_batch(dss_lpcnet_batch *b, const float *d_features, int n_utts, int n_frames, int feat_stride, short *d_pcm,
-                     hipStream_t s)
+                     hipStream_t s, int *d_frames_done = nullptr)
 {
     // the kernels index the forced excitation and the logit trace with the CALL's shape: it must be the shape they were
     // sized for, and a uniform call (the trace build would launch a ragged one as if every row were full)
@@ -960,7 +960,7 @@ static int run_batch(dss_lpcnet_batch *b, const float *d_features, int n_utts, i
     int rc = dss_launch_frame_network(*b->model, b->d, d_features, n_utts, n_frames, feat_stride, s);
     if (rc) return rc;
     if (b->timing) DSS_HIP_CHECK(hipEventRecord(b->ev[1], s));
-    rc = dss_launch_sample_network(*b->model, b->d, n_utts, n_frames, d_pcm, b->trace, b->pair, s);
+    rc = dss_launch_sample_network(*b->model, b->d, n_utts, n_frames, d_pcm, b->trace, b->pair, s, d_frames_done);
     if (rc) return rc;
     if (b->timing) {
         DSS_HIP_CHECK(hipEventRecord(b->ev[2], s));
@@ -1039,6 +1039,32 @@ extern "C" int dss_lpcnet_batch_synthesize_ragged_dev(dss_lpcnet_batch *b, const
     rc = stage_ragged(b, slots, counts, n_utts, n_frames, s);
     if (rc) return rc;
     return run_batch(b, d_features, n_utts, n_frames, feat_stride, d_pcm, s);
+}
+
+// The ragged call with per-frame delivery: PCM goes straight into fine-grained host memory and host_frames_done[row] counts the
+// frames of each row already there (include/dss_hip.h).  Everything is checked before anything is enqueued.
+extern "C" int dss_lpcnet_batch_synthesize_ragged_progress_dev(dss_lpcnet_batch *b, const float *d_features, const int *slots,
+                                                               const int *counts, int n_utts, int n_frames, int feat_stride,
+                                                               short *host_pcm, int *host_frames_done, void *hip_stream)
+{
+    if (!b || !d_features || !host_pcm || !host_frames_done) { dss_set_error("null argument"); return DSS_EINVAL; }
+    int rc = check_batch_shape(b, n_utts, n_frames, feat_stride);
+    if (rc) return rc;
+    if ((b->trace & 15) || b->d.force_exc || b->d.trace_logits) {
+        dss_set_error("progressive calls run without trace or teacher forcing (trace %d%s)", b->trace, b->d.force_exc ? ", forced excitation" : "");
+        return DSS_EINVAL;
+    }
+    DSS_HIP_CHECK(hipSetDevice(b->device));
+    void *d_pcm = nullptr, *d_done = nullptr;
+    rc = dss_fine_host_view(host_pcm, (size_t)n_utts * n_frames * DSS_FRAME_SIZE * sizeof(short), 16, "host_pcm", &d_pcm);
+    if (rc) return rc;
+    rc = dss_fine_host_view(host_frames_done, (size_t)n_utts * sizeof(int), sizeof(int), "host_frames_done", &d_done);
+    if (rc) return rc;
+    for (int i = 0; i < n_utts; ++i) __atomic_store_n(host_frames_done + i, 0, __ATOMIC_RELAXED);   // before anything is enqueued
+    hipStream_t s = (hipStream_t)hip_stream;
+    rc = stage_ragged(b, slots, counts, n_utts, n_frames, s);
+    if (rc) return rc;
+    return run_batch(b, d_features, n_utts, n_frames, feat_stride, (short *)d_pcm, s, (int *)d_done);
 }
 
 extern "C" int dss_lpcnet_batch_synthesize_ragged(dss_lpcnet_batch *b, const float *features, const int *slots,

@@ -139,14 +139,16 @@ struct DssBatchDev {
 int dss_launch_frame_network(const DssModelDev &m, DssBatchDev &b, const float *d_features, int n_utts, int n_frames,
                              int feat_stride, hipStream_t s);
 // pair: 0 = choose (two utterances per workgroup when the call has more utterances than the chip has CUs), -1 = never,
-// 2 = always (uniform calls of models that fit, see dss_pair_fits)
+// 2 = always (uniform calls of models that fit, see dss_pair_fits).
+// frames_done != NULL: a progressive call (dss_lpcnet_batch_synthesize_ragged_progress_dev): d_pcm is the device view of
+// fine-grained host memory, frames_done[row] counts the frames of each row already there; one utterance per workgroup, no trace.
 int dss_launch_sample_network(const DssModelDev &m, DssBatchDev &b, int n_utts, int n_frames, short *d_pcm,
-                              int trace, int pair, hipStream_t s);
+                              int trace, int pair, hipStream_t s, int *frames_done = nullptr);
 int dss_launch_sample_network_pair(const DssModelDev &m, DssBatchDev &b, int n_utts, int n_frames, short *d_pcm, int trace,
                                    hipStream_t s);
 int dss_pair_fits(const DssModelDev &m);
 int dss_launch_sample_network_generic(const DssModelDev &m, DssBatchDev &b, int n_utts, int n_frames, short *d_pcm,
-                                      int trace, hipStream_t s);
+                                      int trace, hipStream_t s, int *frames_done = nullptr);
 int dss_launch_exp10_selftest(const float *d_x, const float *d_comp, float *d_out, long n, hipStream_t s);
 int dss_launch_lin2ulaw_selftest(unsigned start, unsigned stride, long n, unsigned char *d_out, hipStream_t s);
 int dss_launch_lpcnet_reset(const DssModelDev &m, DssBatchDev &b, int utt, hipStream_t s);

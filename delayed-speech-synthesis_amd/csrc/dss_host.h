@@ -6,6 +6,10 @@
 // Selects (and on first use picks: LOCAL_RANK, else 0) this thread's device; DSS_ENODEV without one.
 int dss_ensure_device(void);
 
+// The device view of `bytes` at p, which must lie inside one block from dss_host_alloc_fine and be `align`-byte aligned;
+// DSS_EINVAL with a message otherwise (pageable or cached page-locked memory, a short block, misalignment).
+int dss_fine_host_view(void *p, size_t bytes, size_t align, const char *what, void **dev);
+
 // Small host -> device uploads that must not stall, and must not be overwritten, while earlier calls are still queued.
 //
 // hipMemcpyAsync from pageable memory may wait for the stream's earlier work (the runtime stages it), which would hold the

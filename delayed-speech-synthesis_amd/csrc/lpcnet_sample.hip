@@ -511,10 +511,15 @@ __device__ __forceinline__ void dss_role_a(SampleLds &L, float *hblk_lds, const 
 // RAGGED: rows name their decoder slot and frame count (b.slot_of / b.count_of).  A separate instantiation, so the
 // uniform form keeps its register allocation (the two extra live scalars cost 1.3 % there); the trace build always
 // honours the lists.
-template <bool TRACE, bool STAMP, int Z, bool RAGGED, bool EXT>
+// PROGRESS -- FramesDone = <int *>, instantiated with RAGGED only: pcm_out is the device view of fine-grained host memory,
+// and after each frame's PCM wave 7 publishes frames_done[utt] = f + 1 (dss_publish_frames_done).  The switch is a trailing
+// parameter pack, so that with it empty (every other instantiation) the kernel keeps its arguments and its code exactly.
+template <bool TRACE, bool STAMP, int Z, bool RAGGED, bool EXT, typename... FramesDone>
 __global__ void __launch_bounds__(512)
-lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restrict__ pcm_out)
+lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restrict__ pcm_out, FramesDone... frames_done)
 {
+    constexpr bool PROGRESS = sizeof...(FramesDone) > 0;
+    static_assert(!PROGRESS || (RAGGED && !TRACE && !STAMP && sizeof...(FramesDone) == 1), "progress: ragged rows, one int * counter array");
     __shared__ __attribute__((aligned(16))) SampleLds L;
     extern __shared__ __attribute__((aligned(16))) float hblk_lds[];       // h-gate block records (size per model)
     static_assert(sizeof(SampleLds) % 16 == 0, "dynamic LDS must start 16-byte aligned");
@@ -654,6 +659,7 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
         for (; f_first < nf && fc0 + f_first < DSS_FEATURES_DELAY; ++f_first) {      // lpcnet.c: frame_count <= FEATURES_DELAY -> silence
             short *pcm_frame = pcm_out + ((size_t)utt * n_frames + f_first) * DSS_FRAME_SIZE;
             for (int k = lane; k < DSS_FRAME_SIZE / 2; k += 64) reinterpret_cast<int *>(pcm_frame)[k] = 0;
+            if constexpr (PROGRESS) dss_publish_frames_done(frames_done..., utt, f_first + 1, lane);
             if (TRACE)
                 for (int k = lane; k < DSS_FRAME_SIZE; k += 64) {
                     b.trace_exc[((size_t)utt * n_frames + f_first) * DSS_FRAME_SIZE + k] = -1.f;
@@ -778,6 +784,7 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
             // wave 7 owns L.pcm: LDS operations of one wave are ordered, no barrier needed
             for (int k = lane; k < DSS_FRAME_SIZE / 2; k += 64)
                 reinterpret_cast<int *>(pcm_frame)[k] = reinterpret_cast<const int *>(L.pcm)[k];
+            if constexpr (PROGRESS) dss_publish_frames_done(frames_done..., utt, f + 1, lane);
         }
         __syncthreads();                                                                // final barrier
         if (STAMP && lane == 0 && b.trace_pcm) {        // diagnostic build only
@@ -810,9 +817,11 @@ static int dss_cu_count()
 }
 
 int dss_launch_sample_network(const DssModelDev &m, DssBatchDev &b, int n_utts, int n_frames, short *d_pcm, int trace,
-                              int pair, hipStream_t s)
+                              int pair, hipStream_t s, int *frames_done)
 {
-    if (!m.fast_ok || trace >= 16) return dss_launch_sample_network_generic(m, b, n_utts, n_frames, d_pcm, trace & 15, s);
+    if (frames_done && (trace & 15)) { dss_set_error("progressive calls run without trace or teacher forcing"); return DSS_EINVAL; }
+    if (!m.fast_ok || trace >= 16) return dss_launch_sample_network_generic(m, b, n_utts, n_frames, d_pcm, trace & 15, s, frames_done);
+    if (frames_done) pair = -1;                  // progressive calls: the one-utterance kernel only
     // Calls with more rows than the chip has CUs run two utterances per workgroup (lpcnet_sample_pair.hip: the same
     // roles with the utterances as the halves of packed fp32 instructions); with a CU per utterance the one-utterance
     // form below is faster.  pair: 0 = this rule, -1 = never, 2 = always (tests, A/B timing).
@@ -852,6 +861,8 @@ int dss_launch_sample_network(const DssModelDev &m, DssBatchDev &b, int n_utts, 
         // models with z/r tails or long h lists (m.ext): always on the 10-slot layout, which has registers to spare for them
         DSS_SET_ATTR((lpcnet_sample_kernel<false, false, 10, false, true>));  DSS_SET_ATTR((lpcnet_sample_kernel<false, false, 10, true, true>));
         DSS_SET_ATTR((lpcnet_sample_kernel<true, false, 10, false, true>));
+        DSS_SET_ATTR((lpcnet_sample_kernel<false, false, 10, true, false, int *>)); DSS_SET_ATTR((lpcnet_sample_kernel<false, false, 12, true, false, int *>));
+        DSS_SET_ATTR((lpcnet_sample_kernel<false, false, 10, true, true, int *>));
 #undef DSS_SET_ATTR
         attr_set |= 1ull << (dev & 63);
     }
@@ -865,7 +876,12 @@ int dss_launch_sample_network(const DssModelDev &m, DssBatchDev &b, int n_utts, 
         else hipLaunchKernelGGL((lpcnet_sample_kernel<T, S2, 12, R, false>), dim3(n_rows), dim3(512), dyn, s, m, b, n_frames, d_pcm);     \
     } while (0)
 #define DSS_LAUNCH_EXT(T, R) hipLaunchKernelGGL((lpcnet_sample_kernel<T, false, 10, R, true>), dim3(n_rows), dim3(512), dyn, s, m, b, n_frames, d_pcm)
-    if (m.ext) {
+    if (frames_done) {                           // progressive (ragged) calls
+        if (m.ext) hipLaunchKernelGGL((lpcnet_sample_kernel<false, false, 10, true, true, int *>), dim3(n_rows), dim3(512), dyn, s, m, b, n_frames, d_pcm, frames_done);
+        else if (z10) hipLaunchKernelGGL((lpcnet_sample_kernel<false, false, 10, true, false, int *>), dim3(n_rows), dim3(512), dyn, s, m, b, n_frames, d_pcm, frames_done);
+        else hipLaunchKernelGGL((lpcnet_sample_kernel<false, false, 12, true, false, int *>), dim3(n_rows), dim3(512), dyn, s, m, b, n_frames, d_pcm, frames_done);
+    }
+    else if (m.ext) {
         if (trace) DSS_LAUNCH_EXT(true, false);
         else if (ragged) DSS_LAUNCH_EXT(false, true);
         else DSS_LAUNCH_EXT(false, false);

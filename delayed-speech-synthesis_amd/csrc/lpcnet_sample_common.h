@@ -20,6 +20,18 @@ __device__ __forceinline__ float dss_uniform(float x) { return __builtin_bit_cas
 __device__ __forceinline__ int dss_uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
 __device__ __forceinline__ uint32_t dss_uniform(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
 
+// Progressive launches (the PROGRESS instantiations): pcm_out is the device view of fine-grained page-locked host memory, and
+// the host learns that frames [0, value) of row `utt` are there from frames_done[utt].  Called by the ONE wave that stored all
+// of the frame's PCM: its stores drain, a system-scope release, then one lane stores the counter (vector stores only).  The
+// second wait stands between the release and the counter whatever the compiler makes of the fence's own wait.
+__device__ __forceinline__ void dss_publish_frames_done(int *frames_done, int utt, int value, int lane)
+{
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (lane == 0) __hip_atomic_store(frames_done + utt, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // LDS byte address of an object in the workgroup's LDS (for the hand-written ds_ instructions below)
 __device__ __forceinline__ unsigned dss_lds_addr(const void *p)
 {

@@ -41,10 +41,13 @@ struct SampleLds {
 // Every role executes the same barrier sequence: per synthesised sample A B C D, per frame one more, then the final one.
 
 // ---- waves 0..5: GRU A (lane = unit), waves 0..3 also the dual-FC (lane = tree node) -------------------------------------
-template <bool TRACE, bool STAMP, bool HAS_FC>
+// PROGRESS (FramesDone = <int *>, see lpcnet_sample_generic_kernel): wave 0 stores all of a frame's PCM (80 words; otherwise
+// threads 0..79 of waves 0 and 1), drains it and publishes frames_done[utt].
+template <bool TRACE, bool STAMP, bool HAS_FC, typename... FramesDone>
 __device__ __forceinline__ void generic_role_a(SampleLds &L, const DssModelDev &m, const DssBatchDev &b, int n_frames, int utt,
-                                               int nf, int fc0, int tid, int wave, int lane, short *pcm_out)
+                                               int nf, int fc0, int tid, int wave, int lane, short *pcm_out, FramesDone... frames_done)
 {
+    constexpr bool PROGRESS = sizeof...(FramesDone) > 0;
     const float rbz = m.gru_a_rbias[tid], rbr = m.gru_a_rbias[NA + tid], rbh = m.gru_a_rbias[2 * NA + tid];
     const float dgz = m.gru_a_diag[tid], dgr = m.gru_a_diag[NA + tid], dgh = m.gru_a_diag[2 * NA + tid];
     float fw0[HAS_FC ? NB : 1], fw1[HAS_FC ? NB : 1], fb0 = 0, fb1 = 0, ff0 = 0, ff1 = 0;
@@ -65,7 +68,12 @@ __device__ __forceinline__ void generic_role_a(SampleLds &L, const DssModelDev &
     for (int f = 0; f < nf; ++f) {
         short *pcm_frame = pcm_out + ((size_t)utt * n_frames + f) * DSS_FRAME_SIZE;
         if (fc0 + f < DSS_FEATURES_DELAY) {                 // lpcnet.c: frame_count <= FEATURES_DELAY -> silence
-            if (tid < DSS_FRAME_SIZE / 2) reinterpret_cast<int *>(pcm_frame)[tid] = 0;
+            if constexpr (PROGRESS) {
+                if (wave == 0) {
+                    for (int k = lane; k < DSS_FRAME_SIZE / 2; k += 64) reinterpret_cast<int *>(pcm_frame)[k] = 0;
+                    dss_publish_frames_done(frames_done..., utt, f + 1, lane);
+                }
+            } else if (tid < DSS_FRAME_SIZE / 2) reinterpret_cast<int *>(pcm_frame)[tid] = 0;
             if (TRACE && tid < DSS_FRAME_SIZE) {
                 b.trace_exc[((size_t)utt * n_frames + f) * DSS_FRAME_SIZE + tid] = -1.f;
                 b.trace_pcm[((size_t)utt * n_frames + f) * DSS_FRAME_SIZE + tid] = 0.f;
@@ -164,7 +172,13 @@ __device__ __forceinline__ void generic_role_a(SampleLds &L, const DssModelDev &
             cur ^= 1;
         }
         __syncthreads();                                                            // frame barrier
-        if (tid < DSS_FRAME_SIZE / 2) reinterpret_cast<int *>(pcm_frame)[tid] = reinterpret_cast<const int *>(L.pcm)[tid];
+        if constexpr (PROGRESS) {
+            if (wave == 0) {
+                for (int k = lane; k < DSS_FRAME_SIZE / 2; k += 64)
+                    reinterpret_cast<int *>(pcm_frame)[k] = reinterpret_cast<const int *>(L.pcm)[k];
+                dss_publish_frames_done(frames_done..., utt, f + 1, lane);
+            }
+        } else if (tid < DSS_FRAME_SIZE / 2) reinterpret_cast<int *>(pcm_frame)[tid] = reinterpret_cast<const int *>(L.pcm)[tid];
     }
     __syncthreads();                                                                // final barrier
     if (STAMP && lane == 0 && b.trace_pcm)
@@ -172,10 +186,13 @@ __device__ __forceinline__ void generic_role_a(SampleLds &L, const DssModelDev &
     b.gru_a_state[(size_t)(b.slot_of ? b.slot_of[utt] : utt) * NA + tid] = L.state_a[cur][tid];
 }
 
-template <bool TRACE, bool STAMP>
+// PROGRESS -- FramesDone = <int *>: a progressive call (see generic_role_a).  The switch is a trailing parameter pack, so that
+// with it empty (every other instantiation) the kernel keeps its arguments and its code exactly.
+template <bool TRACE, bool STAMP, typename... FramesDone>
 __global__ void __launch_bounds__(512)
-lpcnet_sample_generic_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restrict__ pcm_out)
+lpcnet_sample_generic_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restrict__ pcm_out, FramesDone... frames_done)
 {
+    static_assert(sizeof...(FramesDone) == 0 || (!TRACE && !STAMP && sizeof...(FramesDone) == 1), "progress: one int * counter array");
     __shared__ __attribute__((aligned(16))) SampleLds L;
     const int utt = blockIdx.x;
     const int slot = b.slot_of ? b.slot_of[utt] : utt;
@@ -193,8 +210,8 @@ lpcnet_sample_generic_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *
     const int fc0 = b.fc0[utt];
     __syncthreads();
 
-    if (wave < 4) { generic_role_a<TRACE, STAMP, true>(L, m, b, n_frames, utt, nf, fc0, tid, wave, lane, pcm_out); return; }
-    if (wave < 6) { generic_role_a<TRACE, STAMP, false>(L, m, b, n_frames, utt, nf, fc0, tid, wave, lane, pcm_out); return; }
+    if (wave < 4) { generic_role_a<TRACE, STAMP, true>(L, m, b, n_frames, utt, nf, fc0, tid, wave, lane, pcm_out, frames_done...); return; }
+    if (wave < 6) { generic_role_a<TRACE, STAMP, false>(L, m, b, n_frames, utt, nf, fc0, tid, wave, lane, pcm_out, frames_done...); return; }
     unsigned long long stamp_acc[6] = {0, 0, 0, 0, 0, 0}, t_prev = 0;
     int cur = 0;
     if (wave == 6) {
@@ -350,9 +367,11 @@ lpcnet_sample_generic_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *
 }
 
 int dss_launch_sample_network_generic(const DssModelDev &m, DssBatchDev &b, int n_utts, int n_frames, short *d_pcm, int trace,
-                              hipStream_t s)
+                              hipStream_t s, int *frames_done)
 {
-    if (trace == 2)        // diagnostic: phase stamps written into trace_pcm (never used for timing claims)
+    if (frames_done)       // progressive call (counters indexed by the row of the call = workgroup here)
+        hipLaunchKernelGGL((lpcnet_sample_generic_kernel<false, false, int *>), dim3(n_utts), dim3(512), 0, s, m, b, n_frames, d_pcm, frames_done);
+    else if (trace == 2)        // diagnostic: phase stamps written into trace_pcm (never used for timing claims)
         hipLaunchKernelGGL((lpcnet_sample_generic_kernel<false, true>), dim3(n_utts), dim3(512), 0, s, m, b, n_frames, d_pcm);
     else if (trace)
         hipLaunchKernelGGL((lpcnet_sample_generic_kernel<true, false>), dim3(n_utts), dim3(512), 0, s, m, b, n_frames, d_pcm);

@@ -39,6 +39,8 @@ def _declare(L):
         "dss_host_alloc": (vp, [sz, i]),
         "dss_host_free": (None, [vp]),
         "dss_memcpy_d2h_async": (i, [vp, vp, sz, vp]),
+        "dss_host_alloc_fine": (vp, [sz]),
+        "dss_progress_read": (i, [vp, i, vp]),
         "lpcnet_create": (vp, []),
         "lpcnet_init": (i, [vp]),
         "lpcnet_destroy": (None, [vp]),
@@ -67,6 +69,7 @@ def _declare(L):
         "dss_lpcnet_batch_synthesize_dev": (i, [vp, vp, i, i, i, vp, vp]),
         "dss_lpcnet_batch_synthesize_ragged": (i, [vp, vp, vp, vp, i, i, i, vp]),
         "dss_lpcnet_batch_synthesize_ragged_dev": (i, [vp, vp, vp, vp, i, i, i, vp, vp]),
+        "dss_lpcnet_batch_synthesize_ragged_progress_dev": (i, [vp, vp, vp, vp, i, i, i, vp, vp, vp]),
         "dss_lpcnet_batch_tap": (i, [vp, i, i, vp, sz]),
         "dss_lpcnet_batch_enable_trace": (i, [vp, i]),
         "dss_lpcnet_batch_set_multi": (i, [vp, i]),

@@ -76,6 +76,14 @@ def model_info() -> dict:
     return info
 
 
+def read_progress(frames_done_ptr: int, n: int, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """The n frame counters of a progressive call, read with acquire loads (``dss_progress_read``)."""
+    if out is None:
+        out = np.empty(n, dtype=np.int32)
+    _lib.check(_lib.load().dss_progress_read(frames_done_ptr, int(n), out.ctypes.data))
+    return out
+
+
 def bytes_per_sample() -> float:
     return float(_lib.load().dss_lpcnet_bytes_per_sample())
 
@@ -211,6 +219,24 @@ class LPCNetBatch:
         _lib.check(self._L.dss_lpcnet_batch_synthesize_ragged_dev(
             self._h, features.data_ptr(), None if sl is None else sl.ctypes.data, c.ctypes.data, n, F, S, out.data_ptr(), s))
         return out
+
+    def synthesize_ragged_progress_torch(self, features, counts, slots, host_pcm_ptr: int, frames_done_ptr: int, stream=None):
+        """Progressive form of ``synthesize_ragged_torch`` (``dss_lpcnet_batch_synthesize_ragged_progress_dev``): the PCM of
+        row i goes straight into the host block at ``host_pcm_ptr`` ((n, Fmax*160) int16) while the kernel runs, and the int32
+        at ``frames_done_ptr + 4*i`` counts its frames already there (read them with ``read_progress``).  Both blocks must
+        come from ``dss_host_alloc_fine`` and must not belong to a call still in flight."""
+        import torch
+        assert features.is_cuda and features.dtype == torch.float32 and features.is_contiguous()
+        self._check_device(features)
+        n, F, S = features.shape
+        c = np.ascontiguousarray(counts, dtype=np.int32)
+        sl = None if slots is None else np.ascontiguousarray(slots, dtype=np.int32)
+        if c.shape != (n,) or (sl is not None and sl.shape != (n,)):
+            raise ValueError("counts/slots must have one entry per row")
+        s = torch.cuda.current_stream(features.device).cuda_stream if stream is None else stream
+        _lib.check(self._L.dss_lpcnet_batch_synthesize_ragged_progress_dev(
+            self._h, features.data_ptr(), None if sl is None else sl.ctypes.data, c.ctypes.data, n, F, S, host_pcm_ptr,
+            frames_done_ptr, s))
 
     # ---- test / measurement taps ------------------------------------------------------------------------
     def enable_trace(self, on=True):

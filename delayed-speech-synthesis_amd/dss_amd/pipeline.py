@@ -179,7 +179,8 @@ class GatedStreamingPipeline(_DecoderMixin):
     on a tick are handed to a ``SegmentSynthesisQueue`` (side streams: whole-segment decoder + ragged vocoder launch + PCM
     copy per job) and ``push()`` returns the segments FINISHED since the last tick.  The reference's own behaviour -- its
     one stream blocks while it vocodes (units.py:531-538) -- is ``asynchronous=False``: every tick then waits for what it
-    started, and returns it."""
+    started, and returns it.  ``progressive=True`` (opt-in) also hands out each segment's audio a 10 ms frame at a time as the
+    vocoder produces it, through ``poll_chunks()``; ``push()``, ``poll()`` and ``flush()`` return whole segments as before."""
 
     def __init__(self, n_streams: int, n_channels: int = 64, fs: int = 1000, packet: int = 40,
                  buffer_size: int = 2000, context_frames: int = 50, smoothing_context: int = 5,
@@ -187,7 +188,7 @@ class GatedStreamingPipeline(_DecoderMixin):
                  decoder: Optional[torch.nn.Module] = None, vad: Optional[torch.nn.Module] = None, seed: int = 0,
                  max_segment_frames: Optional[int] = None, use_vad_kernel: bool = True, use_decoder_kernel: bool = True,
                  asynchronous: bool = True, n_lanes: Optional[int] = None, rows_per_job: int = 32,
-                 pool_rows: Optional[int] = None):
+                 pool_rows: Optional[int] = None, progressive: bool = False):
         self.S, self.C, self.packet = n_streams, n_channels, packet
         self.hga = HgaExtractorGPU(n_streams, n_channels, fs=fs)
         self.decoder = self._make_decoder(n_channels, decoder, seed)
@@ -216,7 +217,7 @@ class GatedStreamingPipeline(_DecoderMixin):
         self.queue = SegmentSynthesisQueue(self.gate, self.vocoder, n_channels, self.seg_cap, decoder_factory=factory,
                                            decoder_module=self.decoder, n_lanes=n_lanes if asynchronous else 1,
                                            rows_per_job=min(rows_per_job, n_streams) if asynchronous else n_streams,
-                                           threaded=asynchronous, pool_rows=pool_rows)
+                                           threaded=asynchronous, pool_rows=pool_rows, progressive=progressive)
         mean = np.zeros(n_channels) if channel_means is None else np.asarray(channel_means, dtype=np.float64)
         std = np.ones(n_channels) if channel_stds is None else np.asarray(channel_stds, dtype=np.float64)
         self.mean, self.std = torch.from_numpy(mean).cuda(), torch.from_numpy(std).cuda()
@@ -282,6 +283,11 @@ class GatedStreamingPipeline(_DecoderMixin):
     def poll(self):
         """Segments finished since the last push()/poll() (a host between ticks may call this as often as it likes)."""
         return self.queue.poll()
+
+    def poll_chunks(self):
+        """progressive=True: pieces of segment audio that reached the host since the last call, as (stream, previous_frames,
+        offset_samples, pcm int16 host array, last); see SegmentSynthesisQueue.poll_chunks."""
+        return self.queue.poll_chunks()
 
     def close(self):
         """Stop the queue's worker thread and release its lanes (also done when the pipeline is dropped)."""

@@ -23,6 +23,12 @@ Lanes: each has its own HIP stream, decoder scratch, vocoder scratch and result 
 a lane sharing the TICK's queue would put 140 ms of vocoder in front of a tick.  So the number of lanes defaults to
 ``GPU_MAX_HW_QUEUES - 1`` (three without the variable; a host that wants more sets it before the HIP runtime starts --
 bench.py and tools/gated_leg.py use 8), at most 7.
+
+``progressive=True`` (opt-in) delivers a segment's audio a 10 ms frame at a time as the vocoder produces it: the lanes' PCM
+and frame counters live in fine-grained host memory, the ragged call is the progressive one (no copy-out kernel), and every
+step of the queue reads the counters of the jobs in flight.  ``poll_chunks()`` returns (stream, tag, offset_samples, pcm,
+last) pieces -- a stream's in frame order, all of a segment before any of its next one, exactly one ``last`` per segment --
+and ``poll()`` still returns every whole segment when its job retires, as without the option.
 """
 from __future__ import annotations
 
@@ -64,11 +70,29 @@ def select_job(pending, busy, max_rows):
     return job, keep
 
 
+def progress_chunks(lengths, sent, counts, retired=False):
+    """The pieces of a progressive job that can go out now.  lengths[k]: frames of row k; sent[k]: frames of it already handed
+    out, or -1 once its last piece has gone (updated in place); counts[k]: its frame counter as last read (ignored once
+    ``retired``: the job's event has fired, every frame is there).  Returns [(k, first_frame, end_frame, last)]: at most one
+    piece per row, from where the previous one ended to the counter (a counter that jumps several frames gives one piece),
+    ``last`` when it reaches the row's length -- a row of length 0 gives one empty last piece."""
+    out = []
+    for k, n in enumerate(lengths):
+        if sent[k] < 0:
+            continue
+        c = n if retired else max(0, min(int(counts[k]), n))
+        if c > sent[k] or c == n:
+            out.append((k, sent[k], c, c == n))
+            sent[k] = -1 if c == n else c
+    return out
+
+
 class _Segment:
-    __slots__ = ("stream", "length", "row", "tag", "ready", "t_close")
+    __slots__ = ("stream", "length", "row", "tag", "ready", "t_close", "t_launch")
 
     def __init__(self, stream, length, row, tag, ready, t_close):
         self.stream, self.length, self.row, self.tag, self.ready, self.t_close = stream, length, row, tag, ready, t_close
+        self.t_launch = None
 
 
 class _Ready:
@@ -80,7 +104,7 @@ class _Ready:
 
 
 class _Lane:
-    def __init__(self, L, vocoder: LPCNetBatch, decoder_factory, rows: int, seg_cap: int, n_out: int):
+    def __init__(self, L, vocoder: LPCNetBatch, decoder_factory, rows: int, seg_cap: int, n_out: int, progressive: bool = False):
         self.L = L
         self.stream = L.dss_stream_create()
         self.done = L.dss_event_create()
@@ -90,14 +114,24 @@ class _Lane:
         self.voc = vocoder.create_lane(rows, seg_cap)
         self.dec = decoder_factory(rows, seg_cap) if decoder_factory is not None else None
         self.feats = torch.zeros(rows * seg_cap * n_out, dtype=torch.float32, device="cuda")      # a job's (rows, fmax, n_out), packed
-        self.pcm = torch.empty(rows * seg_cap * FRAME_SIZE, dtype=torch.int16, device="cuda")    # a job's (rows, fmax * 160), packed
         self.host_bytes = rows * seg_cap * FRAME_SIZE * 2
-        self.host_ptr = L.dss_host_alloc(self.host_bytes, 1)
+        self.done_ptr = None
+        if progressive:             # the kernel stores PCM and frame counters straight into fine-grained host memory
+            self.pcm = None
+            self.host_ptr = L.dss_host_alloc_fine(self.host_bytes)
+            self.done_ptr = L.dss_host_alloc_fine(rows * 4) if self.host_ptr else None
+            if not self.done_ptr:
+                raise MemoryError(L.dss_last_error().decode())
+            self.counts = np.zeros(rows, dtype=np.int32)
+        else:
+            self.pcm = torch.empty(rows * seg_cap * FRAME_SIZE, dtype=torch.int16, device="cuda")    # a job's (rows, fmax * 160), packed
+            self.host_ptr = L.dss_host_alloc(self.host_bytes, 1)
         if not self.host_ptr:
             raise MemoryError(L.dss_last_error().decode())
         self.host = np.ctypeslib.as_array((C.c_int16 * (rows * seg_cap * FRAME_SIZE)).from_address(self.host_ptr))
         self.job: Optional[List[_Segment]] = None
         self.job_frames = 0
+        self.sent: list = []                                  # progressive: frames of each row handed out (-1: all, last piece sent)
 
     def close(self):
         L = self.L
@@ -106,6 +140,8 @@ class _Lane:
             self.voc.close()
             self.dec = None
             L.dss_host_free(self.host_ptr)
+            if self.done_ptr:
+                L.dss_host_free(self.done_ptr)
             L.dss_event_destroy(self.done)
             L.dss_stream_destroy(self.stream)
             self.stream = None
@@ -114,10 +150,11 @@ class _Lane:
 class SegmentSynthesisQueue:
     def __init__(self, gate, vocoder: LPCNetBatch, n_features: int, seg_cap: int, decoder_factory=None, decoder_module=None,
                  n_lanes: Optional[int] = None, rows_per_job: int = 32, pool_rows: Optional[int] = None, n_out: int = 20,
-                 threaded: bool = True):
+                 threaded: bool = True, progressive: bool = False):
         """gate: the SpeechGateGPU whose completed segments are taken; vocoder: the LPCNetBatch with one slot per stream.
         decoder_factory(rows, frames) -> BiLstmDecoderGPU (one per lane: each owns its layer buffers), or None: then
-        decoder_module (any torch module with the reference's call signature) runs row by row on the lane's stream."""
+        decoder_module (any torch module with the reference's call signature) runs row by row on the lane's stream.
+        progressive: also hand out each segment's audio frame by frame as it is produced (``poll_chunks``)."""
         self._L = _lib.require_gpu()
         self.gate, self.S, self.C = gate, gate.S, int(n_features)
         self.cap, self.R, self.n_out = int(seg_cap), int(rows_per_job), int(n_out)
@@ -126,7 +163,8 @@ class SegmentSynthesisQueue:
             raise ValueError("a decoder kernel factory or a decoder module is needed")
         if n_lanes is None:
             n_lanes = default_lanes()
-        self.lanes = [_Lane(self._L, vocoder, decoder_factory, self.R, self.cap, self.n_out) for _ in range(int(n_lanes))]
+        self.progressive = bool(progressive)
+        self.lanes = [_Lane(self._L, vocoder, decoder_factory, self.R, self.cap, self.n_out, self.progressive) for _ in range(int(n_lanes))]
         rows = int(pool_rows or max(2 * self.S, 4 * self.R))
         self.pool = torch.zeros((rows, self.cap, self.C), dtype=torch.float32, device="cuda")
         self._free_rows = list(range(rows - 1, -1, -1))
@@ -136,6 +174,10 @@ class SegmentSynthesisQueue:
         self.busy = np.zeros(self.S, dtype=bool)              # streams with a job in flight
         self.finished: list = []
         self.latencies_ms: list = []                          # segment closed (submit) -> PCM seen on the host (poll)
+        self.chunks: list = []                                # progressive: (stream, tag, offset_samples, pcm, last) not yet polled
+        self.first_pcm_latencies_ms = collections.deque(maxlen=65536)   # progressive: submit -> the piece at offset 0 on the host
+        self.lane_wait_ms = collections.deque(maxlen=65536)             # submit -> launch on a lane
+        self.launch_to_first_pcm_ms = collections.deque(maxlen=65536)   # progressive: launch -> the piece at offset 0 on the host
         self.jobs_launched = 0
         self.segments_done = 0
         self._open = 0                                        # segments submitted and not yet retired
@@ -224,19 +266,51 @@ class SegmentSynthesisQueue:
                         x = self.pool[sg.row, : sg.length][None]
                         y, _ = self.module(x, self.module.create_new_initial_state(batch_size=1, device="cuda"))
                         feats[k, : sg.length] = y[0]
-        pcm = lane.pcm[: self.R * fmax * FRAME_SIZE].view(self.R, fmax * FRAME_SIZE)
-        lane.voc.synthesize_ragged_torch(feats[:n], counts, slots=slots, out=pcm, stream=lane.stream)
-        _lib.check(L.dss_memcpy_d2h_async(lane.host_ptr, pcm.data_ptr(), n * fmax * FRAME_SIZE * 2, lane.stream))
+        if self.progressive:                                  # PCM and counters straight into the lane's host blocks
+            lane.sent = [0] * n
+            lane.voc.synthesize_ragged_progress_torch(feats[:n], counts, slots, lane.host_ptr, lane.done_ptr, stream=lane.stream)
+        else:
+            pcm = lane.pcm[: self.R * fmax * FRAME_SIZE].view(self.R, fmax * FRAME_SIZE)
+            lane.voc.synthesize_ragged_torch(feats[:n], counts, slots=slots, out=pcm, stream=lane.stream)
+            _lib.check(L.dss_memcpy_d2h_async(lane.host_ptr, pcm.data_ptr(), n * fmax * FRAME_SIZE * 2, lane.stream))
         _lib.check(L.dss_event_record(lane.done, lane.stream))
         lane.job, lane.job_frames = job, fmax
         self.jobs_launched += 1
+        now = time.perf_counter()
+        for sg in job:
+            sg.t_launch = now
+            self.lane_wait_ms.append((now - sg.t_close) * 1e3)
         for sg in job:
             sg.ready.refs -= 1
             if sg.ready.refs == 0:                            # every segment of that tick has been launched behind a wait on it
                 self._free_events.append(sg.ready.event)      # (list.append: atomic; submit pops under the lock)
 
+    def _progress(self, lane: _Lane, retired: bool):
+        """Progressive lanes: the pieces of the lane's job that have reached the host since the last look (all that is left
+        once ``retired``), appended to ``chunks`` in row order."""
+        job, fmax = lane.job, lane.job_frames
+        n = len(job)
+        if not retired:
+            _lib.check(self._L.dss_progress_read(lane.done_ptr, n, lane.counts.ctypes.data))    # acquire loads
+        pieces = progress_chunks([sg.length for sg in job], lane.sent, lane.counts, retired)
+        if not pieces:
+            return
+        host = lane.host[: n * fmax * FRAME_SIZE].reshape(n, fmax * FRAME_SIZE)
+        now = time.perf_counter()
+        out = []
+        for k, f0, f1, last in pieces:
+            sg = job[k]
+            out.append((sg.stream, sg.tag, f0 * FRAME_SIZE, host[k, f0 * FRAME_SIZE: f1 * FRAME_SIZE].copy(), last))
+            if f0 == 0:
+                self.first_pcm_latencies_ms.append((now - sg.t_close) * 1e3)
+                self.launch_to_first_pcm_ms.append((now - sg.t_launch) * 1e3)
+        with self._cv:
+            self.chunks += out
+
     def _retire(self, lane: _Lane):
         job, fmax = lane.job, lane.job_frames
+        if self.progressive:
+            self._progress(lane, retired=True)                # every last piece before the stream can start its next segment
         host = lane.host[: len(job) * fmax * FRAME_SIZE].reshape(len(job), fmax * FRAME_SIZE)
         now = time.perf_counter()
         done = [(sg.stream, sg.tag, host[k, : sg.length * FRAME_SIZE].copy()) for k, sg in enumerate(job)]
@@ -288,6 +362,8 @@ class SegmentSynthesisQueue:
             if lane.job is not None and _lib.check(self._L.dss_event_query(lane.done)) == 1:
                 self._retire(lane)
                 did = True
+            elif lane.job is not None and self.progressive:
+                self._progress(lane, retired=False)
         return self._dispatch() or did
 
     def _worker(self):
@@ -316,6 +392,20 @@ class SegmentSynthesisQueue:
             self._step()
         with self._cv:
             out, self.finished = self.finished, []
+        return out
+
+    def poll_chunks(self):
+        """Progressive mode: the pieces of segment audio that reached the host since the last call, as (stream, tag,
+        offset_samples, pcm int16 host array, last).  A stream's pieces come in frame order, all of a segment before any of its
+        next one; each segment ends with exactly one ``last`` piece (an empty one for a segment of 0 frames).  Never blocks.
+        (Unthreaded form: also looks at the jobs in flight, as ``poll()`` does.)"""
+        if not self.progressive:
+            raise RuntimeError("poll_chunks() needs SegmentSynthesisQueue(..., progressive=True)")
+        self._raise_worker_error()
+        if self._thread is None:
+            self._step()
+        with self._cv:
+            out, self.chunks = self.chunks, []
         return out
 
     @property

@@ -73,6 +73,12 @@ void dss_host_free(void *p);
  * small kernel that stores into the mapped host pages, NOT as a DMA copy: a DMA copy queued behind a long kernel holds up
  * every other copy of the process (the tick's packet upload) until that kernel has finished. */
 int dss_memcpy_d2h_async(void *host_dst, const void *d_src, size_t bytes, void *hip_stream);
+/* Explicitly coherent (fine-grained) page-locked memory (hipHostMallocCoherent): the device's stores reach it while a kernel
+ * is still running.  The only memory dss_lpcnet_batch_synthesize_ragged_progress_dev accepts.  Freed with dss_host_free. */
+void *dss_host_alloc_fine(size_t bytes);
+/* Reads n counters of a progressive call (host_frames_done) with acquire loads: once out[i] = v, the first v*160 samples of
+ * row i are in host_pcm.  For C hosts that do not want to reason about the memory model themselves. */
+int dss_progress_read(const int *host_frames_done, int n, int *out);
 
 /* ------------------------------------------------------------------------------------------------
  * Part 1 -- xiph LPCNet decoder symbols, as bound by extensions/lpcnet/cLPCNet.pxd:10-13
@@ -172,6 +178,18 @@ int dss_lpcnet_batch_synthesize_ragged_dev(dss_lpcnet_batch *b, const float *d_f
                                            short *d_pcm, void *hip_stream);
 int dss_lpcnet_batch_synthesize_ragged(dss_lpcnet_batch *b, const float *features, const int *slots,
                                        const int *counts, int n_utts, int n_frames, int feat_stride, short *pcm);
+/* Progressive form of the ragged call (opt-in; the whole-segment contract above stays the default).  Same rows, slots and
+ * counts as dss_lpcnet_batch_synthesize_ragged_dev; the PCM goes straight into host_pcm ([n_utts][n_frames*160] int16) while
+ * the kernel runs, and host_frames_done[i] counts the frames of row i already there: the bytes SoX receives, in order
+ * (local/units.py:531-538,550-552), a 10 ms frame at a time instead of a whole segment.  Read the counters with
+ * dss_progress_read (or acquire loads); counters only grow, and a row of count 0 stays at 0.  The library zeroes
+ * host_frames_done[0..n_utts) on the host before it enqueues anything.  Both host pointers must lie in blocks from
+ * dss_host_alloc_fine (host_pcm 16-byte aligned); pageable, cached page-locked or short buffers, null pointers, and a batch
+ * with trace or teacher forcing on give DSS_EINVAL, and nothing is enqueued.  Neither buffer may belong to a call that is
+ * still in flight.  Always one utterance per workgroup (the pair kernel has no progressive form). */
+int dss_lpcnet_batch_synthesize_ragged_progress_dev(dss_lpcnet_batch *b, const float *d_features, const int *slots,
+                                                    const int *counts, int n_utts, int n_frames, int feat_stride,
+                                                    short *host_pcm, int *host_frames_done, void *hip_stream);
 /* Kernel choice (uniform and ragged calls).  0 (default): one utterance per workgroup (csrc/lpcnet_sample.hip) while the
  * call has at most one row per CU, two utterances per workgroup -- carried as the two halves of packed fp32 instructions,
  * csrc/lpcnet_sample_pair.hip -- beyond (a uniform call is split: full rounds of two rows per CU on the pair kernel, a
