@@ -1440,6 +1440,8 @@ extern "C" int dss_hga_log_power(const double *data, int T, int C, int sr, float
     return DSS_OK;
 }
 
+struct DssHgaTrialDesc { long long in_row, out_row; int n, W, zero_rows, pad; };       // HgaTrialDesc of csrc/hga_kernels.hip
+
 struct dss_hga {
     int device;
     DssHgaDev d;
@@ -1455,6 +1457,15 @@ struct dss_hga {
     double *d_zs[2] = {nullptr, nullptr};                  // z-score mean / std on the device ...
     std::vector<double> zs_host[2];                        // ... and on the host (host-buffer entry points); empty = no z-score
     std::vector<double> zs_dev[2];                         // the values the resident device copies hold (dss_hga_set_zscore)
+    // trial lists (dss_hga_extract_trials*): bad-channel patches, the descriptor table and the host-buffer form's staging
+    std::vector<int> patch_dst, patch_cols, patch_off;     // empty = no patch
+    int *d_patch_dst = nullptr, *d_patch_cols = nullptr, *d_patch_off = nullptr;
+    std::vector<DssHgaTrialDesc> desc;
+    void *d_desc = nullptr;
+    std::vector<long long> single_rows;                    // output frames of the trials that emit one frame
+    long long *d_single = nullptr;
+    double *d_trec = nullptr, *d_tout = nullptr;
+    size_t desc_cap = 0, single_cap = 0, trec_cap = 0, tout_cap = 0;
 };
 
 static int hga_grow_rows(dss_hga *h, int need_rows)
@@ -1509,7 +1520,8 @@ extern "C" void dss_hga_destroy(dss_hga *h)
     if (!h) return;
     hipSetDevice(h->device);
     void *ptrs[] = {h->d.zi, h->d.rows, h->d_zi0[0], h->d_zi0[1], h->d_in, h->d_out, h->d_src_col, h->d_grid_of,
-                    h->d_comp_cols, h->d_comp_off, h->d_pre, h->d_raw, h->d_wire, h->d_zs[0], h->d_zs[1]};
+                    h->d_comp_cols, h->d_comp_off, h->d_pre, h->d_raw, h->d_wire, h->d_zs[0], h->d_zs[1],
+                    h->d_patch_dst, h->d_patch_cols, h->d_patch_off, h->d_desc, h->d_single, h->d_trec, h->d_tout};
     for (void *p : ptrs) if (p) hipFree(p);
     delete h;
 }
@@ -1728,6 +1740,281 @@ extern "C" int dss_hga_extract_raw(dss_hga *h, const double *raw, int n, double 
     DSS_HIP_CHECK(hipMemcpy(out, h->d_out, cnt * sizeof(double), hipMemcpyDeviceToHost));
     hga_host_finish(h, out, cnt);
     return W;
+}
+
+// ---- trial lists: a session's trials in one call (baseline_offline.py:45-60, prepare_corpus.py:42-52,179-199) -------------
+// Frames a FRESH extractor emits for one chunk of `len` rows: CASE 1 (pyx:104-107) from len rows, CASE 2 (pyx:111-122) one
+// zero-padded frame; a chunk no longer than the frame shift is what the reference's frame buffer must not be given (pyx:57).
+extern "C" int dss_hga_trial_frames_for(int fs, float wl, float ws, int len)
+{
+    const int shift = (int)(ws * fs), fl = (int)(wl * fs);
+    if (fs <= 0 || fl <= 0 || shift <= 0 || shift > fl) { dss_set_error("bad window shape"); return DSS_EINVAL; }
+    if (len <= shift) { dss_set_error("a trial of %d rows is not longer than the frame shift (%d rows)", len, shift); return DSS_EINVAL; }
+    const int W = dss_hga_num_windows(len >= fl ? len : fl, fs, wl, ws);
+    return W < 0 ? 0 : W;
+}
+
+extern "C" int dss_hga_trial_frames(const dss_hga *h, int len)
+{
+    if (!h) { dss_set_error("bad arguments"); return DSS_EINVAL; }
+    return dss_hga_trial_frames_for(h->d.fs, h->d.wl, h->d.ws, len);
+}
+
+// every trial inside the recording and long enough; returns the frames of the whole list
+extern "C" int dss_hga_check_trials(int fs, float wl, float ws, long long T_rec, int n_trials, const long long *start, const int *len)
+{
+    if (n_trials < 0 || T_rec < 0 || (n_trials && (!start || !len))) { dss_set_error("bad trial list"); return DSS_EINVAL; }
+    long long total = 0;
+    for (int i = 0; i < n_trials; ++i) {
+        if (start[i] < 0 || len[i] < 0 || start[i] + (long long)len[i] > T_rec) {
+            dss_set_error("trial %d (rows %lld .. %lld) lies outside the recording of %lld rows", i, start[i], start[i] + (long long)len[i], T_rec);
+            return DSS_EINVAL;
+        }
+        const int W = dss_hga_trial_frames_for(fs, wl, ws, len[i]);
+        if (W < 0) { dss_set_error("trial %d: %d rows are not longer than the frame shift", i, len[i]); return DSS_EINVAL; }
+        total += W;
+        if (total > 0x7fffffffLL) { dss_set_error("trial list emits more than 2^31 frames"); return DSS_EINVAL; }
+    }
+    return (int)total;
+}
+
+extern "C" int dss_hga_check_patches(int C, int n_patches, const int *dst_col, const int *nb_cols, const int *nb_off)
+{
+    if (C <= 0 || n_patches < 0 || (n_patches && (!dst_col || !nb_cols || !nb_off))) { dss_set_error("bad patch list"); return DSS_EINVAL; }
+    if (n_patches && nb_off[0] != 0) { dss_set_error("patch offsets must start at 0"); return DSS_EINVAL; }
+    std::vector<char> is_dst((size_t)C, 0);
+    for (int k = 0; k < n_patches; ++k) {
+        if (dst_col[k] < 0 || dst_col[k] >= C) { dss_set_error("patch %d: column %d outside 0..%d", k, dst_col[k], C - 1); return DSS_EINVAL; }
+        if (is_dst[dst_col[k]]) { dss_set_error("column %d is patched twice", dst_col[k]); return DSS_EINVAL; }
+        is_dst[dst_col[k]] = 1;
+        if (nb_off[k + 1] <= nb_off[k] || nb_off[k + 1] - nb_off[k] >= 128) { dss_set_error("patch %d: 1..127 neighbours supported", k); return DSS_EINVAL; }
+    }
+    for (int j = 0; j < (n_patches ? nb_off[n_patches] : 0); ++j) {
+        if (nb_cols[j] < 0 || nb_cols[j] >= C) { dss_set_error("neighbour column %d outside 0..%d", nb_cols[j], C - 1); return DSS_EINVAL; }
+        if (is_dst[nb_cols[j]]) { dss_set_error("neighbour column %d is itself patched", nb_cols[j]); return DSS_EINVAL; }
+    }
+    return DSS_OK;
+}
+
+// BadChannelCorrection.__call__ (local/common.py:286-291) in place on ONE call's frames (N, C), by numpy's own summation
+// order for np.mean(data[:, neighbours], axis=1): with N >= 2 the fancy-indexed copy is Fortran-ordered and is added one
+// column at a time (the sequential sum in list order, for 8 neighbours too); with N == 1 it is one contiguous row, which
+// numpy's pairwise kernel sums as eight running sums over blocks of eight, ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the
+// remainder in order (fewer than 8: sequential).  Neighbours are never patched columns (dss_hga_check_patches).
+static double hga_row_mean(const double *fr, const int *cols, int n, bool single)
+{
+    double sum;
+    if (!single || n < 8) {
+        sum = fr[cols[0]];
+        for (int j = 1; j < n; ++j) sum += fr[cols[j]];
+    } else {
+        double r[8];
+        for (int u = 0; u < 8; ++u) r[u] = fr[cols[u]];
+        int i = 8;
+        for (; i < n - (n % 8); i += 8)
+            for (int u = 0; u < 8; ++u) r[u] += fr[cols[i + u]];
+        sum = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (; i < n; ++i) sum += fr[cols[i]];
+    }
+    return sum / (double)n;
+}
+
+extern "C" int dss_hga_apply_patches(double *frames, long long N, int C, int n_patches, const int *dst_col, const int *nb_cols,
+                                     const int *nb_off)
+{
+    if (N < 0 || (N && !frames)) { dss_set_error("bad arguments"); return DSS_EINVAL; }
+    const int rc = dss_hga_check_patches(C, n_patches, dst_col, nb_cols, nb_off);
+    if (rc) return rc;
+    for (long long i = 0; i < N; ++i) {
+        double *fr = frames + (size_t)i * C;
+        for (int k = 0; k < n_patches; ++k)
+            fr[dst_col[k]] = hga_row_mean(fr, nb_cols + nb_off[k], nb_off[k + 1] - nb_off[k], N == 1);
+    }
+    return DSS_OK;
+}
+
+// np.vstack([np.mean(x, axis=0), np.std(x, axis=0)]) of a C-contiguous (N, C) array, in numpy's order: rows are added one
+// after the other (row 0, += row 1, ...), / N; std from d = x - mean, d * d summed the same way, / N, sqrt
+extern "C" int dss_hga_column_stats(const double *frames, long long N, int C, double *out)
+{
+    if (!frames || !out || N <= 0 || C <= 0) { dss_set_error("column statistics need at least one frame"); return DSS_EINVAL; }
+    double *mean = out, *sd = out + C;
+    for (int c = 0; c < C; ++c) mean[c] = frames[c];
+    for (long long i = 1; i < N; ++i)
+        for (int c = 0; c < C; ++c) mean[c] += frames[(size_t)i * C + c];
+    for (int c = 0; c < C; ++c) mean[c] = mean[c] / (double)N;
+    for (int c = 0; c < C; ++c) { const double d = frames[c] - mean[c]; sd[c] = d * d; }
+    for (long long i = 1; i < N; ++i)
+        for (int c = 0; c < C; ++c) { const double d = frames[(size_t)i * C + c] - mean[c]; sd[c] += d * d; }
+    for (int c = 0; c < C; ++c) sd[c] = sqrt(sd[c] / (double)N);
+    return DSS_OK;
+}
+
+extern "C" int dss_hga_column_stats_dev(const double *d_frames, long long N, int C, double *d_out, void *hip_stream)
+{
+    if (!d_frames || !d_out || N <= 0 || C <= 0) { dss_set_error("column statistics need at least one frame"); return DSS_EINVAL; }
+    int rc = dss_ensure_device();
+    if (rc) return rc;
+    return dss_launch_hga_colstats(d_frames, (long)N, C, d_out, (hipStream_t)hip_stream);
+}
+
+extern "C" int dss_hga_set_patches(dss_hga *h, int n_patches, const int *dst_col, const int *nb_cols, const int *nb_off)
+{
+    if (!h) { dss_set_error("bad arguments"); return DSS_EINVAL; }
+    if (!dst_col || n_patches == 0) n_patches = 0;
+    int rc = dss_hga_check_patches(h->d.C, n_patches, dst_col, nb_cols, nb_off);
+    if (rc) return rc;
+    DSS_HIP_CHECK(hipSetDevice(h->device));
+    int **dev[3] = {&h->d_patch_dst, &h->d_patch_cols, &h->d_patch_off};
+    for (int k = 0; k < 3; ++k) if (*dev[k]) { hipFree(*dev[k]); *dev[k] = nullptr; }
+    h->patch_dst.clear(); h->patch_cols.clear(); h->patch_off.clear();
+    if (!n_patches) return DSS_OK;
+    h->patch_dst.assign(dst_col, dst_col + n_patches);
+    h->patch_off.assign(nb_off, nb_off + n_patches + 1);
+    h->patch_cols.assign(nb_cols, nb_cols + nb_off[n_patches]);
+    rc = dev_upload<int>(h->patch_dst.data(), h->patch_dst.size(), &h->d_patch_dst);
+    rc |= dev_upload<int>(h->patch_cols.data(), h->patch_cols.size(), &h->d_patch_cols);
+    rc |= dev_upload<int>(h->patch_off.data(), h->patch_off.size(), &h->d_patch_off);
+    if (rc) { h->patch_dst.clear(); h->patch_cols.clear(); h->patch_off.clear(); return DSS_ENOMEM; }
+    return DSS_OK;
+}
+
+template <typename T>
+static int hga_grow(T **buf, size_t *cap, size_t need)
+{
+    if (need <= *cap) return DSS_OK;
+    if (*buf) hipFree(*buf);
+    *buf = nullptr; *cap = 0;
+    DSS_HIP_CHECK(hipMalloc((void **)buf, need * sizeof(T)));
+    *cap = need;
+    return DSS_OK;
+}
+
+// first and one-past-last recording row any trial reads
+static void hga_trial_hull(int n_trials, const long long *start, const int *len, long long *lo, long long *hi)
+{
+    *lo = start[0]; *hi = start[0] + len[0];
+    for (int i = 1; i < n_trials; ++i) {
+        if (start[i] < *lo) *lo = start[i];
+        if (start[i] + len[i] > *hi) *hi = start[i] + len[i];
+    }
+}
+
+// The trial list on device-resident rows.  d_rows holds recording rows row_base .. (c_in columns); `finish` = log, patch and
+// z-score on the device (the device-resident entry point) or none of them (the host-buffer one finishes on the host).
+static int hga_trials_run(dss_hga *h, const double *d_rows, long long row_base, int n_trials, const long long *start, const int *len,
+                          double *d_out, int apply_log, bool finish, hipStream_t st)
+{
+    const DssHgaDev &d = h->d;
+    long long lo, hi;
+    hga_trial_hull(n_trials, start, len, &lo, &hi);
+    const double *d_data = d_rows;
+    long long data_base = row_base;             // recording row that d_data's row 0 holds
+    if (h->c_raw) {
+        // the front end runs once over the rows the trials span (they overlap and cover most of a recording), not per trial
+        const long long span = hi - lo;
+        if (span > 0x7fffffffLL / (h->c_raw > d.C ? h->c_raw : d.C)) { dss_set_error("trial list spans too many rows for one front-end launch"); return DSS_EINVAL; }
+        int rc = hga_grow(&h->d_pre, &h->pre_cap, (size_t)span * d.C);
+        if (rc) return rc;
+        rc = dss_launch_hga_frontend(d_rows + (size_t)(lo - row_base) * h->c_raw, h->d_pre, 1, (int)span, h->c_raw, d.C, h->d_src_col,
+                                     h->d_grid_of, h->n_grids, h->d_comp_cols, h->d_comp_off, st);
+        if (rc) return rc;
+        d_data = h->d_pre;
+        data_base = lo;
+    }
+    // descriptor table, longest trial first: the long trials' blocks start first and the short ones fill the tail
+    std::vector<int> order((size_t)n_trials);
+    for (int i = 0; i < n_trials; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return len[a] > len[b]; });
+    std::vector<long long> out_row((size_t)n_trials);
+    long long total = 0;
+    for (int i = 0; i < n_trials; ++i) { out_row[i] = total; total += dss_hga_trial_frames_for(d.fs, d.wl, d.ws, len[i]); }
+    h->desc.resize((size_t)n_trials);
+    for (int k = 0; k < n_trials; ++k) {
+        const int i = order[k];
+        DssHgaTrialDesc &t = h->desc[k];
+        t.in_row = start[i] - data_base; t.out_row = out_row[i]; t.n = len[i];
+        t.W = dss_hga_trial_frames_for(d.fs, d.wl, d.ws, len[i]);
+        t.zero_rows = len[i] >= d.frame_length ? 0 : d.frame_length - len[i];
+        t.pad = 0;
+    }
+    {
+        DssHgaTrialDesc *dd = static_cast<DssHgaTrialDesc *>(h->d_desc);
+        int rc = hga_grow(&dd, &h->desc_cap, (size_t)n_trials);
+        h->d_desc = dd;
+        if (rc) return rc;
+    }
+    DSS_HIP_CHECK(hipMemcpyAsync(h->d_desc, h->desc.data(), sizeof(DssHgaTrialDesc) * (size_t)n_trials, hipMemcpyHostToDevice, st));
+    const bool patched = finish && !h->patch_dst.empty();
+    const bool zs = finish && d.zs_mean;
+    // the patch stands between the log and the z-score (prepare_corpus.py:166-170), so with patches the z-score leaves the
+    // trial kernel's epilogue and follows the patch kernel
+    int rc = dss_launch_hga_trials(d, d_data, h->d_desc, n_trials, h->d_zi0[0], h->d_zi0[1], d_out, finish ? apply_log : 0,
+                                   zs && !patched, st);
+    if (rc) return rc;
+    if (patched) {
+        // the reference patches trial by trial, and numpy sums the neighbours of a ONE-frame call differently (hga_patch_kernel)
+        h->single_rows.clear();
+        for (int i = 0; i < n_trials; ++i)
+            if (dss_hga_trial_frames_for(d.fs, d.wl, d.ws, len[i]) == 1) h->single_rows.push_back(out_row[i]);
+        if (!h->single_rows.empty()) {
+            rc = hga_grow(&h->d_single, &h->single_cap, h->single_rows.size());
+            if (rc) return rc;
+            DSS_HIP_CHECK(hipMemcpyAsync(h->d_single, h->single_rows.data(), sizeof(long long) * h->single_rows.size(), hipMemcpyHostToDevice, st));
+        }
+        rc = dss_launch_hga_patch(d_out, (long)total, d.C, (int)h->patch_dst.size(), h->d_patch_dst, h->d_patch_cols, h->d_patch_off,
+                                  h->d_single, (long)h->single_rows.size(), zs ? d.zs_mean : nullptr, zs ? d.zs_std : nullptr, st);
+    }
+    return rc ? rc : (int)total;
+}
+
+extern "C" int dss_hga_extract_trials_dev(dss_hga *h, const double *d_rec, long long T_rec, int n_trials, const long long *start,
+                                          const int *len, double *d_out, int apply_log, void *hip_stream)
+{
+    if (!h) { dss_set_error("bad arguments"); return DSS_EINVAL; }
+    const int total = dss_hga_check_trials(h->d.fs, h->d.wl, h->d.ws, T_rec, n_trials, start, len);
+    if (total <= 0) return total;
+    if (!d_rec || !d_out) { dss_set_error("bad arguments"); return DSS_EINVAL; }
+    DSS_HIP_CHECK(hipSetDevice(h->device));
+    return hga_trials_run(h, d_rec, 0, n_trials, start, len, d_out, apply_log, true, (hipStream_t)hip_stream);
+}
+
+extern "C" int dss_hga_extract_trials(dss_hga *h, const double *rec, long long T_rec, int n_trials, const long long *start,
+                                      const int *len, double *out)
+{
+    if (!h) { dss_set_error("bad arguments"); return DSS_EINVAL; }
+    const int total = dss_hga_check_trials(h->d.fs, h->d.wl, h->d.ws, T_rec, n_trials, start, len);
+    if (total <= 0) return total;
+    if (!rec || !out) { dss_set_error("bad arguments"); return DSS_EINVAL; }
+    DSS_HIP_CHECK(hipSetDevice(h->device));
+    const int c_in = h->c_raw ? h->c_raw : h->d.C;
+    long long lo, hi;
+    hga_trial_hull(n_trials, start, len, &lo, &hi);
+    // only the rows the trials span cross the bus, once, however the trials overlap
+    int rc = hga_grow(&h->d_trec, &h->trec_cap, (size_t)(hi - lo) * c_in);
+    if (!rc) rc = hga_grow(&h->d_tout, &h->tout_cap, (size_t)total * h->d.C);
+    if (rc) return rc;
+    DSS_HIP_CHECK(hipMemcpy(h->d_trec, rec + (size_t)lo * c_in, sizeof(double) * (size_t)(hi - lo) * c_in, hipMemcpyHostToDevice));
+    rc = hga_trials_run(h, h->d_trec, lo, n_trials, start, len, h->d_tout, 0, false, nullptr);
+    if (rc < 0) return rc;
+    const size_t cnt = (size_t)total * h->d.C;
+    DSS_HIP_CHECK(hipMemcpy(out, h->d_tout, cnt * sizeof(double), hipMemcpyDeviceToHost));
+    // host libm log (pyx:46; DESIGN.md "HGA log"), BadChannelCorrection, ZScoreNormalization: the reference's order
+    for (size_t k = 0; k < cnt; ++k) out[k] = log(out[k]);
+    if (!h->patch_dst.empty()) {
+        size_t row = 0;                         // trial by trial, as the reference's post-transform sees the frames
+        for (int i = 0; i < n_trials; ++i) {
+            const int W = dss_hga_trial_frames_for(h->d.fs, h->d.wl, h->d.ws, len[i]);
+            dss_hga_apply_patches(out + row * h->d.C, W, h->d.C, (int)h->patch_dst.size(), h->patch_dst.data(), h->patch_cols.data(),
+                                  h->patch_off.data());
+            row += (size_t)W;
+        }
+    }
+    if (!h->zs_host[0].empty()) {
+        const int C = h->d.C;
+        for (size_t k = 0; k < cnt; ++k) out[k] = (out[k] - h->zs_host[0][k % C]) / h->zs_host[1][k % C];
+    }
+    return total;
 }
 
 // ------------------------------------------------------------------------------------------------------

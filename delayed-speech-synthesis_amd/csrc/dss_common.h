@@ -227,5 +227,14 @@ int dss_launch_hga_frontend(const double *d_raw, double *d_pre, int S, int n, in
                             const int *grid_of, int n_grids, const int *comp_cols, const int *comp_off, hipStream_t s);
 int dss_launch_hga_wire(const float *d_payload, double *d_rows, int S, int C, int n, hipStream_t s);
 int dss_launch_hga_reset(const DssHgaDev &h, const double *d_zi_hg, const double *d_zi_fh, hipStream_t s);
+// one launch for n_trials fresh-extractor trials that are row ranges of one (rows, C) device array; d_desc is the device copy of
+// the descriptor table {int64 in_row, out_row; int32 n, W, zero_rows, pad} (csrc/hga_kernels.hip, HgaTrialDesc)
+int dss_launch_hga_trials(const DssHgaDev &h, const double *d_data, const void *d_desc, int n_trials, const double *d_zi_hg,
+                          const double *d_zi_fh, double *d_out, int apply_log, int with_zscore, hipStream_t s);
+// in place on (N, C) frames: the bad-channel patch (n_patches may be 0; d_single_rows: the frames of trials that emit one
+// frame, which numpy sums as a contiguous row), then the z-score when zs_mean is not NULL
+int dss_launch_hga_patch(double *d_frames, long N, int C, int n_patches, const int *dst_col, const int *nb_cols, const int *nb_off,
+                         const long long *d_single_rows, long n_single, const double *zs_mean, const double *zs_std, hipStream_t s);
+int dss_launch_hga_colstats(const double *d_frames, long N, int C, double *d_out, hipStream_t s);
 int dss_launch_log_power(const double *d_data, int T, int C, int sr, float wl, float ws, int W, double *d_out,
                          int apply_log, hipStream_t s);

@@ -365,6 +365,313 @@ hga_fused_kernel(const double *__restrict__ data, double *__restrict__ zi, doubl
 #undef HGF_FETCH
 }
 
+// ---- trial form: one launch for a list of trials of unequal length ----------------------------------------------------
+// hga_fused_kernel advances all streams by one n; a session's trials (baseline_offline.py:45-60, prepare_corpus.py:42-52) are
+// windows of unequal length into ONE recording, each fed to a FRESH HighGammaExtractor as a single chunk.  Here a block takes
+// (trial, 16-column group): its n, W, zero rows, first input row and first output frame come from a descriptor table, the
+// filter state starts at the unit-step state of sosfilt_zi (units.py:128-132) and nothing is written back -- no per-stream
+// zi / rowbuf is touched.  The per-step code, the ring, the window tables and the sequential window sum are those of
+// hga_fused_kernel, statement for statement (the body is repeated rather than shared so that the streaming kernel's code
+// generation cannot move); windows past HGF_WTAB take their row range from the float32 arithmetic directly, as there.
+// `data` is the recording (or its front-end output), (rows, C) row-major; trial i reads rows in_row .. in_row + n - 1 and
+// writes frames out_row .. out_row + W - 1 of the concatenated (sum W, C) output.  Every range is checked on the host.
+struct HgaTrialDesc { long long in_row, out_row; int n, W, zero_rows, pad; };
+
+__global__ void __launch_bounds__(256, 4)
+hga_trials_kernel(const double *__restrict__ data, const HgaTrialDesc *__restrict__ desc, double *__restrict__ out,
+                  const double *__restrict__ zi_hg, const double *__restrict__ zi_fh, HgaSos sos, int C, int cgroups, int nsec,
+                  int sr, float wl, float ws, int apply_log, int R, const double *__restrict__ zs_mean,
+                  const double *__restrict__ zs_std)
+{
+    __shared__ double xs[HGA_TT + 1][16];
+    __shared__ double ys[HGA_TT][16];
+    __shared__ double coef[16][5];
+    __shared__ int wtab[2][HGF_WTAB];
+    extern __shared__ __attribute__((aligned(16))) double ring[];         // [R][16]
+    const int tid = threadIdx.x, r = tid & 15, pib = tid >> 4;
+    const int trial = blockIdx.x / cgroups, cg = blockIdx.x - trial * cgroups;
+    const HgaTrialDesc d = desc[trial];
+    const int n = d.n, W = d.W, row0 = d.zero_rows;       // a fresh frame buffer: CASE 1 (row0 = 0) or CASE 2 (left zero pad)
+    const int col0 = cg * 16;
+    const int nsec2 = 2 * nsec;
+    const bool has_sec = r < nsec2;
+    const bool is_last = r == nsec2 - 1;
+    const int f = has_sec ? r / nsec : 0, q = has_sec ? r - f * nsec : 0;
+    if (tid < 16) {
+        const int ff = tid < nsec2 ? tid / nsec : 0, qq = tid < nsec2 ? tid - ff * nsec : 0;
+        coef[tid][0] = sos.k[ff][qq][0]; coef[tid][1] = sos.k[ff][qq][1]; coef[tid][2] = sos.k[ff][qq][2];
+        coef[tid][3] = sos.k[ff][qq][4]; coef[tid][4] = sos.k[ff][qq][5];
+    }
+    // units.py:128-132: every column starts at sosfilt_zi(sos), not scaled by the first sample
+    const double *z_src = f ? zi_fh : zi_hg;
+    double z0 = has_sec ? z_src[q * 2 + 0] : 0.0, z1 = has_sec ? z_src[q * 2 + 1] : 0.0;
+    for (int w = tid; w < W && w < HGF_WTAB; w += 256) {
+        const int st = hga_win_start(w, ws, sr);
+        wtab[0][w] = st;
+        wtab[1][w] = hga_win_stop(st, wl, sr);
+    }
+    for (int idx = tid; idx < row0 * 16; idx += 256) ring[idx] = 0.0;     // CASE 2, pyx:116 (row0 <= frame length <= R)
+    __syncthreads();
+    const double b0 = coef[r][0], b1 = coef[r][1], b2 = coef[r][2], a1 = coef[r][3], a2 = coef[r][4];
+    const int steps = n + nsec2 - 1;
+    double y = 0.0;
+    int w_next = 0;
+    const int lp = tid & 15, ltt = tid >> 4;
+    const bool lvalid = col0 + lp < C;
+    const double *lcol = data + (size_t)d.in_row * C + (lvalid ? col0 + lp : 0);
+    double pre[HGA_TT / 16];
+#define HGT_FETCH(BASE)                                                                          \
+    _Pragma("unroll") for (int j = 0; j < HGA_TT / 16; ++j) {                                        \
+        const int t = (BASE) + ltt + 16 * j;                                                     \
+        pre[j] = (lvalid && t < n) ? lcol[(size_t)t * C] : 0.0;                                  \
+    }
+    HGT_FETCH(0)
+    int tile_pos = (row0 + R * 16 - (nsec2 - 1)) % R;
+    for (int base = 0; base < steps; base += HGA_TT) {
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < HGA_TT / 16; ++j) xs[ltt + 16 * j][lp] = pre[j];
+        if (base + HGA_TT < steps) { HGT_FETCH(base + HGA_TT) }
+        __syncthreads();
+        const int kend = min(base + HGA_TT, steps);
+        int k = base;
+        for (; k < kend && (k < nsec2 - 1 || k >= n); ++k) {
+            const double in = hga_shift_in(xs[k - base][pib], y);
+            const int t = k - r;
+            if (has_sec && t >= 0 && t < n) {
+                HGA_BIQUAD(in)
+                if (is_last) ys[k - base][pib] = y;
+            }
+        }
+        const int ksteady = min(kend, n);
+        {
+            const double *xp = &xs[k - base][pib];
+            double xcur = *xp;
+            double *const yl = &ys[k - base][pib];
+            int kk = 0;
+            for (; k + 4 <= ksteady; k += 4, kk += 4) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const double xnext = xp[16 * (kk + u + 1)];
+                    const double in = hga_shift_in(xcur, y);
+                    HGA_BIQUAD(in)
+                    if (is_last) yl[16 * (kk + u)] = y;
+                    xcur = xnext;
+                }
+            }
+            for (; k < ksteady; ++k, ++kk) {
+                const double xnext = xp[16 * (kk + 1)];
+                const double in = hga_shift_in(xcur, y);
+                HGA_BIQUAD(in)
+                if (is_last) yl[16 * kk] = y;
+                xcur = xnext;
+            }
+        }
+        for (; k < kend; ++k) {
+            const double in = hga_shift_in(xs[k - base][pib], y);
+            const int t = k - r;
+            if (has_sec && t >= 0 && t < n) {
+                HGA_BIQUAD(in)
+                if (is_last) ys[k - base][pib] = y;
+            }
+        }
+        __syncthreads();
+        for (int idx = tid; idx < HGA_TT * 16; idx += 256) {
+            const int tt = idx >> 4, p = idx & 15;
+            const int t = base + tt - (nsec2 - 1);
+            int pos = tile_pos + tt;
+            if (pos >= R) pos -= R;
+            if (base + tt < kend && t >= 0 && t < n) ring[pos * 16 + p] = ys[tt][p];
+        }
+        tile_pos += HGA_TT;
+        if (tile_pos >= R) tile_pos -= R;
+        __syncthreads();
+        int t_done = kend - (nsec2 - 1);
+        t_done = t_done < 0 ? 0 : (t_done > n ? n : t_done);
+        const int rows_done = row0 + t_done;
+        {
+            const int p = tid & 15, wi = tid >> 4;
+            const int c = col0 + p;
+            for (int w = w_next + wi; w < W; w += 16) {
+                const int start = w < HGF_WTAB ? wtab[0][w] : hga_win_start(w, ws, sr);
+                const int stop = w < HGF_WTAB ? wtab[1][w] : hga_win_stop(start, wl, sr);
+                if (stop > rows_done) break;
+                double sum = 0.0;
+                int pos = start % R, left = stop - start;
+                while (left > 0) {
+                    const int run = min(left, R - pos);
+                    const double *rp = ring + pos * 16 + p;
+                    int i = 0;
+                    for (; i + 8 <= run; i += 8) {
+                        double v[8];
+#pragma unroll
+                        for (int u = 0; u < 8; ++u) v[u] = rp[(i + u) * 16];
+#pragma unroll
+                        for (int u = 0; u < 8; ++u) sum += v[u] * v[u];
+                    }
+                    for (; i < run; ++i) {
+                        const double v = rp[i * 16];
+                        sum += v * v;
+                    }
+                    left -= run;
+                    pos = 0;
+                }
+                if (c < C) {
+                    const double pw = sum / (double)(stop - start) + 0.01;
+                    double o = apply_log ? log(pw) : pw;
+                    if (zs_mean) o = (o - zs_mean[c]) / zs_std[c];
+                    out[((size_t)d.out_row + w) * C + c] = o;
+                }
+            }
+            while (w_next < W && (w_next < HGF_WTAB ? wtab[1][w_next] : hga_win_stop(hga_win_start(w_next, ws, sr), wl, sr)) <= rows_done)
+                ++w_next;
+        }
+    }
+#undef HGT_FETCH
+}
+
+int dss_launch_hga_trials(const DssHgaDev &h, const double *d_data, const void *d_desc, int n_trials, const double *d_zi_hg,
+                          const double *d_zi_fh, double *d_out, int apply_log, int with_zscore, hipStream_t st)
+{
+    if (n_trials <= 0) return DSS_OK;
+    HgaSos sos;
+    memcpy(&sos, h.sos, sizeof(sos));
+    const int shift = h.frame_length - h.overlap;
+    int ring_rows = h.frame_length + shift + HGA_TT + 2;
+    ring_rows = (ring_rows + 7) & ~7;
+    const size_t ring_bytes = (size_t)ring_rows * 16 * sizeof(double);
+    if (ring_bytes > 40 * 1024) {
+        dss_set_error("HGA trials: a frame of %d rows does not fit the kernel's ring", h.frame_length);
+        return DSS_EINVAL;
+    }
+    const int cgroups = (h.C + 15) / 16;
+    const long blocks = (long)n_trials * cgroups;
+    if (blocks > 0x7fffffffL) { dss_set_error("HGA trials: too many blocks"); return DSS_EINVAL; }
+    hipLaunchKernelGGL(hga_trials_kernel, dim3((unsigned)blocks), dim3(256), ring_bytes, st, d_data,
+                       static_cast<const HgaTrialDesc *>(d_desc), d_out, d_zi_hg, d_zi_fh, sos, h.C, cgroups, h.nsec, h.fs, h.wl, h.ws,
+                       apply_log, ring_rows, with_zscore ? h.zs_mean : nullptr, with_zscore ? h.zs_std : nullptr);
+    DSS_HIP_CHECK(hipGetLastError());
+    return DSS_OK;
+}
+
+// BadChannelCorrection.__call__ (local/common.py:286-291) on log-power frames: lane = (frame, corrected channel).  The mean
+// of the neighbour columns is numpy's np.mean(data[:, neighbours], axis=1): for two or more frames the fancy-indexed copy is
+// Fortran-ordered and numpy adds it one column at a time -- the SEQUENTIAL sum in list order, for 8 neighbours too; a SINGLE
+// frame (a trial that emits one: the reference patches trial by trial) is a contiguous row, which numpy sums with its
+// pairwise kernel: eight running sums over blocks of eight, ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the remainder in
+// order (fewer than 8 elements: sequential).  One division follows.  Neighbours are never corrected channels themselves
+// (checked on the host), so the patch runs in place.  rows: the frames to patch (NULL: all N, sequential rule).
+__device__ __forceinline__ double hga_row_mean(const double *fr, const int *__restrict__ cols, int a, int b, bool single)
+{
+    const int n = b - a;
+    double sum;
+    if (!single || n < 8) {
+        sum = fr[cols[a]];
+        for (int j = a + 1; j < b; ++j) sum += fr[cols[j]];
+    } else {
+        double r[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) r[u] = fr[cols[a + u]];
+        int i = 8;
+        for (; i < n - (n % 8); i += 8) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) r[u] += fr[cols[a + i + u]];
+        }
+        sum = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (; i < n; ++i) sum += fr[cols[a + i]];
+    }
+    return sum / (double)n;
+}
+
+__global__ void __launch_bounds__(256)
+hga_patch_kernel(double *__restrict__ frames, long N, int C, int n_patches, const int *__restrict__ dst_col,
+                 const int *__restrict__ nb_cols, const int *__restrict__ nb_off, const long long *__restrict__ rows)
+{
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= N * n_patches) return;
+    const long i = gid / n_patches;
+    const int k = (int)(gid - i * n_patches);
+    double *fr = frames + (size_t)(rows ? rows[i] : i) * C;
+    fr[dst_col[k]] = hga_row_mean(fr, nb_cols, nb_off[k], nb_off[k + 1], rows != nullptr);
+}
+
+// ZScoreNormalization behind the patch (the trial kernel's own epilogue cannot run before it)
+__global__ void __launch_bounds__(256)
+hga_zscore_kernel(double *__restrict__ frames, long total, int C, const double *__restrict__ zs_mean, const double *__restrict__ zs_std)
+{
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= total) return;
+    const int c = (int)(gid % C);
+    frames[gid] = (frames[gid] - zs_mean[c]) / zs_std[c];
+}
+
+int dss_launch_hga_patch(double *d_frames, long N, int C, int n_patches, const int *dst_col, const int *nb_cols, const int *nb_off,
+                         const long long *d_single_rows, long n_single, const double *zs_mean, const double *zs_std, hipStream_t st)
+{
+    if (N <= 0) return DSS_OK;
+    if (n_patches > 0) {
+        const long lanes = N * n_patches;
+        hipLaunchKernelGGL(hga_patch_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, d_frames, N, C, n_patches,
+                           dst_col, nb_cols, nb_off, nullptr);
+        DSS_HIP_CHECK(hipGetLastError());
+        if (n_single > 0) {         // the frames of single-frame trials again, by numpy's rule for one contiguous row
+            const long l1 = n_single * n_patches;
+            hipLaunchKernelGGL(hga_patch_kernel, dim3((unsigned)((l1 + 255) / 256)), dim3(256), 0, st, d_frames, n_single, C,
+                               n_patches, dst_col, nb_cols, nb_off, d_single_rows);
+            DSS_HIP_CHECK(hipGetLastError());
+        }
+    }
+    if (zs_mean) {
+        const long total = N * C;
+        hipLaunchKernelGGL(hga_zscore_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_frames, total, C, zs_mean,
+                           zs_std);
+        DSS_HIP_CHECK(hipGetLastError());
+    }
+    return DSS_OK;
+}
+
+// np.mean / np.std over axis 0 of a C-contiguous (N, C) array: numpy adds whole rows in order, so column c's sum is
+// row 0, += row 1, ... (no pairwise tree on this axis); std uses that mean, d = x - m, d * d summed in the same order, / N,
+// sqrt.  One lane per column walks the rows -- the order is the contract, the sum is NOT split.  Eight loads in flight.
+__global__ void __launch_bounds__(64)
+hga_colstats_kernel(const double *__restrict__ frames, long N, int C, double *__restrict__ out)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const double *col = frames + c;
+    double sum = col[0];
+    long i = 1;
+    for (; i + 8 <= N; i += 8) {
+        double v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = col[(size_t)(i + u) * C];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) sum += v[u];
+    }
+    for (; i < N; ++i) sum += col[(size_t)i * C];
+    const double m = sum / (double)N;
+    double d0 = col[0] - m;
+    double sq = d0 * d0;
+    i = 1;
+    for (; i + 8 <= N; i += 8) {
+        double v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = col[(size_t)(i + u) * C];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { const double dd = v[u] - m; sq += dd * dd; }
+    }
+    for (; i < N; ++i) { const double dd = col[(size_t)i * C] - m; sq += dd * dd; }
+    out[c] = m;
+    out[C + c] = sqrt(sq / (double)N);
+}
+
+int dss_launch_hga_colstats(const double *d_frames, long N, int C, double *d_out, hipStream_t st)
+{
+    hipLaunchKernelGGL(hga_colstats_kernel, dim3((C + 63) / 64), dim3(64), 0, st, d_frames, N, C, d_out);
+    DSS_HIP_CHECK(hipGetLastError());
+    return DSS_OK;
+}
+
 // ---- stage 2: windowed mean power ---------------------------------------------------------------------------------
 // A 256-thread block takes 8 consecutive windows x 32 consecutive channels of one stream: the rows those windows cover
 // (50 + 7*10 for the reference's 50 ms / 10 ms at 1 kHz) are staged once through LDS in 256-byte row segments instead

@@ -111,6 +111,16 @@ def _declare(L):
         "dss_hga_extract_wire_dev": (i, [vp, vp, i, vp, i, vp]),
         "dss_hga_set_zscore": (i, [vp, vp, vp]),
         "dss_selftest_hga_force_path": (i, [vp, i]),
+        "dss_hga_trial_frames": (i, [vp, i]),
+        "dss_hga_trial_frames_for": (i, [i, f, f, i]),
+        "dss_hga_check_trials": (i, [i, f, f, C.c_longlong, i, vp, vp]),
+        "dss_hga_extract_trials": (i, [vp, vp, C.c_longlong, i, vp, vp, vp]),
+        "dss_hga_extract_trials_dev": (i, [vp, vp, C.c_longlong, i, vp, vp, vp, i, vp]),
+        "dss_hga_set_patches": (i, [vp, i, vp, vp, vp]),
+        "dss_hga_check_patches": (i, [i, i, vp, vp, vp]),
+        "dss_hga_apply_patches": (i, [vp, C.c_longlong, i, i, vp, vp, vp]),
+        "dss_hga_column_stats": (i, [vp, C.c_longlong, i, vp]),
+        "dss_hga_column_stats_dev": (i, [vp, C.c_longlong, i, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

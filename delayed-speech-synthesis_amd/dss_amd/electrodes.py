@@ -54,12 +54,49 @@ def reference_frontend(bad_channels: Sequence[int] = BAD_CHANNELS):
 
 
 def frontend_from_transforms(select_all, car, select_sub):
-    """Same triple from three transform OBJECTS of the user's ``local.common`` (duck-typed by attribute)."""
+    """Same triple from three transform OBJECTS of the user's ``local.common`` (duck-typed by attribute).
+    ``select_sub=None`` gives the offline form without the speech-area selection: all (128) referenced channels."""
     sel1 = np.asarray(select_all.grid_mapping, dtype=np.int64)          # raw column of each mid channel
-    sel2 = np.asarray(select_sub.speech_grid_mapping, dtype=np.int64)   # mid channel of each output channel
+    if select_sub is None:
+        # the offline chain (prepare_corpus.py:147-157) stops behind the referencing: every mid channel is an output channel
+        sel2 = np.arange(len(sel1), dtype=np.int64)
+    else:
+        sel2 = np.asarray(select_sub.speech_grid_mapping, dtype=np.int64)   # mid channel of each output channel
     grid_of_mid = np.full(len(sel1), -1, dtype=np.int64)
     comp_lists = []
     for g, (used, applied) in enumerate(zip(car.selection_masks_computation, car.selection_masks_application)):
         grid_of_mid[np.nonzero(applied)[0]] = g
         comp_lists.append(sel1[np.nonzero(used)[0]])                    # ascending mid index = numpy's summation order
     return sel1[sel2], grid_of_mid[sel2], comp_lists
+
+
+def patches_from_correction(correction) -> List[Tuple[int, np.ndarray]]:
+    """``[(column, neighbour columns)]`` of a ``BadChannelCorrection`` OBJECT of the user's ``local.common``
+    (common.py:220-305), duck-typed on ``.patches`` -- for ``HgaExtractorGPU.set_patches``."""
+    out = []
+    for loc, neighbours in correction.patches:
+        loc = np.asarray(loc).reshape(-1)
+        if loc.size != 1:
+            raise ValueError("a corrected channel must sit in exactly one column of the layout")
+        out.append((int(loc[0]), np.asarray(neighbours, dtype=np.int64).reshape(-1)))
+    return out
+
+
+def neighbour_patches(channels: Sequence[int], grids: Sequence[np.ndarray], layout) -> List[Tuple[int, np.ndarray]]:
+    """The patches ``BadChannelCorrection(channels, grids, layout)`` holds, derived without ``scipy.ndimage``: each
+    corrected channel is replaced by the mean of its 8-neighbourhood inside its own grid, minus the neighbours that are
+    corrected themselves, in row-major order of the grid array as given (the order boolean indexing walks it in)."""
+    layout = np.asarray(layout)
+    corrected = {int(c) for c in channels}
+    out = []
+    for ch in channels:
+        grid = next((np.asarray(g) for g in grids if ch in np.asarray(g)), None)
+        if grid is None:
+            raise IndexError("Channel could not be found in given grids.")
+        (row,), (col,) = np.where(grid == ch)
+        neighbours = [int(grid[r, c]) for r in range(max(row - 1, 0), min(row + 2, grid.shape[0]))
+                      for c in range(max(col - 1, 0), min(col + 2, grid.shape[1]))
+                      if (r, c) != (row, col) and int(grid[r, c]) not in corrected]
+        (dst,) = np.where(layout == ch)[0]
+        out.append((int(dst), np.array([np.where(layout == nb)[0][0] for nb in neighbours], dtype=np.int64)))
+    return out

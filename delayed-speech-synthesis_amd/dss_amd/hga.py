@@ -68,6 +68,71 @@ def log_power(data: np.ndarray, sr: int, wl: float, ws: float) -> np.ndarray:
     return out
 
 
+def trial_frames(length: int, fs: int = 1000, window_length: float = 0.05, window_shift: float = 0.01) -> int:
+    """Frames a fresh extractor emits for one trial of ``length`` rows (dss_hga_trial_frames_for; needs no GPU)."""
+    return _lib.check(_lib.load().dss_hga_trial_frames_for(int(fs), window_length, window_shift, int(length)))
+
+
+def _trial_arrays(trials):
+    """[(start, length)] -> contiguous int64 starts, int32 lengths (values that do not fit are left for the C checks to refuse)."""
+    t = np.asarray(list(trials), dtype=np.int64).reshape(-1, 2)
+    if np.any(np.abs(t[:, 1]) > 2**31 - 1):
+        raise _lib.DssError("trial length does not fit 32 bits")
+    return np.ascontiguousarray(t[:, 0]), np.ascontiguousarray(t[:, 1].astype(np.int32))
+
+
+def check_trials(n_rows: int, trials, fs: int = 1000, window_length: float = 0.05, window_shift: float = 0.01) -> int:
+    """The argument checks of ``extract_trials`` on their own: total frames of ``[(start, length)]`` in a recording of
+    ``n_rows`` rows, DssError for a range outside it or a length not above the frame shift (needs no GPU)."""
+    start, length = _trial_arrays(trials)
+    return _lib.check(_lib.load().dss_hga_check_trials(int(fs), window_length, window_shift, int(n_rows), len(start),
+                                                       start.ctypes.data, length.ctypes.data))
+
+
+def _patch_arrays(patches):
+    dst = np.ascontiguousarray([int(p[0]) for p in patches], dtype=np.int32)
+    lists = [np.asarray(p[1], dtype=np.int32).reshape(-1) for p in patches]
+    cols = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0, np.int32), dtype=np.int32)
+    off = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(c) for c in lists])]), dtype=np.int32)
+    return dst, cols, off
+
+
+def apply_patches(frames: np.ndarray, patches) -> np.ndarray:
+    """BadChannelCorrection.__call__ (local/common.py:286-291) on host frames (N, C) with ``[(column, neighbour columns)]``
+    patches, bit-identical to the numpy class called on the same frames -- numpy sums the neighbours of a single frame
+    pairwise and those of two or more sequentially, so frames are passed as the reference passes them: trial by trial
+    (dss_hga_apply_patches; needs no GPU).  Returns a corrected copy."""
+    out = np.array(frames, dtype=np.float64, order="C")
+    if out.ndim != 2:
+        raise ValueError("frames must be (N, C)")
+    dst, cols, off = _patch_arrays(patches)
+    _lib.check(_lib.load().dss_hga_apply_patches(out.ctypes.data, out.shape[0], out.shape[1], len(dst), dst.ctypes.data,
+                                                 cols.ctypes.data, off.ctypes.data))
+    return out
+
+
+def column_stats(frames: np.ndarray) -> np.ndarray:
+    """``np.vstack([frames.mean(axis=0), frames.std(axis=0)])`` of host frames (N, C), in numpy's summation order and
+    therefore bit-identical to it (dss_hga_column_stats; needs no GPU)."""
+    x = np.ascontiguousarray(frames, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError("frames must be (N, C)")
+    out = np.empty((2, x.shape[1]), dtype=np.float64)
+    _lib.check(_lib.load().dss_hga_column_stats(x.ctypes.data, x.shape[0], x.shape[1], out.ctypes.data))
+    return out
+
+
+def column_stats_torch(frames, stream=None):
+    """The same statistics of a CUDA float64 (N, C) tensor on the device -> CUDA (2, C) (dss_hga_column_stats_dev)."""
+    import torch
+    L = _lib.require_gpu()
+    assert frames.is_cuda and frames.dtype == torch.float64 and frames.is_contiguous() and frames.dim() == 2
+    out = torch.empty((2, frames.shape[1]), dtype=torch.float64, device=frames.device)
+    s = torch.cuda.current_stream(frames.device).cuda_stream if stream is None else stream
+    _lib.check(L.dss_hga_column_stats_dev(frames.data_ptr(), frames.shape[0], frames.shape[1], out.data_ptr(), s))
+    return out
+
+
 class HgaExtractorGPU:
     """n_streams independent HighGammaExtractor states (filter state + warm-start frame buffer) on one GPU."""
 
@@ -111,6 +176,53 @@ class HgaExtractorGPU:
         if m.shape != (self.C,) or sd.shape != (self.C,):
             raise ValueError(f"means / stds must have shape ({self.C},)")
         _lib.check(self._L.dss_hga_set_zscore(self._h, m.ctypes.data, sd.ctypes.data))
+
+    # ---- a session's trials in one call (dss_hga_extract_trials*) -------------------------------------------
+    def set_patches(self, patches=None):
+        """BadChannelCorrection on the frames of ``extract_trials*``, after the log and before the z-score:
+        ``[(column, neighbour columns)]`` (``electrodes.patches_from_correction`` / ``neighbour_patches``); None clears."""
+        if not patches:
+            _lib.check(self._L.dss_hga_set_patches(self._h, 0, None, None, None))
+            return
+        dst, cols, off = _patch_arrays(patches)
+        _lib.check(self._L.dss_hga_set_patches(self._h, len(dst), dst.ctypes.data, cols.ctypes.data, off.ctypes.data))
+
+    def trial_frames(self, length: int) -> int:
+        return _lib.check(self._L.dss_hga_trial_frames(self._h, int(length)))
+
+    def extract_trials(self, recording: np.ndarray, trials) -> np.ndarray:
+        """``recording`` (T, c_in) float64 host, ``trials`` [(start, length)] -> (sum W_i, C) host frames: each trial through a
+        FRESH extractor as one chunk, all in one launch, bit-identical to the reference chain.  Streaming state untouched."""
+        rec = np.ascontiguousarray(recording, dtype=np.float64)
+        c_in = getattr(self, "c_raw", None) or self.C
+        if rec.ndim != 2 or rec.shape[1] != c_in:
+            raise ValueError(f"expected (T, {c_in}), got {rec.shape}")
+        start, length = _trial_arrays(trials)
+        total = _lib.check(self._L.dss_hga_check_trials(self.fs, self.wl, self.ws, rec.shape[0], len(start), start.ctypes.data,
+                                                        length.ctypes.data))
+        out = np.empty((total, self.C), dtype=np.float64)
+        got = _lib.check(self._L.dss_hga_extract_trials(self._h, rec.ctypes.data, rec.shape[0], len(start), start.ctypes.data,
+                                                        length.ctypes.data, out.ctypes.data))
+        assert got == total
+        return out
+
+    def extract_trials_torch(self, recording, trials, apply_log: bool = True, stream=None):
+        """Device-resident form: CUDA float64 (T, c_in) -> CUDA (sum W_i, C); OCML log, patch and z-score on the device."""
+        import torch
+        c_in = getattr(self, "c_raw", None) or self.C
+        assert recording.is_cuda and recording.dtype == torch.float64 and recording.is_contiguous()
+        if recording.dim() != 2 or recording.shape[1] != c_in:
+            raise ValueError(f"expected (T, {c_in}), got {tuple(recording.shape)}")
+        start, length = _trial_arrays(trials)
+        total = _lib.check(self._L.dss_hga_check_trials(self.fs, self.wl, self.ws, recording.shape[0], len(start),
+                                                        start.ctypes.data, length.ctypes.data))
+        out = torch.empty((total, self.C), dtype=torch.float64, device=recording.device)
+        s = torch.cuda.current_stream(recording.device).cuda_stream if stream is None else stream
+        got = _lib.check(self._L.dss_hga_extract_trials_dev(self._h, recording.data_ptr(), recording.shape[0], len(start),
+                                                            start.ctypes.data, length.ctypes.data, out.data_ptr(),
+                                                            int(apply_log), s))
+        assert got == total
+        return out
 
     def _force_path(self, path: int):
         """Tests / A-B timing only: 0 choose, 1 hga_fused_kernel, 2 three launches (dss_selftest_hga_force_path)."""

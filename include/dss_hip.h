@@ -282,6 +282,46 @@ int dss_hga_extract_wire_dev(dss_hga *h, const float *d_payload, int n, double *
  * points then return z-scored frames (hga_fused_kernel's epilogue, or hga_window_kernel's in the three-launch form); the
  * host-buffer ones apply it on the host after their host-libm log. */
 int dss_hga_set_zscore(dss_hga *h, const double *means, const double *stds);
+/* ---- a session's trials in one call (baseline_offline.py:45-60, prepare_corpus.py:42-52,179-199) ----
+ * The reference builds a FRESH HighGammaExtractor per trial and feeds it rows start .. start+len of one recording as a single
+ * chunk.  These entry points do that for a whole trial list with one extractor launch: filters, front end and z-score are the
+ * handle's, every trial starts from the unit-step filter state and an empty frame buffer (CASE 1 when len >= one frame,
+ * CASE 2 -- left zero pad to one frame -- when frame shift < len < frame; len <= frame shift is an error, pyx:57), and the
+ * handle's streaming state (dss_hga_extract*) is neither read nor written.  rec: (T_rec, c_in) float64 row-major, c_in = c_raw
+ * with a front end configured, else n_channels; trial ranges may overlap.  out: (sum of W_i, n_channels), trial after trial in
+ * list order.  Every range and length is checked on the host before anything is launched.  Returns the number of frames
+ * written or a negative error. */
+/* Frames of one trial of `len` rows; negative for a rejected length.  The _for form needs no handle (and no device). */
+int dss_hga_trial_frames(const dss_hga *h, int len);
+int dss_hga_trial_frames_for(int fs, float window_length, float window_shift, int len);
+/* The argument checks of the two extract_trials entry points on their own: frames of the whole list, or a negative error. */
+int dss_hga_check_trials(int fs, float window_length, float window_shift, long long T_rec, int n_trials,
+                         const long long *start, const int *len);
+/* Host buffers; host libm log, then patch and z-score on the host: bit-identical to the reference chain. */
+int dss_hga_extract_trials(dss_hga *h, const double *rec, long long T_rec, int n_trials, const long long *start,
+                           const int *len, double *out);
+/* Device-resident; OCML log (<= 1 ulp, as dss_hga_extract_dev), patch and z-score on the device.  start / len are HOST arrays.
+ * The call returns once the launches are queued on hip_stream; one call per handle may be in flight. */
+int dss_hga_extract_trials_dev(dss_hga *h, const double *d_rec, long long T_rec, int n_trials, const long long *start,
+                               const int *len, double *d_out, int apply_log, void *hip_stream);
+/* BadChannelCorrection (local/common.py:220-305) on the frames of the trial entry points, after the log and before the
+ * z-score, trial by trial as the reference's post-transform runs: column dst_col[k] = mean of columns
+ * nb_cols[nb_off[k] .. nb_off[k+1]) in the order numpy's np.mean(data[:, neighbours], axis=1) adds them -- the SEQUENTIAL sum
+ * in list order when the trial has two or more frames (for 8 neighbours too), numpy's pairwise kernel (eight running sums,
+ * ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), remainder in order; sequential below 8 elements) when it has ONE frame -- and one
+ * division.  Neighbours are read from the uncorrected frame: a neighbour that is itself a patched column is an error, as are
+ * columns >= n_channels and lists of 128 or more.  NULL / 0 clears. */
+int dss_hga_set_patches(dss_hga *h, int n_patches, const int *dst_col, const int *nb_cols, const int *nb_off);
+int dss_hga_check_patches(int n_channels, int n_patches, const int *dst_col, const int *nb_cols, const int *nb_off);
+/* The same patch on the host frames (N, C) of ONE call of the reference's class, in place (N == 1: the one-frame rule);
+ * needs no handle. */
+int dss_hga_apply_patches(double *frames, long long N, int C, int n_patches, const int *dst_col, const int *nb_cols,
+                          const int *nb_off);
+/* out (2, C) = vstack([np.mean(frames, axis=0), np.std(frames, axis=0)]) in numpy's summation order for a C-contiguous
+ * (N, C) array: rows added one after the other, / N; std from d = x - mean, d * d, summed the same way, / N, sqrt.  Bit-identical
+ * to numpy on the same frames, on the host and on the device (one lane per column walks the rows: the order is the contract). */
+int dss_hga_column_stats(const double *frames, long long N, int C, double *out);
+int dss_hga_column_stats_dev(const double *d_frames, long long N, int C, double *d_out, void *hip_stream);
 /* Tests and A/B timing only: which kernel form serves this extractor.  0 = choose (default: hga_fused_kernel; three
  * launches when its ring does not fit LDS), 1 = hga_fused_kernel, 2 = the three-launch form. */
 int dss_selftest_hga_force_path(dss_hga *h, int path);
