@@ -1,0 +1,274 @@
+// csrc/dss_avad.cpp -- host side of Part 7 of include/dss_hip.h: acoustic voice-activity labels over a trial list.
+//
+// Owns the tables (window, twiddles, the mel matrix's nonzero runs), the descriptor and tile tables of a call and the
+// staging of the host-buffer form; the arithmetic of steps 3-5 runs in csrc/acoustic_vad.hip only.  Every check and the
+// threshold / vote of one trial are handle-free host functions, so they are testable without a device.
+#include <math.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "acoustic_vad.h"
+#include "dss_host.h"
+
+struct dss_avad {
+    int device = 0;
+    dss_avad_params p;
+    DssAvadDev d;
+    double *d_win = nullptr, *d_tw = nullptr, *d_mel_w = nullptr;
+    int *d_band_lo = nullptr, *d_band_off = nullptr;
+    // per call (one call per handle in flight)
+    std::vector<DssAvadTrialDesc> desc;
+    std::vector<DssAvadTile> tiles;
+    DssAvadTrialDesc *d_desc = nullptr;  size_t desc_cap = 0;
+    DssAvadTile *d_tiles = nullptr;      size_t tiles_cap = 0;
+    double *d_le = nullptr;              size_t le_cap = 0;       // log energies when the caller does not want them
+    // staging of the host-buffer form
+    short *d_audio = nullptr;            size_t audio_cap = 0;
+    unsigned char *d_labels = nullptr;   size_t labels_cap = 0;
+    double *d_le_out = nullptr;          size_t le_out_cap = 0;
+    double *d_thr = nullptr;             size_t thr_cap = 0;
+};
+
+template <typename T>
+static int avad_grow(T **p, size_t *cap, size_t need)
+{
+    if (need <= *cap) return DSS_OK;
+    if (*p) hipFree(*p);
+    *p = nullptr; *cap = 0;
+    const size_t n = need + need / 4 + 64;
+    DSS_HIP_CHECK(hipMalloc((void **)p, n * sizeof(T)));
+    *cap = n;
+    return DSS_OK;
+}
+
+template <typename T>
+static int avad_upload(const T *host, size_t count, T **out)
+{
+    T *d = nullptr;
+    DSS_HIP_CHECK(hipMalloc((void **)&d, count * sizeof(T) + 16));
+    DSS_HIP_CHECK(hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice));
+    *out = d;
+    return DSS_OK;
+}
+
+extern "C" int dss_avad_check_params(const dss_avad_params *p)
+{
+    if (!p) { dss_set_error("acoustic VAD: no parameters"); return DSS_EINVAL; }
+    if (p->window < 4 || (p->window & 3)) { dss_set_error("acoustic VAD: the window must be a positive multiple of 4 samples, not %d", p->window); return DSS_EINVAL; }
+    if (p->shift < 1 || p->shift > p->window) { dss_set_error("acoustic VAD: frame shift %d outside 1 .. window (%d)", p->shift, p->window); return DSS_EINVAL; }
+    if (p->n_bins != p->window / 2 + 1) { dss_set_error("acoustic VAD: %d bins for a window of %d samples (expected %d)", p->n_bins, p->window, p->window / 2 + 1); return DSS_EINVAL; }
+    if (p->n_bands < 1 || p->n_bands > AVAD_MAX_BANDS) { dss_set_error("acoustic VAD: 1 .. %d mel bands supported, not %d", AVAD_MAX_BANDS, p->n_bands); return DSS_EINVAL; }
+    if (p->frames_context < 0) { dss_set_error("acoustic VAD: frames_context must not be negative"); return DSS_EINVAL; }
+    if (!(p->energy_mean_scale >= 0.0)) { dss_set_error("acoustic VAD: energy_mean_scale must not be negative"); return DSS_EINVAL; }
+    if (!(p->proportion_threshold > 0.0 && p->proportion_threshold < 1.0)) { dss_set_error("acoustic VAD: proportion_threshold must lie inside (0, 1)"); return DSS_EINVAL; }
+    if (!isfinite(p->energy_threshold)) { dss_set_error("acoustic VAD: energy_threshold is not finite"); return DSS_EINVAL; }
+    if (dss_avad_energy_lds_bytes(p->window, p->shift, p->n_bins, p->n_bands) > AVAD_LDS_LIMIT) {
+        dss_set_error("acoustic VAD: a window of %d samples shifted by %d does not fit the energy kernel's tile", p->window, p->shift);
+        return DSS_EINVAL;
+    }
+    return DSS_OK;
+}
+
+extern "C" int dss_avad_trial_frames_for(int n, int window, int shift)
+{
+    if (window <= 0 || shift <= 0) { dss_set_error("acoustic VAD: bad frame shape"); return DSS_EINVAL; }
+    if (n < window) { dss_set_error("a trial of %d samples is shorter than one window (%d samples)", n, window); return DSS_EINVAL; }
+    return (n - window) / shift + 1;
+}
+
+extern "C" int dss_avad_check_trials(long long n_audio, int n_trials, const long long *first, const int *len, const int *lead,
+                                     int window, int shift)
+{
+    if (window <= 0 || shift <= 0) { dss_set_error("acoustic VAD: bad frame shape"); return DSS_EINVAL; }
+    if (n_trials < 0 || n_audio < 0) { dss_set_error("bad trial list: negative count"); return DSS_EINVAL; }
+    if (n_trials && (!first || !len || !lead)) { dss_set_error("bad trial list: missing array"); return DSS_EINVAL; }
+    long long total = 0;
+    for (int i = 0; i < n_trials; ++i) {
+        if (first[i] < 0 || len[i] < 0) { dss_set_error("trial %d: negative first sample or length", i); return DSS_EINVAL; }
+        if (lead[i] < 0 || lead[i] > len[i]) { dss_set_error("trial %d: %d leading zeros in a trial of %d samples", i, lead[i], len[i]); return DSS_EINVAL; }
+        if (first[i] > n_audio || (long long)(len[i] - lead[i]) > n_audio - first[i]) {
+            dss_set_error("trial %d (samples %lld .. %lld) lies outside the audio of %lld samples", i, first[i],
+                          first[i] + (long long)(len[i] - lead[i]), n_audio);
+            return DSS_EINVAL;
+        }
+        if (len[i] < window) { dss_set_error("trial %d: %d samples are shorter than one window (%d samples)", i, len[i], window); return DSS_EINVAL; }
+        total += (len[i] - window) / shift + 1;
+        if (total > 0x7fffffffLL) { dss_set_error("trial list emits more than 2^31 - 1 frames"); return DSS_EINVAL; }
+    }
+    return (int)total;
+}
+
+// the sum of the device kernel (avad_vote_kernel): 256 strided running sums, then a halving tree
+static double avad_ordered_sum(const double *x, int W)
+{
+    double part[256];
+    for (int t = 0; t < 256; ++t) {
+        double s = 0.0;
+        for (int i = t; i < W; i += 256) s += x[i];
+        part[t] = s;
+    }
+    for (int o = 128; o > 0; o >>= 1)
+        for (int t = 0; t < o; ++t) part[t] += part[t + o];
+    return part[0];
+}
+
+extern "C" int dss_avad_vote_host(const double *log_energy, int W, const dss_avad_params *p, unsigned char *labels, double *threshold)
+{
+    if (!log_energy || !labels || !p || W <= 0) { dss_set_error("acoustic VAD vote: bad arguments"); return DSS_EINVAL; }
+    if (p->frames_context < 0 || !(p->energy_mean_scale >= 0.0) || !(p->proportion_threshold > 0.0 && p->proportion_threshold < 1.0)) {
+        dss_set_error("acoustic VAD vote: bad parameters");
+        return DSS_EINVAL;
+    }
+    double thr = p->energy_threshold;
+    if (p->energy_mean_scale != 0.0) thr += p->energy_mean_scale * avad_ordered_sum(log_energy, W) / (double)W;
+    if (threshold) *threshold = thr;
+    for (int i = 0; i < W; ++i) {
+        int num = 0, den = 0;
+        for (long long t2 = (long long)i - p->frames_context; t2 < (long long)i + p->frames_context; ++t2) {
+            if (t2 >= 0 && t2 < W) {
+                ++den;
+                if (log_energy[t2] > thr) ++num;
+            }
+        }
+        labels[i] = (double)num >= (double)den * p->proportion_threshold ? 1 : 0;
+    }
+    return DSS_OK;
+}
+
+extern "C" void dss_avad_destroy(dss_avad *h)
+{
+    if (!h) return;
+    hipSetDevice(h->device);
+    hipDeviceSynchronize();
+    for (void *q : {(void *)h->d_win, (void *)h->d_tw, (void *)h->d_mel_w, (void *)h->d_band_lo, (void *)h->d_band_off, (void *)h->d_desc,
+                    (void *)h->d_tiles, (void *)h->d_le, (void *)h->d_audio, (void *)h->d_labels, (void *)h->d_le_out, (void *)h->d_thr})
+        if (q) hipFree(q);
+    delete h;
+}
+
+static int avad_setup(dss_avad *h, const double *window_fn, const double *mel)
+{
+    const dss_avad_params &p = h->p;
+    const int N = p.window;
+    std::vector<double> win((size_t)N), tw((size_t)2 * N);
+    for (int j = 0; j < N; ++j) {
+        win[j] = window_fn[j] * (1.0 / 32768.0);          // exact: x / 2^15 * w == x * (w * 2^-15)
+        const double a = 2.0 * M_PI * (double)j / (double)N;
+        tw[2 * j] = cos(a);
+        tw[2 * j + 1] = sin(a);
+    }
+    // every band's column of the mel matrix as its run first nonzero .. last nonzero (a triangular filter: one run)
+    std::vector<double> mel_w;
+    std::vector<int> lo((size_t)p.n_bands), off((size_t)p.n_bands + 1);
+    for (int b = 0; b < p.n_bands; ++b) {
+        int a = -1, z = -1;
+        for (int k = 0; k < p.n_bins; ++k) {
+            const double w = mel[(size_t)k * p.n_bands + b];
+            if (!isfinite(w)) { dss_set_error("acoustic VAD: the mel matrix holds a non-finite value"); return DSS_EINVAL; }
+            if (w != 0.0) { if (a < 0) a = k; z = k; }
+        }
+        off[b] = (int)mel_w.size();
+        lo[b] = a < 0 ? 0 : a;
+        for (int k = a; a >= 0 && k <= z; ++k) mel_w.push_back(mel[(size_t)k * p.n_bands + b]);
+    }
+    off[p.n_bands] = (int)mel_w.size();
+    if (mel_w.empty()) mel_w.push_back(0.0);
+    int rc = avad_upload(win.data(), win.size(), &h->d_win);
+    if (!rc) rc = avad_upload(tw.data(), tw.size(), &h->d_tw);
+    if (!rc) rc = avad_upload(mel_w.data(), mel_w.size(), &h->d_mel_w);
+    if (!rc) rc = avad_upload(lo.data(), lo.size(), &h->d_band_lo);
+    if (!rc) rc = avad_upload(off.data(), off.size(), &h->d_band_off);
+    if (rc) return rc;
+    DssAvadDev &d = h->d;
+    d.N = N; d.shift = p.shift; d.bins = p.n_bins; d.bands = p.n_bands; d.context = p.frames_context;
+    d.threshold = p.energy_threshold; d.mean_scale = p.energy_mean_scale; d.proportion = p.proportion_threshold;
+    d.win = h->d_win; d.tw = h->d_tw; d.mel_w = h->d_mel_w; d.band_lo = h->d_band_lo; d.band_off = h->d_band_off;
+    return DSS_OK;
+}
+
+extern "C" dss_avad *dss_avad_create(const dss_avad_params *p, const double *window_fn, const double *mel)
+{
+    if (dss_avad_check_params(p)) return nullptr;
+    if (!window_fn || !mel) { dss_set_error("acoustic VAD: missing window or mel matrix"); return nullptr; }
+    if (dss_ensure_device()) return nullptr;
+    dss_avad *h = new dss_avad;
+    h->p = *p;
+    hipGetDevice(&h->device);
+    if (avad_setup(h, window_fn, mel)) { dss_avad_destroy(h); return nullptr; }
+    return h;
+}
+
+// The trial list on device-resident audio.  d_audio holds samples audio_base .. of the caller's array.
+static int avad_run(dss_avad *h, const short *d_audio, long long audio_base, int n_trials, const long long *first, const int *len,
+                    const int *lead, const unsigned char *silence, unsigned char *d_labels, double *d_le, double *d_thr, hipStream_t st)
+{
+    const int N = h->p.window, shift = h->p.shift;
+    // descriptor table, longest trial first: the long trials' tiles start first and the short ones fill the tail
+    std::vector<int> order((size_t)n_trials);
+    for (int i = 0; i < n_trials; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return len[a] > len[b]; });
+    std::vector<long long> out_frame((size_t)n_trials);
+    long long total = 0;
+    for (int i = 0; i < n_trials; ++i) { out_frame[i] = total; total += (len[i] - N) / shift + 1; }
+    h->desc.resize((size_t)n_trials);
+    h->tiles.clear();
+    for (int k = 0; k < n_trials; ++k) {
+        const int i = order[k];
+        DssAvadTrialDesc &t = h->desc[k];
+        t.first = first[i] - audio_base; t.out_frame = out_frame[i]; t.n = len[i]; t.lead = lead[i];
+        t.W = (len[i] - N) / shift + 1; t.silence = silence && silence[i] ? 1 : 0; t.index = i; t.pad = 0;
+        for (int f0 = 0; f0 < t.W; f0 += AVAD_TILE_FRAMES) h->tiles.push_back(DssAvadTile{k, f0});
+    }
+    if (h->tiles.size() > 0x7fffffffULL) { dss_set_error("acoustic VAD: too many tiles for one launch"); return DSS_EINVAL; }
+    int rc = avad_grow(&h->d_desc, &h->desc_cap, h->desc.size());
+    if (!rc) rc = avad_grow(&h->d_tiles, &h->tiles_cap, h->tiles.size());
+    if (!rc && !d_le) { rc = avad_grow(&h->d_le, &h->le_cap, (size_t)total); d_le = h->d_le; }
+    if (rc) return rc;
+    DSS_HIP_CHECK(hipMemcpyAsync(h->d_desc, h->desc.data(), sizeof(DssAvadTrialDesc) * h->desc.size(), hipMemcpyHostToDevice, st));
+    DSS_HIP_CHECK(hipMemcpyAsync(h->d_tiles, h->tiles.data(), sizeof(DssAvadTile) * h->tiles.size(), hipMemcpyHostToDevice, st));
+    rc = dss_launch_avad_energy(h->d, d_audio, h->d_desc, h->d_tiles, (int)h->tiles.size(), d_le, st);
+    if (!rc) rc = dss_launch_avad_vote(h->d, h->d_desc, n_trials, d_le, d_labels, d_thr, st);
+    return rc ? rc : (int)total;
+}
+
+extern "C" int dss_avad_labels_trials_dev(dss_avad *h, const int16_t *d_audio, long long n_audio, int n_trials, const long long *first,
+                                          const int *len, const int *lead, const unsigned char *silence, unsigned char *d_labels,
+                                          double *d_log_energy, double *d_threshold, void *hip_stream)
+{
+    if (!h) { dss_set_error("bad arguments"); return DSS_EINVAL; }
+    const int total = dss_avad_check_trials(n_audio, n_trials, first, len, lead, h->p.window, h->p.shift);
+    if (total <= 0) return total;
+    if (!d_audio || !d_labels) { dss_set_error("bad arguments"); return DSS_EINVAL; }
+    DSS_HIP_CHECK(hipSetDevice(h->device));
+    return avad_run(h, d_audio, 0, n_trials, first, len, lead, silence, d_labels, d_log_energy, d_threshold, (hipStream_t)hip_stream);
+}
+
+extern "C" int dss_avad_labels_trials(dss_avad *h, const int16_t *audio, long long n_audio, int n_trials, const long long *first,
+                                      const int *len, const int *lead, const unsigned char *silence, unsigned char *labels,
+                                      double *log_energy, double *threshold)
+{
+    if (!h) { dss_set_error("bad arguments"); return DSS_EINVAL; }
+    const int total = dss_avad_check_trials(n_audio, n_trials, first, len, lead, h->p.window, h->p.shift);
+    if (total <= 0) return total;
+    if (!audio || !labels) { dss_set_error("bad arguments"); return DSS_EINVAL; }
+    DSS_HIP_CHECK(hipSetDevice(h->device));
+    // only the samples the trials span cross the bus, once, however the trials overlap
+    long long lo = first[0], hi = first[0] + (len[0] - lead[0]);
+    for (int i = 1; i < n_trials; ++i) {
+        lo = std::min(lo, first[i]);
+        hi = std::max(hi, first[i] + (long long)(len[i] - lead[i]));
+    }
+    int rc = avad_grow(&h->d_audio, &h->audio_cap, (size_t)(hi - lo) + 1);
+    if (!rc) rc = avad_grow(&h->d_labels, &h->labels_cap, (size_t)total);
+    if (!rc) rc = avad_grow(&h->d_le_out, &h->le_out_cap, (size_t)total);
+    if (!rc) rc = avad_grow(&h->d_thr, &h->thr_cap, (size_t)n_trials);
+    if (rc) return rc;
+    if (hi > lo) DSS_HIP_CHECK(hipMemcpy(h->d_audio, audio + lo, sizeof(short) * (size_t)(hi - lo), hipMemcpyHostToDevice));
+    rc = avad_run(h, h->d_audio, lo, n_trials, first, len, lead, silence, h->d_labels, h->d_le_out, h->d_thr, nullptr);
+    if (rc < 0) return rc;
+    DSS_HIP_CHECK(hipMemcpy(labels, h->d_labels, (size_t)total, hipMemcpyDeviceToHost));
+    if (log_energy) DSS_HIP_CHECK(hipMemcpy(log_energy, h->d_le_out, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost));
+    if (threshold) DSS_HIP_CHECK(hipMemcpy(threshold, h->d_thr, sizeof(double) * (size_t)n_trials, hipMemcpyDeviceToHost));
+    return total;
+}

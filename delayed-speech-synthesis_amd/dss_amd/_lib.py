@@ -121,6 +121,14 @@ def _declare(L):
         "dss_hga_apply_patches": (i, [vp, C.c_longlong, i, i, vp, vp, vp]),
         "dss_hga_column_stats": (i, [vp, C.c_longlong, i, vp]),
         "dss_hga_column_stats_dev": (i, [vp, C.c_longlong, i, vp, vp]),
+        "dss_avad_check_params": (i, [vp]),
+        "dss_avad_create": (vp, [vp, vp, vp]),
+        "dss_avad_destroy": (None, [vp]),
+        "dss_avad_trial_frames_for": (i, [i, i, i]),
+        "dss_avad_check_trials": (i, [C.c_longlong, i, vp, vp, vp, i, i]),
+        "dss_avad_labels_trials": (i, [vp, vp, C.c_longlong, i, vp, vp, vp, vp, vp, vp, vp]),
+        "dss_avad_labels_trials_dev": (i, [vp, vp, C.c_longlong, i, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "dss_avad_vote_host": (i, [vp, i, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

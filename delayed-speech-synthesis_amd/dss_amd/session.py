@@ -11,6 +11,12 @@ What the reference does on the CPU before its online decoder can start:
 Here the recording crosses the bus once and all trials run in one launch (``HgaExtractorGPU.extract_trials``); the frames,
 and with them the statistics, are bit-identical to the reference chain.  Parsing the ``.mat`` files stays with the user:
 ``recording`` is ``BCI2000MatFile.signals()``, ``trials`` the ``(start, stop)`` pairs of ``trial_indices()``.
+
+  * ``prepare_corpus.py:78-137,202-234``: the corpus file of a recording -- ``hga_activity`` (the z-scored frames),
+    ``vad_labels`` (an ``EnergyBasedVad`` per trial on the session's wav) and ``trial_ids``: ``session_corpus`` below, with
+    the labels of all trials in one pass over the audio (``AcousticVadGPU.labels_trials``).  Two things of that script
+    stay outside: the per-trial loudness normalisation through pydub (the audio is labelled as it is handed over), and
+    ``lpc_coefficients``, which need xiph's LPCNet feature encoder.
 """
 from __future__ import annotations
 
@@ -18,7 +24,7 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import electrodes
+from . import acoustic_vad, electrodes, hga
 from .hga import HgaExtractorGPU, column_stats
 
 N_GRID_CHANNELS = 128
@@ -84,3 +90,85 @@ def save_normalization(path, stats: np.ndarray) -> None:
     if stats.ndim != 2 or stats.shape[0] != 2:
         raise ValueError("statistics must be (2, n_channels): mean row, std row")
     np.save(path, np.vstack([stats[0], stats[1]]))
+
+
+# ---- the training corpus of one recording (prepare_corpus.py:78-137, 202-234) ------------------------------------------------
+def trial_audio_ranges(trials, fs: int = 1000, fs_audio: int = 16000, n_audio: Optional[int] = None):
+    """[(start, stop)] in recording rows -> [(first, length)] in audio samples (prepare_corpus.py:84-87):
+    ``wav[int(start * fs_audio / fs) : int(stop * fs_audio / fs) + int(0.04 * fs_audio)]``, clamped to ``n_audio`` samples as
+    Python's slicing clamps a range that ends behind the file."""
+    out = []
+    for start, stop in trials:
+        a = int(start * fs_audio / fs)
+        b = int(stop * fs_audio / fs) + int(0.04 * fs_audio)
+        if n_audio is not None:
+            a, b = min(a, int(n_audio)), min(b, int(n_audio))
+        out.append((a, max(b - a, 0)))
+    return out
+
+
+def session_vad_labels(wav: np.ndarray, trials, stimulus_labels, fs: int = 1000, fs_audio: int = 16000,
+                       shift_seconds: float = 0.016, vad: Optional[acoustic_vad.AcousticVadGPU] = None) -> np.ndarray:
+    """np.concatenate of every trial's EnergyBasedVad labels (prepare_corpus.get_vad_labels): bool (sum W_i,).  ``wav`` is the
+    session's int16 audio AS IT IS: the reference's per-trial pydub loudness normalisation is not applied (normalise the audio
+    yourself first if your corpus needs it).  Every trial is shifted by ``shift_seconds`` (zeros in front, the tail dropped,
+    prepare_corpus.py:91-93); trials whose stimulus label is "SILENCE" get all-zero labels (prepare_corpus.py:99-100)."""
+    wav = np.asarray(wav)
+    ranges = trial_audio_ranges(trials, fs, fs_audio, len(wav))
+    silence = [label == "SILENCE" for label in stimulus_labels]
+    if len(silence) != len(ranges):
+        raise ValueError("one stimulus label per trial")
+    own = vad is None
+    v = acoustic_vad.AcousticVadGPU(fs=fs_audio) if own else vad
+    try:
+        return v.labels_trials(wav, ranges, lead=int(shift_seconds * fs_audio), silence=silence)
+    finally:
+        if own:
+            v.close()
+
+
+def trial_ids(trials, stimulus_labels, stimuli, fs: int = 1000) -> np.ndarray:
+    """prepare_corpus.get_trial_ids (prepare_corpus.py:118-137): per frame the one-based index of the trial's stimulus in
+    ``stimuli``, negated when the trial repeats the stimulus of the trial before it (and positive again on the next
+    repetition), int16."""
+    stimuli = list(stimuli)
+    ids = []
+    last = None
+    for (start, stop), label in zip(trials, stimulus_labels):
+        interval = int(stop + (0.04 * fs)) - start
+        num_windows = int(np.floor((interval - 0.04 * fs) / (0.01 * fs)))
+        code = stimuli.index(label) + 1
+        if last is None or last != code:
+            last = code
+        else:
+            last = code * -1
+        ids.append(np.ones(num_windows) * last)
+    return np.hstack(ids).astype(np.int16) if ids else np.zeros(0, dtype=np.int16)
+
+
+def session_corpus(recording: np.ndarray, wav: np.ndarray, trials, stimulus_labels, stimuli, normalization: np.ndarray,
+                   fs: int = 1000, fs_audio: int = 16000, bad_channels: Optional[Sequence[int]] = None,
+                   contaminated_channels: Optional[Sequence[int]] = None, shift_seconds: float = 0.016) -> dict:
+    """Three of the four arrays prepare_corpus.main stores per recording (prepare_corpus.py:218-234), ready for the user's own
+    ``save_data_to_hdf``: ``hga_activity`` = (session_features - mean) / std with ``normalization`` = vstack([mean, std]) of the
+    day, ``vad_labels`` (bool), ``trial_ids`` (int16).  Raises ValueError when a trial's frame count differs between the
+    features and the labels (a trial clamped at the end of the wav, a sampling-rate ratio that truncates): the reference
+    would write misaligned arrays.  ``lpc_coefficients`` is not a key: it needs xiph's LPCNet feature encoder, which this
+    package does not have (its five symbols fail cleanly).  The wav is labelled as it is handed over (no pydub loudness
+    normalisation)."""
+    trials = [(int(a), int(b)) for a, b in trials]
+    stats = np.asarray(normalization, dtype=np.float64)
+    if stats.ndim != 2 or stats.shape[0] != 2:
+        raise ValueError("normalization must be (2, n_channels): mean row, std row")
+    v_window, v_shift = int(fs_audio * 0.05), int(fs_audio * 0.01)
+    for k, ((_, n_rows), (_, n_samples)) in enumerate(zip(trial_ranges(trials, fs), trial_audio_ranges(trials, fs, fs_audio, len(wav)))):
+        w_hga = hga.trial_frames(n_rows, fs)
+        w_vad = acoustic_vad.trial_frames(n_samples, v_window, v_shift)
+        if w_hga != w_vad:
+            raise ValueError(f"trial {k}: {w_hga} feature frames but {w_vad} label frames")
+    feats = session_features(recording, trials, fs, bad_channels, contaminated_channels)
+    labels = session_vad_labels(wav, trials, stimulus_labels, fs, fs_audio, shift_seconds)
+    ids = trial_ids(trials, stimulus_labels, stimuli, fs)
+    if not (len(feats) == len(labels) == len(ids)):
+        raise ValueError(f"misaligned corpus: {len(feats)} feature frames, {len(labels)} labels, {len(ids)} trial ids")
+    return dict(hga_activity=(feats - stats[0]) / stats[1], vad_labels=labels, trial_ids=ids)

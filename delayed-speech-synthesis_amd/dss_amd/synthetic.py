@@ -20,3 +20,25 @@ def synthetic_ecog(seed: int, n_samples: int = 1040, n_channels: int = 64, fs: i
     x += 20.0 * np.sin(2 * np.pi * 60.0 * t + phase[0])
     x += 20.0 * np.sin(2 * np.pi * 120.0 * t + phase[1])
     return np.ascontiguousarray(x)
+
+
+def synthetic_speech_audio(seed: int, n_samples: int, fs: int = 16000) -> np.ndarray:
+    """Seeded int16 stand-in for a session's microphone track: low room noise (about 12 LSB rms) plus, roughly every 1.2 s, a
+    burst of 0.25 - 0.7 s of harmonics of an 90 - 220 Hz fundamental under a raised-cosine envelope, so that an energy
+    based detector meets both classes of frame."""
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal(n_samples) * 12.0
+    t = 0
+    while True:
+        t += int(rng.uniform(0.5, 1.9) * fs)
+        dur = int(rng.uniform(0.25, 0.7) * fs)
+        if t + dur >= n_samples:
+            break
+        f0 = rng.uniform(90.0, 220.0)
+        k = np.arange(dur, dtype=np.float64)
+        burst = np.zeros(dur)
+        for h in range(1, 9):
+            burst += (rng.uniform(0.3, 1.0) / h) * np.sin(2 * np.pi * f0 * h * k / fs + rng.uniform(0, 2 * np.pi))
+        x[t:t + dur] += rng.uniform(2500.0, 7000.0) * (0.5 - 0.5 * np.cos(2 * np.pi * k / (dur - 1))) * burst
+        t += dur
+    return np.clip(np.rint(x), -32768, 32767).astype(np.int16)

@@ -426,6 +426,60 @@ int dss_dec_forward_dev(dss_dec *v, const void *d_frames, int frames_are_f64, in
 int dss_dec_forward_rows_dev(dss_dec *v, const void *d_frames, int frames_are_f64, int row_frames, const int *in_rows,
                              const int *counts, int n_streams, int n_frames, float *d_feats, void *hip_stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Part 7 -- acoustic voice-activity labels for the trials of a recording session: the `vad_labels` array of the training
+ * corpus (prepare_corpus.get_vad_labels, prepare_corpus.py:78-116), which the neural detector of Part 5 is trained on.  Per
+ * trial the reference builds a fresh EnergyBasedVad (local/common.py:556-649) and runs from_wav on int16 audio: frames of
+ * `window` samples every `shift`, W = floor((n - window) / shift) + 1; x / 2^15 times the window, |real DFT|, the mel filter
+ * bank (MelFilterBank, common.py:475-514), log(mel + 1e-7); the frame's log energy is coefficient 0 of scipy's type-2 DCT over
+ * the bands, 2 * sum; threshold = energy_threshold + energy_mean_scale * sum(log energy) / W (the mean term is skipped when
+ * the scale is 0); frame i is voiced iff, over the frames t in [i - frames_context, i + frames_context) inside the trial,
+ * (number with log energy > threshold) >= (number of frames) * proportion_threshold in float64.
+ * Here a whole trial list runs in two launches (csrc/acoustic_vad.hip).  The audio is taken AS THE CALLER HANDS IT OVER: the
+ * reference's per-trial loudness normalisation through pydub (prepare_corpus._normalize_audio) is not part of this library.
+ * Trial i is `lead[i]` zero samples followed by audio[first[i] .. first[i] + len[i] - lead[i]): len[i] samples in all, which
+ * is the reference's 16 ms shift (prepare_corpus.py:91-93) with lead = 256.  Ranges may overlap.  A trial shorter than one
+ * window has no frame (the reference divides by zero there) and is refused.  silence[i] != 0 gives the trial all-zero labels
+ * (prepare_corpus.py:99-100).  The reference's arithmetic is numpy's FFT and BLAS: log energies agree with it to ~1e-12, not
+ * bit for bit; the same trial gives the same bits alone or inside any list, on every run.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct dss_avad_params {
+    int window, shift;                 /* samples per frame (a multiple of 4), samples between frames: 800, 160 at 16 kHz */
+    int n_bins, n_bands;               /* window / 2 + 1 spectrum bins, mel bands (<= 64) */
+    int frames_context, reserved;      /* EnergyBasedVad's vad_frames_context (5) */
+    double energy_threshold;           /* 4 */
+    double energy_mean_scale;          /* 1; >= 0 */
+    double proportion_threshold;       /* 0.6; inside (0, 1) */
+} dss_avad_params;
+typedef struct dss_avad dss_avad;
+/* The checks of dss_avad_create on their own (no device needed). */
+int dss_avad_check_params(const dss_avad_params *p);
+/* window_fn: `window` doubles (numpy.hanning(window) in the reference); mel: the (n_bins, n_bands) row-major filter matrix
+ * (MelFilterBank.melMatrix).  Both are data the caller computes (dss_amd.acoustic_vad).  NULL on failure. */
+dss_avad *dss_avad_create(const dss_avad_params *p, const double *window_fn, const double *mel);
+void dss_avad_destroy(dss_avad *h);
+/* Frames of a trial of n samples, or DSS_EINVAL when n < window (no device needed). */
+int dss_avad_trial_frames_for(int n, int window, int shift);
+/* The argument checks of the two labels_trials entry points on their own (no device needed): frames of the whole list, or
+ * DSS_EINVAL with the reason in dss_last_error() -- NULL arrays, a negative count, first < 0, len < 0, lead < 0, lead > len,
+ * a range that ends behind the audio, len < window, more than 2^31 - 1 frames. */
+int dss_avad_check_trials(long long n_audio, int n_trials, const long long *first, const int *len, const int *lead, int window,
+                          int shift);
+/* Host buffers: audio int16[n_audio]; silence (n_trials bytes) may be NULL; labels uint8[sum W], trial after trial in list
+ * order; log_energy double[sum W] and threshold double[n_trials] may be NULL.  Returns the number of frames. */
+int dss_avad_labels_trials(dss_avad *h, const int16_t *audio, long long n_audio, int n_trials, const long long *first,
+                           const int *len, const int *lead, const unsigned char *silence, unsigned char *labels,
+                           double *log_energy, double *threshold);
+/* Device-resident: d_audio, d_labels, d_log_energy (or NULL), d_threshold (or NULL) are device pointers; first / len / lead /
+ * silence are HOST arrays.  Returns once the launches are queued on hip_stream; one call per handle may be in flight. */
+int dss_avad_labels_trials_dev(dss_avad *h, const int16_t *d_audio, long long n_audio, int n_trials, const long long *first,
+                               const int *len, const int *lead, const unsigned char *silence, unsigned char *d_labels,
+                               double *d_log_energy, double *d_threshold, void *hip_stream);
+/* Threshold and vote of ONE trial on the host from its W log energies (no device needed).  The vote's comparison is the
+ * reference's; the sum behind the mean is taken in the device kernel's order (256 strided running sums, then a halving
+ * tree), not numpy's pairwise one.  labels: W bytes; threshold may be NULL. */
+int dss_avad_vote_host(const double *log_energy, int W, const dss_avad_params *p, unsigned char *labels, double *threshold);
+
 #ifdef __cplusplus
 }
 #endif
