@@ -40,6 +40,10 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#if defined(__x86_64__)
+#include <xmmintrin.h>
+#include <pmmintrin.h>
+#endif
 
 #include "../include/dss_lpcnet_blob.h"
 
@@ -206,6 +210,74 @@ const float *oracle_lpcnet_table(const oracle_lpcnet_model *m, int which)
 }
 
 /* ------------------------------------------------------------------------------------------------
+ * witnesses (tests/test_cpu_lpcnet_regimes.py): counters of the value regime a run visits.  Off by default,
+ * switched on per decoder (oracle_lpcnet_set_counters); they only read values the decoder computes anyway
+ * and never take part in an arithmetic operation.  The layout is mirrored by tests/oracle_api.py.
+ * ---------------------------------------------------------------------------------------------- */
+enum { SITE_FRAME = 0, SITE_GRU_A = 1, SITE_GRU_B = 2, SITE_DUAL_FC = 3, N_SITES = 4 };
+typedef struct {
+    int64_t evals[N_SITES];          /* tanh_approx evaluations (sigmoid_approx is one of them) */
+    int64_t clamped[N_SITES];        /* ... whose table index was beyond 200 before the clamp */
+    int64_t out_of_range[N_SITES];   /* ... whose result has |r| > 1 */
+    int64_t saturated[N_SITES];      /* ... whose result is exactly +1 or -1 */
+    int64_t subnormal_in[N_SITES];   /* ... whose argument is a nonzero subnormal */
+    int64_t nonfinite;               /* non-finite values written to a state (GRU A/B, conditioning, LPC, signal history) */
+    int64_t n_pre;                   /* samples synthesised */
+    float pre_min, pre_max;          /* pre-quantised sample (pred + ulaw2lin(exc)) */
+    int64_t clip_hi, clip_lo;        /* de-emphasised samples clipped at +32767 / -32767 */
+    int64_t exc_hist[256];           /* excitation index of every sample (sampled, or forced) */
+    int64_t walk_above, walk_below;  /* tree-walk logits above the largest / below the smallest table threshold */
+    int64_t walk_equal;              /* tree-walk comparisons `threshold < logit` taken at equality */
+    float *clamp_x;                  /* optional: arguments of the clamped GRU A / GRU B evaluations, first clamp_cap */
+    int64_t clamp_cap, clamp_n;
+} oracle_lpcnet_counters;
+
+static __thread oracle_lpcnet_counters *cnt_sink;      /* NULL = off */
+static __thread int cnt_site;
+
+static void count_activation(float arg, int index_before_clamp, float result)
+{
+    oracle_lpcnet_counters *c = cnt_sink;
+    const int s = cnt_site;
+    c->evals[s]++;
+    if (index_before_clamp > 200) {
+        c->clamped[s]++;
+        if ((s == SITE_GRU_A || s == SITE_GRU_B) && c->clamp_x && c->clamp_n < c->clamp_cap) c->clamp_x[c->clamp_n++] = arg;
+    }
+    if (fabsf(result) > 1.f) c->out_of_range[s]++;
+    if (fabsf(result) == 1.f) c->saturated[s]++;
+    if (fpclassify(arg) == FP_SUBNORMAL) c->subnormal_in[s]++;
+}
+
+static void count_state(const float *v, int n)
+{
+    for (int i = 0; i < n; ++i) if (!isfinite(v[i])) cnt_sink->nonfinite++;
+}
+
+/* Subnormal witness: FTZ + DAZ in MXCSR turn this library into "the kernel that flushes".  Returns 0, or -1 where
+ * the switch does not exist (then the witness is skipped, visibly).  The caller restores the mode. */
+int oracle_set_flush_denormals(int on)
+{
+#if defined(__x86_64__)
+    _MM_SET_FLUSH_ZERO_MODE(on ? _MM_FLUSH_ZERO_ON : _MM_FLUSH_ZERO_OFF);
+    _MM_SET_DENORMALS_ZERO_MODE(on ? _MM_DENORMALS_ZERO_ON : _MM_DENORMALS_ZERO_OFF);
+    return 0;
+#else
+    (void)on;
+    return -1;
+#endif
+}
+
+int oracle_get_flush_denormals(void)
+{
+#if defined(__x86_64__)
+    return (_MM_GET_FLUSH_ZERO_MODE() == _MM_FLUSH_ZERO_ON) | ((_MM_GET_DENORMALS_ZERO_MODE() == _MM_DENORMALS_ZERO_ON) << 1);
+#else
+    return -1;
+#endif
+}
+
+/* ------------------------------------------------------------------------------------------------
  * activations (vec.h generic path, table form)
  * ---------------------------------------------------------------------------------------------- */
 static float tanh_approx(const oracle_lpcnet_model *m, float x)
@@ -213,14 +285,18 @@ static float tanh_approx(const oracle_lpcnet_model *m, float x)
     int i;
     float y, dy;
     float sign = 1;
+    const float arg = x;
+    int i_raw;
     if (x < 0) { x = -x; sign = -1; }
     i = (int)floor(.5f + 25 * x);
+    i_raw = i;
     if (i < 0) i = 0;
     if (i > 200) i = 200;
     x -= .04f * i;
     y = m->tansig_table[i];
     dy = 1 - y * y;
     y = y + x * dy * (1 - y * x);
+    if (cnt_sink) count_activation(arg, i_raw, sign * y);
     return sign * y;
 }
 
@@ -348,6 +424,7 @@ typedef struct {
     const unsigned char *forced_exc;
     float *forced_logits;
     long forced_pos, forced_cap;
+    oracle_lpcnet_counters *counters;   /* optional witnesses (tests): NULL = off */
 } oracle_lpcnet_state;
 
 int oracle_lpcnet_init(oracle_lpcnet_state *st)
@@ -355,9 +432,11 @@ int oracle_lpcnet_init(oracle_lpcnet_state *st)
     const oracle_lpcnet_model *m = st->m;
     unsigned char *te = st->trace_exc; float *tp = st->trace_pcm; long cap = st->trace_cap;
     const unsigned char *fe = st->forced_exc; float *fl = st->forced_logits; long fcap = st->forced_cap;
+    oracle_lpcnet_counters *cn = st->counters;
     memset(st, 0, sizeof(*st));
     st->m = m; st->trace_exc = te; st->trace_pcm = tp; st->trace_cap = cap;
     st->forced_exc = fe; st->forced_logits = fl; st->forced_cap = fcap;
+    st->counters = cn;
     st->last_exc = lin2ulaw(0.f);
     kiss99_srand(&st->rng, (const unsigned char *)"LPCNet", 6);
     return 0;
@@ -383,6 +462,13 @@ void oracle_lpcnet_set_forced(oracle_lpcnet_state *st, const unsigned char *exc,
 {
     st->forced_exc = exc; st->forced_logits = logits; st->forced_cap = cap; st->forced_pos = 0;
 }
+
+/* witnesses: c stays owned by the caller and is filled by every later call on this decoder; NULL switches them off */
+void oracle_lpcnet_set_counters(oracle_lpcnet_state *st, oracle_lpcnet_counters *c)
+{
+    st->counters = c;
+}
+int oracle_lpcnet_counters_size(void) { return (int)sizeof(oracle_lpcnet_counters); }
 
 /* test hook: overwrite the recurrent state and the per-frame conditioning (teacher-forced single steps) */
 void oracle_lpcnet_set_state(oracle_lpcnet_state *st, const float *gru_a_state, const float *gru_b_state,
@@ -471,6 +557,7 @@ void oracle_lpcnet_frame_network(oracle_lpcnet_state *st, const float *features)
     const dss_blob_header *h = &m->h;
     float in[512], conv1_out[512], conv2_out[512], dense1_out[512], condition[512];
     int pitch = (int)floor(.1 + 50 * features[NB_BANDS] + 100);
+    cnt_sink = st->counters; cnt_site = SITE_FRAME;
     if (pitch < 33) pitch = 33;
     if (pitch > 255) pitch = 255;
     const int fin = h->nb_features + h->embed_pitch_dim;
@@ -488,6 +575,12 @@ void oracle_lpcnet_frame_network(oracle_lpcnet_state *st, const float *features)
     memcpy(st->lpc, st->old_lpc[FEATURES_DELAY - 1], sizeof(st->lpc));
     memmove(st->old_lpc[1], st->old_lpc[0], (FEATURES_DELAY - 1) * sizeof(st->lpc));
     oracle_lpc_from_cepstrum(m, st->old_lpc[0], features);
+    if (cnt_sink) {
+        count_state(st->gru_a_condition, 3 * h->gru_a);
+        count_state(st->gru_b_condition, 3 * h->gru_b);
+        count_state(st->old_lpc[0], LPC_ORDER);
+        cnt_sink = NULL;
+    }
     if (st->frame_count < 1000) st->frame_count++;
 }
 
@@ -506,6 +599,7 @@ static int run_sample_network(oracle_lpcnet_state *st, int last_exc, int last_si
                          + m->embed_pred[(size_t)pred * 3 * N + i] + m->embed_exc[(size_t)last_exc * 3 * N + i];
 
     /* compute_sparse_gru */
+    cnt_sink = st->counters; cnt_site = SITE_GRU_A;
     {
         float *state = st->gru_a_state;
         float *z = recur, *r = recur + N, *hh = recur + 2 * N;
@@ -540,9 +634,11 @@ static int run_sample_network(oracle_lpcnet_state *st, int last_exc, int last_si
         for (int i = 0; i < N; i++) hh[i] = hh[i] * r[i] + gru_a_input[2 * N + i];
         for (int i = 0; i < N; i++) hh[i] = tanh_approx(m, hh[i]);
         for (int i = 0; i < N; i++) state[i] = z[i] * state[i] + (1 - z[i]) * hh[i];
+        if (cnt_sink) count_state(state, N);
     }
 
     /* compute_gruB: input = gru_a_state, condition added to the input bias */
+    cnt_site = SITE_GRU_B;
     {
         float zrh[3 * 64], rec[3 * 64];
         float *state = st->gru_b_state;
@@ -557,9 +653,11 @@ static int run_sample_network(oracle_lpcnet_state *st, int last_exc, int last_si
         for (int i = 0; i < NB; i++) hh[i] = tanh_approx(m, hh[i]);
         for (int i = 0; i < NB; i++) hh[i] = z[i] * state[i] + (1 - z[i]) * hh[i];
         for (int i = 0; i < NB; i++) state[i] = hh[i];
+        if (cnt_sink) count_state(state, NB);
     }
 
     /* sample_mdense: 8-level binary tree over the dual-FC outputs, thresholds from the RNG */
+    cnt_site = SITE_DUAL_FC;
     {
         const int M = NB, Nout = m->h.dual_fc_out, stride = 2 * NB;
         float thresholds[8];
@@ -588,8 +686,14 @@ static int run_sample_network(oracle_lpcnet_state *st, int last_exc, int last_si
             float sum1;
             NODE_LOGIT(i, sum1);
             int bit = thresholds[b] < sum1;
+            if (cnt_sink) {
+                if (sum1 > m->sampling_logit_table[255]) cnt_sink->walk_above++;
+                if (sum1 < m->sampling_logit_table[0]) cnt_sink->walk_below++;
+                if (thresholds[b] == sum1) cnt_sink->walk_equal++;
+            }
             val = (val << 1) | bit;
         }
+        cnt_sink = NULL;                                             /* the walk's evaluations are the ones counted */
         if (st->forced_exc && st->forced_pos < st->forced_cap) {     /* teacher forcing (tests only) */
             if (st->forced_logits) {
                 float *lo = st->forced_logits + st->forced_pos * 256;
@@ -637,6 +741,14 @@ void oracle_lpcnet_synthesize(oracle_lpcnet_state *st, const float *features, sh
         pred_ulaw = lin2ulaw(pred);
         exc = run_sample_network(st, st->last_exc, last_sig_ulaw, pred_ulaw);
         pcm = pred + m->ulaw2lin_table[exc];
+        if (st->counters) {
+            oracle_lpcnet_counters *c = st->counters;
+            if (!c->n_pre || pcm < c->pre_min) c->pre_min = pcm;
+            if (!c->n_pre || pcm > c->pre_max) c->pre_max = pcm;
+            c->n_pre++;
+            c->exc_hist[exc]++;
+            if (!isfinite(pcm)) c->nonfinite++;
+        }
         if (st->trace_exc && st->trace_pos < st->trace_cap) {
             st->trace_exc[st->trace_pos] = (unsigned char)exc;
             st->trace_pcm[st->trace_pos] = pcm;
@@ -647,6 +759,11 @@ void oracle_lpcnet_synthesize(oracle_lpcnet_state *st, const float *features, sh
         st->last_exc = exc;
         pcm += PREEMPH * st->deemph_mem;
         st->deemph_mem = pcm;
+        if (st->counters) {
+            if (!isfinite(pcm)) st->counters->nonfinite++;
+            if (pcm < -32767) st->counters->clip_lo++;
+            if (pcm > 32767) st->counters->clip_hi++;
+        }
         if (pcm < -32767) pcm = -32767;
         if (pcm > 32767) pcm = 32767;
         output[i] = (int)floor(.5 + pcm);

@@ -5,6 +5,21 @@ import numpy as np
 
 _dp = C.POINTER(C.c_double)
 
+SITES = ("frame", "gru_a", "gru_b", "dual_fc")     # oracle/lpcnet_oracle.c: SITE_*
+
+
+class Counters(C.Structure):
+    """oracle_lpcnet_counters (oracle/lpcnet_oracle.c): witnesses of the value regime a decoder visits."""
+    _fields_ = [("evals", C.c_int64 * 4), ("clamped", C.c_int64 * 4), ("out_of_range", C.c_int64 * 4),
+                ("saturated", C.c_int64 * 4), ("subnormal_in", C.c_int64 * 4), ("nonfinite", C.c_int64),
+                ("n_pre", C.c_int64), ("pre_min", C.c_float), ("pre_max", C.c_float), ("clip_hi", C.c_int64),
+                ("clip_lo", C.c_int64), ("exc_hist", C.c_int64 * 256), ("walk_above", C.c_int64),
+                ("walk_below", C.c_int64), ("walk_equal", C.c_int64), ("clamp_x", C.c_void_p),
+                ("clamp_cap", C.c_int64), ("clamp_n", C.c_int64)]
+
+    def site(self, field, name):
+        return int(getattr(self, field)[SITES.index(name)])
+
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
@@ -59,6 +74,44 @@ class Oracle:
         L.oracle_lpcnet_sample_step.restype = C.c_int
         L.oracle_lpcnet_sample_step.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.oracle_lpcnet_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        # witnesses (newer than the rest): bound when present, asked for through require_witnesses()
+        self.has_witnesses = all(hasattr(L, n) for n in self._WITNESS_SYMBOLS)
+        if self.has_witnesses:
+            L.oracle_lpcnet_set_counters.argtypes = [C.c_void_p, C.c_void_p]
+            L.oracle_lpcnet_counters_size.restype = C.c_int
+            L.oracle_set_flush_denormals.restype = C.c_int
+            L.oracle_set_flush_denormals.argtypes = [C.c_int]
+            L.oracle_get_flush_denormals.restype = C.c_int
+
+    _WITNESS_SYMBOLS = ("oracle_lpcnet_set_counters", "oracle_lpcnet_counters_size", "oracle_set_flush_denormals",
+                        "oracle_get_flush_denormals")
+
+    def require_witnesses(self):
+        """The counters and the flush switch, or a message that says what to do about a stale library."""
+        if not self.has_witnesses:
+            raise RuntimeError("oracle/liboracle.so is older than oracle/lpcnet_oracle.c (no witness counters, no "
+                               "oracle_set_flush_denormals): rebuild oracle/ (`make -C oracle`)")
+        if self.lib.oracle_lpcnet_counters_size() != C.sizeof(Counters):
+            raise RuntimeError("oracle_lpcnet_counters differs between oracle/liboracle.so and tests/oracle_api.py: "
+                               "rebuild oracle/ (`make -C oracle`)")
+
+    def flush_denormals(self, on=True):
+        """Context manager: FTZ + DAZ on the calling thread while inside (the 'kernel that flushes'); the earlier mode
+        comes back on exit.  Raises NotImplementedError where the oracle has no such switch."""
+        import contextlib
+        self.require_witnesses()
+        lib = self.lib
+
+        @contextlib.contextmanager
+        def cm():
+            before = lib.oracle_get_flush_denormals()
+            if before < 0 or lib.oracle_set_flush_denormals(1 if on else 0) != 0:
+                raise NotImplementedError("oracle_set_flush_denormals: unsupported on this CPU architecture")
+            try:
+                yield
+            finally:
+                lib.oracle_set_flush_denormals(1 if before else 0)
+        return cm()
 
     # ---- HGA ---------------------------------------------------------------------------------
     def sosfilt(self, sos, x, zi):
@@ -147,6 +200,17 @@ class Oracle:
                 self.trace_pcm = np.zeros(trace_cap, np.float32)
                 lib.oracle_lpcnet_set_trace(self.h, _p(self.trace_exc), _p(self.trace_pcm), trace_cap)
 
+        def count(self, clamp_cap=0):
+            """Switch the witness counters on (oracle_api.Counters, filled by every later call); with clamp_cap, the
+            arguments of the first clamp_cap clamped GRU A / GRU B activations are kept in self.clamp_x."""
+            self.counters = Counters()
+            if clamp_cap:
+                self.clamp_x = np.zeros(clamp_cap, np.float32)
+                self.counters.clamp_x = self.clamp_x.ctypes.data
+                self.counters.clamp_cap = clamp_cap
+            self.lib.oracle_lpcnet_set_counters(self.h, C.byref(self.counters))
+            return self.counters
+
         def force(self, exc, want_logits=True):
             """Teacher forcing: sample k takes exc[k]; all 255 node logits of each forced sample are recorded."""
             self.forced_exc = np.ascontiguousarray(exc, dtype=np.uint8)
@@ -183,8 +247,13 @@ class Oracle:
         def __del__(self):
             self.lib.oracle_lpcnet_destroy(self.h)
 
-    def decoder(self, model, trace_cap=0):
-        return Oracle.Decoder(self.lib, model, trace_cap)
+    def decoder(self, model, trace_cap=0, count=False, clamp_cap=0):
+        if count or clamp_cap:
+            self.require_witnesses()
+        dec = Oracle.Decoder(self.lib, model, trace_cap)
+        if count or clamp_cap:
+            dec.count(clamp_cap)
+        return dec
 
     # ---- known-answer hooks -------------------------------------------------------------------
     def kiss99(self, seed4=None, srand: bytes = None):
