@@ -242,3 +242,106 @@ int dss_launch_decoder(const DssDecDev &d, const void *d_frames, int frames_f64,
     DSS_HIP_CHECK(hipGetLastError());
     return DSS_OK;
 }
+
+// ---- a trial list (dss_dec_forward_trials_dev; the reference's validation pass, train_bidirectional_model.py:165-178) ----------
+// The layers are bilstm_layer_kernel's ragged form as it is: trial s of the chunk is "row" first[s] of a buffer with ONE frame per
+// row, i.e. frames first[s] + t of the concatenated (N, C) array, with counts[s] frames of its own -- so a trial's arithmetic is
+// what dss_dec_forward_rows_dev gives it.  Only the regressor differs: its rows leave the padded (S, T) grid of the layer outputs
+// for the trial's rows out_row[s] .. of the concatenated features (same dot product, term for term, as dec_regress_kernel).
+__global__ void __launch_bounds__(256)
+dec_regress_trials_kernel(const float *__restrict__ top, long rows, int K, int O, const float *__restrict__ w, const float *__restrict__ b,
+                          float *__restrict__ feats, const int *__restrict__ counts, const long long *__restrict__ out_row, int T)
+{
+    extern __shared__ __attribute__((aligned(16))) float rs[];             // [O][K + 1] weights, then [DEC_RROWS][K] inputs
+    float *ws = rs, *xs = rs + (size_t)O * (K + 1);
+    const int tid = threadIdx.x;
+    const long r0 = (long)blockIdx.x * DEC_RROWS;
+    auto live = [&](long r) { return r < rows && (int)(r % T) < counts[r / T]; };
+    bool any = false;                                      // (uniform over the block: a block of padding rows has nothing to do)
+    for (int rr = 0; rr < DEC_RROWS; ++rr) any = any || live(r0 + rr);
+    if (!any) return;
+    for (int k = tid; k < O * K; k += 256) { const int o = k / K, j = k - o * K; ws[o * (K + 1) + j] = w[k]; }
+    for (int k = tid; k < DEC_RROWS * K; k += 256) {
+        const long r = r0 + k / K;
+        xs[k] = live(r) ? top[r * K + (k % K)] : 0.f;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < DEC_RROWS * O; idx += 256) {
+        const int rr = idx / O, o = idx - rr * O;
+        const long r = r0 + rr;
+        if (!live(r)) continue;
+        const float *x = xs + rr * K, *wr = ws + o * (K + 1);
+        float a = 0.f;
+        for (int k = 0; k < K; ++k) a = __builtin_fmaf(wr[k], x[k], a);
+        feats[(size_t)(out_row[r / T] + r % T) * O + o] = a + b[o];
+    }
+}
+
+int dss_launch_decoder_trials(const DssDecDev &d, const void *d_frames, int frames_f64, int S, int T, float *d_feats,
+                              const int *d_counts, const int *d_first, const long long *d_out_row, hipStream_t st)
+{
+    if (d.H < 1 || d.H > DEC_MAXH || 4 * d.H > DEC_THREADS || d.C < 1 || d.C > DEC_MAXC || 2 * d.H > DEC_MAXC) {
+        dss_set_error("decoder kernel: hidden size %d / %d inputs out of range (<= %d / <= %d)", d.H, d.C, DEC_MAXH, DEC_MAXC);
+        return DSS_EINVAL;
+    }
+    if (d.O < 1 || d.O > 32) { dss_set_error("decoder kernel: %d outputs out of range (<= 32)", d.O); return DSS_EINVAL; }
+    if (S < 1 || S > d.S_max || T < 1 || T > d.T_max || !d_counts || !d_first || !d_out_row) {
+        dss_set_error("decoder kernel: %d trials x %d frames exceed the handle's %d x %d", S, T, d.S_max, d.T_max);
+        return DSS_EINVAL;
+    }
+    const int Wsel = 2 * S <= 256 ? 1 : (S <= 256 ? 2 : 4);                // as dss_launch_decoder
+    const dim3 block(DEC_THREADS);
+#define DEC_TLAUNCH(INT, WV, IN, CIN, L, OUT)                                                                                  \
+    hipLaunchKernelGGL((bilstm_layer_kernel<INT, WV>), dim3((S + WV - 1) / WV, 2), block, 0, st, (const INT *)(IN), S, T, CIN, d.H,  \
+                       d.wT[L][0], d.wT[L][1], d.b[L][0], d.b[L][1], OUT, d_counts, (L) == 0 ? d_first : (const int *)nullptr,    \
+                       (L) == 0 ? 1 : T)
+#define DEC_TLAUNCH_W(INT, IN, CIN, L, OUT)                                                                                     \
+    do {                                                                                                                        \
+        if (Wsel == 1) DEC_TLAUNCH(INT, 1, IN, CIN, L, OUT);                                                                    \
+        else if (Wsel == 2) DEC_TLAUNCH(INT, 2, IN, CIN, L, OUT);                                                               \
+        else DEC_TLAUNCH(INT, 4, IN, CIN, L, OUT);                                                                              \
+    } while (0)
+    if (frames_f64) DEC_TLAUNCH_W(double, d_frames, d.C, 0, d.mid);
+    else DEC_TLAUNCH_W(float, d_frames, d.C, 0, d.mid);
+    DEC_TLAUNCH_W(float, d.mid, 2 * d.H, 1, d.top);
+#undef DEC_TLAUNCH_W
+#undef DEC_TLAUNCH
+    const long rows = (long)S * T;
+    const size_t rlds = ((size_t)d.O * (2 * d.H + 1) + (size_t)DEC_RROWS * 2 * d.H) * sizeof(float);
+    hipLaunchKernelGGL(dec_regress_trials_kernel, dim3((unsigned)((rows + DEC_RROWS - 1) / DEC_RROWS)), dim3(256), rlds, st, d.top, rows,
+                       2 * d.H, d.O, d.wr, d.br, d_feats, d_counts, d_out_row, T);
+    DSS_HIP_CHECK(hipGetLastError());
+    return DSS_OK;
+}
+
+// per-trial mean squared error of concatenated (sum len, O) features against targets of the same shape (nn.MSELoss() on one trial,
+// train_bidirectional_model.py:176-177), in float64 in a fixed order: thread t of the trial's workgroup adds the squared
+// differences of elements t, t + 256, ... in that order, then a halving tree over the 256 partial sums.  The launch's trials
+// travel as kernel arguments (DssTrialLens).
+__global__ void __launch_bounds__(256)
+dec_mse_trials_kernel(DssTrialLens tl, const float *__restrict__ feats, const float *__restrict__ targets, int O, double *__restrict__ mse)
+{
+    __shared__ double part[256];
+    const int tid = threadIdx.x, k = blockIdx.x;
+    long long off = tl.base;
+    for (int j = 0; j < k; ++j) off += tl.len[j];
+    const long long n = (long long)tl.len[k] * O;
+    const float *f = feats + off * O, *g = targets + off * O;
+    double acc = 0.0;
+    for (long long i = tid; i < n; i += 256) { const double e = (double)f[i] - (double)g[i]; acc += e * e; }
+    part[tid] = acc;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h) part[tid] += part[tid + h];
+        __syncthreads();
+    }
+    if (tid == 0) mse[tl.first_trial + k] = part[0] / (double)n;
+}
+
+int dss_launch_dec_mse_trials(const DssTrialLens &tl, const float *d_feats, const float *d_targets, int n_outputs, double *d_mse,
+                              hipStream_t st)
+{
+    hipLaunchKernelGGL(dec_mse_trials_kernel, dim3(tl.n), dim3(256), 0, st, tl, d_feats, d_targets, n_outputs, d_mse);
+    DSS_HIP_CHECK(hipGetLastError());
+    return DSS_OK;
+}

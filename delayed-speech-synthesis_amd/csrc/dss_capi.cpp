@@ -2188,6 +2188,10 @@ struct dss_vad {
     DssVadDev d;
     float *w[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // wT0, b0, wT1, b1, wc, bc
     bool loaded = false;
+    // trial lists (dss_vad_forward_trials_dev): the descriptor table of the last call, pinned staging and device
+    DssPinnedStage tstage;
+    DssVadTrialDesc *d_tdesc = nullptr;
+    size_t tdesc_cap = 0;
 };
 
 extern "C" dss_vad *dss_vad_create(int n_streams, int n_inputs, int hidden_units)
@@ -2219,6 +2223,8 @@ extern "C" void dss_vad_destroy(dss_vad *v)
     for (float *p : v->w) if (p) hipFree(p);
     if (v->d.h) hipFree(v->d.h);
     if (v->d.c) hipFree(v->d.c);
+    if (v->d_tdesc) hipFree(v->d_tdesc);
+    v->tstage.destroy();
     delete v;
 }
 
@@ -2322,6 +2328,12 @@ struct dss_dec {
     bool loaded = false;
     int *d_meta = nullptr;        // [2][S_max]: frame counts, input rows of a ragged call (dss_dec_forward_rows_dev)
     DssPinnedRing meta;           //   their pinned staging
+    // trial lists (dss_dec_forward_trials_dev): per trial, longest first: output row | frame count, first row; pinned staging
+    // and device
+    DssPinnedStage tstage;
+    int *d_tmeta = nullptr;
+    long long *d_tout = nullptr;
+    size_t tmeta_cap = 0, tout_cap = 0;
 };
 
 extern "C" dss_dec *dss_dec_create(int max_streams, int max_frames, int n_inputs, int hidden_units, int n_outputs)
@@ -2357,6 +2369,9 @@ extern "C" void dss_dec_destroy(dss_dec *v)
     if (v->d.mid) hipFree(v->d.mid);
     if (v->d.top) hipFree(v->d.top);
     if (v->d_meta) hipFree(v->d_meta);
+    if (v->d_tmeta) hipFree(v->d_tmeta);
+    if (v->d_tout) hipFree(v->d_tout);
+    v->tstage.destroy();
     v->meta.destroy();
     delete v;
 }
@@ -2444,4 +2459,149 @@ extern "C" int dss_dec_forward_rows_dev(dss_dec *v, const void *d_frames, int fr
     if (rc) return rc;
     return dss_launch_decoder(v->d, d_frames, frames_are_f64, n_streams, n_frames, d_feats, v->d_meta, in_rows ? v->d_meta + S : nullptr,
                               row_frames, s);
+}
+
+// ------------------------------------------------------------------------------------------------------
+// the two recurrent models over a trial list (Part 8 of include/dss_hip.h; csrc/vad_lstm.hip, csrc/bilstm_decoder.hip)
+// ------------------------------------------------------------------------------------------------------
+extern "C" int dss_trials_check(long long N, int n_trials, const long long *first, const int *len, long long *total)
+{
+    if (!first || !len || !total) { dss_set_error("trial list: null argument"); return DSS_EINVAL; }
+    if (n_trials < 0 || N < 0) { dss_set_error("trial list: negative count"); return DSS_EINVAL; }
+    long long sum = 0;
+    for (int i = 0; i < n_trials; ++i) {
+        if (len[i] < 1) { dss_set_error("trial %d: %d frames (at least 1)", i, len[i]); return DSS_EINVAL; }
+        if (first[i] < 0) { dss_set_error("trial %d: first row %lld is negative", i, first[i]); return DSS_EINVAL; }
+        if (first[i] > N - len[i]) {
+            dss_set_error("trial %d: rows %lld .. %lld end behind the %lld rows of the array", i, first[i], first[i] + len[i], N);
+            return DSS_EINVAL;
+        }
+        sum += len[i];
+    }
+    *total = sum;
+    return DSS_OK;
+}
+
+// a device array that only grows (the buffer of a call still queued is not freed under it: hipFree waits for the device)
+template <typename T>
+static int trials_grow(T **buf, size_t *cap, size_t need)
+{
+    if (need <= *cap) return DSS_OK;
+    if (*buf) { hipFree(*buf); *buf = nullptr; *cap = 0; }
+    DSS_HIP_CHECK(hipMalloc((void **)buf, need * sizeof(T)));
+    *cap = need;
+    return DSS_OK;
+}
+
+// list positions, longest trial first (ties in list order): the long trials start first, the short ones fill the tail
+static std::vector<int> trials_longest_first(int n_trials, const int *len)
+{
+    std::vector<int> order((size_t)n_trials);
+    for (int i = 0; i < n_trials; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return len[a] > len[b]; });
+    return order;
+}
+
+extern "C" int dss_vad_forward_trials_dev(dss_vad *v, const void *d_frames, int frames_are_f64, long long N, int n_trials,
+                                          const long long *first, const int *len, int *d_labels, float *d_logits, void *hip_stream)
+{
+    if (!v || !d_frames || !d_labels) { dss_set_error("dss_vad_forward_trials_dev: bad arguments"); return DSS_EINVAL; }
+    if (!v->loaded) { dss_set_error("dss_vad_forward_trials_dev: no weights loaded (dss_vad_load_weights)"); return DSS_EINVAL; }
+    long long total = 0;
+    int rc = dss_trials_check(N, n_trials, first, len, &total);
+    if (rc) return rc;
+    if (!n_trials) return DSS_OK;
+    DSS_HIP_CHECK(hipSetDevice(v->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    std::vector<long long> out_row((size_t)n_trials);
+    long long row = 0;
+    for (int i = 0; i < n_trials; ++i) { out_row[i] = row; row += len[i]; }
+    const std::vector<int> order = trials_longest_first(n_trials, len);
+    DssVadTrialDesc *desc = (DssVadTrialDesc *)v->tstage.acquire(sizeof(DssVadTrialDesc) * (size_t)n_trials);
+    if (!desc) { dss_set_error("pinned staging for the trial table failed"); return DSS_ENOMEM; }
+    for (int k = 0; k < n_trials; ++k) { const int i = order[k]; desc[k] = DssVadTrialDesc{first[i], out_row[i], len[i], 0}; }
+    rc = trials_grow(&v->d_tdesc, &v->tdesc_cap, (size_t)n_trials);
+    if (rc) return rc;
+    DSS_HIP_CHECK(hipMemcpyAsync(v->d_tdesc, desc, sizeof(DssVadTrialDesc) * (size_t)n_trials, hipMemcpyHostToDevice, st));
+    if ((rc = v->tstage.commit(st))) return rc;
+    return dss_launch_vad_trials(v->d, d_frames, frames_are_f64, v->d_tdesc, n_trials, d_labels, d_logits, st);
+}
+
+// the chunks of a reduction over a trial list: DSS_TRIAL_CHUNK trials per launch, their lengths as kernel arguments
+template <typename F>
+static int trials_reduce(const char *what, int n_trials, const int *len, F launch)
+{
+    if (n_trials < 0 || (n_trials && !len)) { dss_set_error("%s: bad trial list", what); return DSS_EINVAL; }
+    for (int i = 0; i < n_trials; ++i)
+        if (len[i] < 1) { dss_set_error("%s: trial %d has %d frames (at least 1)", what, i, len[i]); return DSS_EINVAL; }
+    if (dss_ensure_device()) return DSS_ENODEV;
+    DssTrialLens tl;
+    long long base = 0;
+    for (int i0 = 0; i0 < n_trials; i0 += DSS_TRIAL_CHUNK) {
+        tl.base = base; tl.first_trial = i0; tl.n = std::min(DSS_TRIAL_CHUNK, n_trials - i0);
+        memset(tl.len, 0, sizeof(tl.len));
+        for (int k = 0; k < tl.n; ++k) { tl.len[k] = len[i0 + k]; base += len[i0 + k]; }
+        int rc = launch(tl);
+        if (rc) return rc;
+    }
+    return DSS_OK;
+}
+
+extern "C" int dss_vad_score_trials_dev(const float *d_logits, const int *d_labels, const unsigned char *d_targets, int n_trials,
+                                        const int *len, double *d_loss, int *d_correct, float *d_prob, void *hip_stream)
+{
+    if (!d_logits || !d_labels || !d_targets || !d_loss || !d_correct) { dss_set_error("dss_vad_score_trials_dev: null argument"); return DSS_EINVAL; }
+    return trials_reduce("dss_vad_score_trials_dev", n_trials, len, [&](const DssTrialLens &tl) {
+        return dss_launch_vad_score_trials(tl, d_logits, d_labels, d_targets, d_loss, d_correct, d_prob, (hipStream_t)hip_stream);
+    });
+}
+
+extern "C" int dss_dec_forward_trials_dev(dss_dec *v, const void *d_frames, int frames_are_f64, long long N, int n_trials,
+                                          const long long *first, const int *len, float *d_feats, void *hip_stream)
+{
+    if (!v || !d_frames || !d_feats) { dss_set_error("dss_dec_forward_trials_dev: bad arguments"); return DSS_EINVAL; }
+    if (!v->loaded) { dss_set_error("dss_dec_forward_trials_dev: no weights loaded (dss_dec_load_weights)"); return DSS_EINVAL; }
+    long long total = 0;
+    int rc = dss_trials_check(N, n_trials, first, len, &total);
+    if (rc) return rc;
+    for (int i = 0; i < n_trials; ++i) {
+        if (len[i] > v->d.T_max) {
+            dss_set_error("dss_dec_forward_trials_dev: trial %d has %d frames, the handle takes %d (max_frames)", i, len[i], v->d.T_max);
+            return DSS_EINVAL;
+        }
+        if (first[i] > 0x7fffffffLL) { dss_set_error("dss_dec_forward_trials_dev: trial %d starts behind row 2^31 - 1", i); return DSS_EINVAL; }
+    }
+    if (!n_trials) return DSS_OK;
+    DSS_HIP_CHECK(hipSetDevice(v->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const size_t n = (size_t)n_trials;
+    std::vector<long long> out_row(n);
+    long long row = 0;
+    for (int i = 0; i < n_trials; ++i) { out_row[i] = row; row += len[i]; }
+    const std::vector<int> order = trials_longest_first(n_trials, len);
+    long long *tout = (long long *)v->tstage.acquire((sizeof(long long) + 2 * sizeof(int)) * n);      // [n] output rows, then [2][n] ints
+    if (!tout) { dss_set_error("pinned staging for the trial table failed"); return DSS_ENOMEM; }
+    int *tmeta = (int *)(tout + n);
+    for (int k = 0; k < n_trials; ++k) { const int i = order[k]; tmeta[k] = len[i]; tmeta[n + k] = (int)first[i]; tout[k] = out_row[i]; }
+    if ((rc = trials_grow(&v->d_tmeta, &v->tmeta_cap, 2 * n)) || (rc = trials_grow(&v->d_tout, &v->tout_cap, n))) return rc;
+    DSS_HIP_CHECK(hipMemcpyAsync(v->d_tmeta, tmeta, sizeof(int) * 2 * n, hipMemcpyHostToDevice, st));
+    DSS_HIP_CHECK(hipMemcpyAsync(v->d_tout, tout, sizeof(long long) * n, hipMemcpyHostToDevice, st));
+    if ((rc = v->tstage.commit(st))) return rc;
+    // chunks of max_streams trials share the handle's layer buffers one after the other; longest first, so a chunk's trials are of
+    // similar length and its padded (trials x longest) grid holds little padding
+    for (int k0 = 0; k0 < n_trials; k0 += v->d.S_max) {
+        const int S = std::min(v->d.S_max, n_trials - k0), T = len[order[k0]];
+        rc = dss_launch_decoder_trials(v->d, d_frames, frames_are_f64, S, T, d_feats, v->d_tmeta + k0, v->d_tmeta + n + k0, v->d_tout + k0, st);
+        if (rc) return rc;
+    }
+    return DSS_OK;
+}
+
+extern "C" int dss_dec_mse_trials_dev(const float *d_feats, const float *d_targets, int n_outputs, int n_trials, const int *len,
+                                      double *d_mse, void *hip_stream)
+{
+    if (!d_feats || !d_targets || !d_mse || n_outputs < 1) { dss_set_error("dss_dec_mse_trials_dev: bad arguments"); return DSS_EINVAL; }
+    return trials_reduce("dss_dec_mse_trials_dev", n_trials, len, [&](const DssTrialLens &tl) {
+        return dss_launch_dec_mse_trials(tl, d_feats, d_targets, n_outputs, d_mse, (hipStream_t)hip_stream);
+    });
 }

@@ -190,6 +190,17 @@ struct DssVadDev {
     float *h, *c;                 // [2 layers][S][H] each
 };
 int dss_launch_vad(const DssVadDev &v, const void *d_frames, int frames_f64, int W, int *d_labels, float *d_logits, hipStream_t s);
+// trial lists (Part 8): one table entry and one workgroup per trial, in table order: rows in_row .. in_row + len of the (N, C)
+// frames go to rows out_row .. of the concatenated outputs; v.h / v.c are neither read nor written
+struct DssVadTrialDesc { long long in_row, out_row; int len, pad; };
+int dss_launch_vad_trials(const DssVadDev &v, const void *d_frames, int frames_f64, const DssVadTrialDesc *d_desc, int n_trials, int *d_labels,
+                          float *d_logits, hipStream_t s);
+// up to DSS_TRIAL_CHUNK consecutive trials of a concatenated (sum len, ...) array, handed to a reduction kernel by value: trial
+// first_trial + k covers rows base + sum(len[:k]) .. + len[k]
+#define DSS_TRIAL_CHUNK 256
+struct DssTrialLens { long long base; int first_trial, n; int len[DSS_TRIAL_CHUNK]; };
+int dss_launch_vad_score_trials(const DssTrialLens &tl, const float *d_logits, const int *d_labels, const unsigned char *d_targets,
+                                double *d_loss, int *d_correct, float *d_prob, hipStream_t s);
 
 // ---- bidirectional recurrent decoder (bilstm_decoder.hip) ----------------------------------------------------
 struct DssDecDev {
@@ -203,6 +214,12 @@ struct DssDecDev {
 // d_counts (frames per stream, <= T), d_in_row (input row of stream s in a buffer of Tin frames per row): device arrays or NULL
 int dss_launch_decoder(const DssDecDev &d, const void *d_frames, int frames_f64, int S, int T, float *d_feats,
                        const int *d_counts, const int *d_in_row, int Tin, hipStream_t s);
+// trial lists (Part 8): S <= S_max trials whose frames start at rows d_first[s] of one (N, C) array and have d_counts[s] <= T
+// frames; features of trial s go to rows d_out_row[s] .. of d_feats, the concatenated (sum len, O) output.  Device arrays.
+int dss_launch_decoder_trials(const DssDecDev &d, const void *d_frames, int frames_f64, int S, int T, float *d_feats,
+                              const int *d_counts, const int *d_first, const long long *d_out_row, hipStream_t s);
+int dss_launch_dec_mse_trials(const DssTrialLens &tl, const float *d_feats, const float *d_targets, int n_outputs, double *d_mse,
+                              hipStream_t s);
 
 struct DssHgaDev {
     int S, C, fs, nsec;

@@ -62,3 +62,42 @@ struct DssPinnedRing {
         return DSS_OK;
     }
 };
+
+// One grow-only page-locked block for a call's variable-size table (the trial lists of Part 8): acquire(bytes) waits until the
+// copies of the call before it have run (its event), so the block is never rewritten under a queued copy, and hipMemcpyAsync out
+// of it is asynchronous (pageable memory would be staged by the runtime, and may hold the host behind the stream's earlier work).
+struct DssPinnedStage {
+    void *host = nullptr;
+    size_t cap = 0;
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+
+    void *acquire(size_t bytes)
+    {
+        if (pending) {
+            if (hipEventSynchronize(ev) != hipSuccess) return nullptr;
+            pending = false;
+        }
+        if (bytes > cap) {
+            if (host) { hipHostFree(host); host = nullptr; cap = 0; }
+            if (hipHostMalloc(&host, bytes, hipHostMallocDefault) != hipSuccess) { host = nullptr; return nullptr; }
+            cap = bytes;
+        }
+        if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { ev = nullptr; return nullptr; }
+        return host;
+    }
+    // call after the copies out of the block have been issued on s
+    int commit(hipStream_t s)
+    {
+        DSS_HIP_CHECK(hipEventRecord(ev, s));
+        pending = true;
+        return DSS_OK;
+    }
+    void destroy()
+    {
+        if (pending && ev) hipEventSynchronize(ev);
+        if (host) hipHostFree(host);
+        if (ev) hipEventDestroy(ev);
+        host = nullptr; ev = nullptr; cap = 0; pending = false;
+    }
+};

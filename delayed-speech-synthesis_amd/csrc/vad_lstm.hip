@@ -227,3 +227,151 @@ int dss_launch_vad(const DssVadDev &v, const void *d_frames, int frames_f64, int
     DSS_HIP_CHECK(hipGetLastError());
     return DSS_OK;
 }
+
+// ---- a trial list in one launch (dss_vad_forward_trials_dev; the reference's validation pass, train_unidirectional_vad.py:181-215) ----
+// Trial k is rows in_row .. in_row + len of one (N, C) array and starts from the zero state of both layers; its labels and logits go
+// to rows out_row .. of the concatenated outputs.  One workgroup per trial, one stream wide (SW = 1): the arithmetic of a trial is,
+// term for term, what vad_lstm_kernel<FrameT, 1> does for the only stream of a one-stream handle stepped through all len frames in
+// one call -- the same vad_dot / vad_dot_steps chains per gate row, the same cell update, the same classifier loop -- so the
+// results are the same bits.  The table comes sorted longest trial first: workgroups are dispatched in index order, so the long
+// trials start first and the short ones fill the CUs they leave (a trial is a serial chain of len steps; nothing else balances
+// it).  The handle's persistent (h, c) are not touched: h lives in LDS and c in registers for the length of the trial.
+
+template <typename FrameT>
+__global__ void __launch_bounds__(VAD_THREADS, 5)         // 5 waves per SIMD = two trials per CU: one hides the other's L2 and barrier waits
+vad_trials_kernel(DssVadDev v, const FrameT *__restrict__ frames, const DssVadTrialDesc *__restrict__ desc, int *__restrict__ labels,
+                  float *__restrict__ logits)
+{
+    typedef typename VadVec<1>::type V;
+    __shared__ __attribute__((aligned(16))) V xin[VAD_TP][VAD_MAXC];
+    __shared__ __attribute__((aligned(16))) V h0s[VAD_TP][VAD_MAXH];
+    __shared__ __attribute__((aligned(16))) V hs[2][VAD_MAXH];
+    __shared__ __attribute__((aligned(16))) V gates[4 * VAD_MAXH];
+    __shared__ float lg[2];
+    const DssVadTrialDesc d = desc[blockIdx.x];
+    const int tid = threadIdx.x, C = v.C, H = v.H, H4 = 4 * H, W = d.len;
+    const int Cp = (C + 3) & ~3, Hp = (H + 3) & ~3;
+    const FrameT *x = frames + (size_t)d.in_row * C;
+    int *lab = labels + d.out_row;
+    float *lgo = logits ? logits + (size_t)d.out_row * 2 : nullptr;
+    float c0 = 0.f, c1 = 0.f;                              // create_new_initial_state: zeros (models.py:22-24)
+    for (int k = tid; k < 2 * VAD_MAXH; k += VAD_THREADS) reinterpret_cast<float *>(hs)[k] = 0.f;
+    for (int k = tid; k < VAD_TP * VAD_MAXH; k += VAD_THREADS) reinterpret_cast<float *>(h0s)[k] = 0.f;
+    for (int k = tid; k < VAD_TP * VAD_MAXC; k += VAD_THREADS) reinterpret_cast<float *>(xin)[k] = 0.f;
+    __syncthreads();
+    const bool rowt = tid < H4;
+    const float bias0 = rowt ? v.b0[tid] : 0.f, bias1 = rowt ? v.b1[tid] : 0.f;
+    for (int w0 = 0; w0 < W; w0 += VAD_TP) {
+        const int nst = min(VAD_TP, W - w0);
+        for (int idx = tid; idx < nst * C; idx += VAD_THREADS) {
+            const int tt = idx / C, k = idx - tt * C;
+            xin[tt][k].v = (float)x[(size_t)(w0 + tt) * C + k];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int layer = 0; layer < 2; ++layer) {
+            V pre[VAD_TP];
+#pragma unroll
+            for (int tt = 0; tt < VAD_TP; ++tt) pre[tt].v = 0.f;
+            if (rowt) {
+                if (layer == 0) vad_dot_steps<1, V, VAD_MAXC>(pre, v.wT0, H4, tid, xin, Cp);
+                else vad_dot_steps<1, V, VAD_MAXH>(pre, v.wT1, H4, tid, h0s, Hp);
+            }
+#pragma unroll
+            for (int tt = 0; tt < VAD_TP; ++tt) {
+                if (tt >= nst) break;
+                if (rowt) {
+                    V acc = pre[tt];
+                    if (layer == 0) vad_dot<1, V>(acc, v.wT0 + (size_t)Cp * H4, H4, tid, hs[0], Hp);
+                    else vad_dot<1, V>(acc, v.wT1 + (size_t)Hp * H4, H4, tid, hs[1], Hp);
+                    acc.v += layer == 0 ? bias0 : bias1;
+                    gates[tid] = acc;
+                }
+                __syncthreads();
+                if (tid < H) {
+                    const float gi = gates[tid].v, gf = gates[H + tid].v, gg = gates[2 * H + tid].v, go = gates[3 * H + tid].v;
+                    float &c = layer == 0 ? c0 : c1;
+                    c = vad_sigmoid(gf) * c + vad_sigmoid(gi) * tanhf(gg);
+                    const float h = vad_sigmoid(go) * tanhf(c);
+                    hs[layer][tid].v = h;
+                    if (layer == 0) h0s[tt][tid].v = h;
+                }
+                __syncthreads();
+                if (layer == 1) {
+                    const int w = w0 + tt;
+                    if (tid < 2) {
+                        float a = 0.f;
+                        for (int k = 0; k < H; ++k) a = __builtin_fmaf(v.wc[tid * H + k], hs[1][k].v, a);
+                        a += v.bc[tid];
+                        lg[tid] = a;
+                        if (lgo) lgo[(size_t)w * 2 + tid] = a;
+                    }
+                    __syncthreads();
+                    if (tid == 0) lab[w] = lg[1] > lg[0] ? 1 : 0;      // the step kernel's tie rule: equal logits are non-speech
+                }
+            }
+        }
+    }
+}
+
+int dss_launch_vad_trials(const DssVadDev &v, const void *d_frames, int frames_f64, const DssVadTrialDesc *desc, int n_trials, int *d_labels,
+                          float *d_logits, hipStream_t st)
+{
+    if (v.H < 1 || v.H > VAD_MAXH || 4 * v.H > VAD_THREADS || v.C < 1 || v.C > VAD_MAXC) {
+        dss_set_error("VAD kernel: hidden size %d / %d inputs out of range (<= %d / <= %d)", v.H, v.C, VAD_MAXH, VAD_MAXC);
+        return DSS_EINVAL;
+    }
+    if (n_trials < 1) return DSS_OK;
+    if (frames_f64) hipLaunchKernelGGL((vad_trials_kernel<double>), dim3(n_trials), dim3(VAD_THREADS), 0, st, v, (const double *)d_frames, desc, d_labels, d_logits);
+    else hipLaunchKernelGGL((vad_trials_kernel<float>), dim3(n_trials), dim3(VAD_THREADS), 0, st, v, (const float *)d_frames, desc, d_labels, d_logits);
+    DSS_HIP_CHECK(hipGetLastError());
+    return DSS_OK;
+}
+
+// ---- scoring a trial list (dss_vad_score_trials_dev): what the validation pass derives from the logits of a trial --------------
+// Per frame, in float64 from the float32 logits: loss = logsumexp(z) - z[target] (nn.CrossEntropyLoss), prob = softmax(z)[1].
+// Per trial: the mean of the losses, summed IN FRAME ORDER by one thread (tiles of 256 frames go through LDS), and the number of
+// frames whose label equals the target.  One workgroup per trial; the launch's trials and their lengths travel as kernel
+// arguments (DssTrialLens), so the entry point needs no handle and no device scratch.
+#define SCORE_THREADS 256
+__global__ void __launch_bounds__(SCORE_THREADS)
+vad_score_trials_kernel(DssTrialLens tl, const float *__restrict__ logits, const int *__restrict__ labels,
+                        const unsigned char *__restrict__ targets, double *__restrict__ loss, int *__restrict__ correct,
+                        float *__restrict__ prob)
+{
+    __shared__ double ls[SCORE_THREADS];
+    __shared__ int cs[SCORE_THREADS];
+    const int tid = threadIdx.x, k = blockIdx.x;
+    long long off = tl.base;
+    for (int j = 0; j < k; ++j) off += tl.len[j];
+    const int L = tl.len[k];
+    double acc = 0.0;
+    int corr = 0;
+    for (int t0 = 0; t0 < L; t0 += SCORE_THREADS) {
+        const int t = t0 + tid;
+        if (t < L) {
+            const double z0 = logits[(off + t) * 2], z1 = logits[(off + t) * 2 + 1];
+            const int tg = targets[off + t];
+            const double m = fmax(z0, z1);
+            const double lse = m + log(exp(z0 - m) + exp(z1 - m));
+            ls[tid] = lse - (tg ? z1 : z0);
+            cs[tid] = labels[off + t] == tg ? 1 : 0;
+            if (prob) prob[off + t] = (float)exp(z1 - lse);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            const int n = min(SCORE_THREADS, L - t0);
+            for (int j = 0; j < n; ++j) { acc += ls[j]; corr += cs[j]; }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) { loss[tl.first_trial + k] = acc / (double)L; correct[tl.first_trial + k] = corr; }
+}
+
+int dss_launch_vad_score_trials(const DssTrialLens &tl, const float *d_logits, const int *d_labels, const unsigned char *d_targets,
+                                double *d_loss, int *d_correct, float *d_prob, hipStream_t st)
+{
+    hipLaunchKernelGGL(vad_score_trials_kernel, dim3(tl.n), dim3(SCORE_THREADS), 0, st, tl, d_logits, d_labels, d_targets, d_loss, d_correct, d_prob);
+    DSS_HIP_CHECK(hipGetLastError());
+    return DSS_OK;
+}

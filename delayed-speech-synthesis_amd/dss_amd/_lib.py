@@ -129,6 +129,11 @@ def _declare(L):
         "dss_avad_labels_trials": (i, [vp, vp, C.c_longlong, i, vp, vp, vp, vp, vp, vp, vp]),
         "dss_avad_labels_trials_dev": (i, [vp, vp, C.c_longlong, i, vp, vp, vp, vp, vp, vp, vp, vp]),
         "dss_avad_vote_host": (i, [vp, i, vp, vp, vp]),
+        "dss_trials_check": (i, [C.c_longlong, i, vp, vp, vp]),
+        "dss_vad_forward_trials_dev": (i, [vp, vp, i, C.c_longlong, i, vp, vp, vp, vp, vp]),
+        "dss_vad_score_trials_dev": (i, [vp, vp, vp, i, vp, vp, vp, vp, vp]),
+        "dss_dec_forward_trials_dev": (i, [vp, vp, i, C.c_longlong, i, vp, vp, vp, vp]),
+        "dss_dec_mse_trials_dev": (i, [vp, vp, i, i, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -122,3 +122,22 @@ class BiLstmDecoderGPU:
                                                     None if r is None else r.ctypes.data, c.ctypes.data, n, int(n_frames),
                                                     feats.data_ptr(), s))
         return feats
+
+    def forward_trials_torch(self, frames, ranges):
+        """The decoder on every trial of a corpus in one call (``dss_dec_forward_trials_dev``): frames is a CUDA (N, C) float64 or
+        float32 tensor, ``ranges`` [(first, len)] in rows (overlapping, any order; more than max_streams run in chunks inside the
+        call; a trial longer than max_frames raises), every trial as a whole from a fresh state.  Returns float32 CUDA features
+        (sum len, n_outputs), trial after trial in list order."""
+        import torch
+        from .validation import _ranges
+        if frames.dtype not in (torch.float64, torch.float32):
+            raise TypeError("frames must be float64 or float32")
+        if frames.dim() != 2 or frames.shape[1] != self.C or not frames.is_cuda:
+            raise ValueError(f"frames must be a CUDA tensor of shape (N, {self.C})")
+        frames = frames.contiguous()
+        first, length, total = _ranges(self._L, int(frames.shape[0]), ranges)
+        feats = torch.empty((total, self.O), dtype=torch.float32, device=frames.device)
+        _lib.check(self._L.dss_dec_forward_trials_dev(self._h, frames.data_ptr(), int(frames.dtype == torch.float64), int(frames.shape[0]),
+                                                      len(first), first.ctypes.data, length.ctypes.data, feats.data_ptr(),
+                                                      torch.cuda.current_stream().cuda_stream))
+        return feats

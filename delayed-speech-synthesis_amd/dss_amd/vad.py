@@ -98,6 +98,27 @@ class VadLstmGPU:
                                             logits.data_ptr() if want_logits else None, torch.cuda.current_stream().cuda_stream))
         return (labels, logits) if want_logits else labels
 
+    def forward_trials_torch(self, frames, ranges, want_logits: bool = False):
+        """The detector on every trial of a corpus in one launch (``dss_vad_forward_trials_dev``): frames is a CUDA (N, C) float64
+        or float32 tensor, ``ranges`` [(first, len)] in rows (any number, overlapping, any order), every trial from the zero
+        state.  Returns int32 CUDA labels (sum len,) [, float32 logits (sum len, 2)], trial after trial in list order.  The
+        streaming state of this object (``step_torch``, ``state``) is not touched."""
+        import torch
+        from .validation import _ranges
+        if frames.dtype not in (torch.float64, torch.float32):
+            raise TypeError("frames must be float64 or float32")
+        if frames.dim() != 2 or frames.shape[1] != self.C or not frames.is_cuda:
+            raise ValueError(f"frames must be a CUDA tensor of shape (N, {self.C})")
+        frames = frames.contiguous()
+        first, length, total = _ranges(self._L, int(frames.shape[0]), ranges)
+        labels = torch.empty((total,), dtype=torch.int32, device=frames.device)
+        logits = torch.empty((total, 2), dtype=torch.float32, device=frames.device) if want_logits else None
+        _lib.check(self._L.dss_vad_forward_trials_dev(self._h, frames.data_ptr(), int(frames.dtype == torch.float64), int(frames.shape[0]),
+                                                      len(first), first.ctypes.data, length.ctypes.data, labels.data_ptr(),
+                                                      logits.data_ptr() if want_logits else None,
+                                                      torch.cuda.current_stream().cuda_stream))
+        return (labels, logits) if want_logits else labels
+
     def state(self):
         """(h, c), host float32 arrays [2][S][H]."""
         h = np.empty((2, self.S, self.H), np.float32)

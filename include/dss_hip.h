@@ -14,6 +14,9 @@
  * local/training.py:165-207, and the north-star batch configs need).
  * Part 3 is the HGA operator (extensions/hga/hga_optimized.pyx and HighGammaExtractor,
  * local/units.py:97-161).
+ * Parts 4-6 are the speech gate and the two recurrent models of the online path, Part 7 the acoustic labels of a
+ * training corpus, Part 8 the two recurrent models over the trials of such a corpus (the validation passes of the
+ * reference's training scripts), each described at its declarations.
  *
  * Error convention: functions returning int return 0 on success and a negative DSS_E* code on failure;
  * dss_last_error() gives a thread-local message.  Creators return NULL on failure (the reference's
@@ -479,6 +482,46 @@ int dss_avad_labels_trials_dev(dss_avad *h, const int16_t *d_audio, long long n_
  * reference's; the sum behind the mean is taken in the device kernel's order (256 strided running sums, then a halving
  * tree), not numpy's pairwise one.  labels: W bytes; threshold may be NULL. */
 int dss_avad_vote_host(const double *log_energy, int W, const dss_avad_params *p, unsigned char *labels, double *threshold);
+
+/* ------------------------------------------------------------------------------------------------
+ * Part 8 -- the two recurrent models over the trials of a corpus, and their validation scores.  A corpus is concatenated
+ * arrays cut into trials (hga_activity (N, C), vad_labels, lpc_coefficients, trial_ids: prepare_corpus.py:218-234); the
+ * reference's training scripts run every validation trial through the model from a fresh state once per epoch and score it:
+ * train_unidirectional_vad.py:181-215 (per-trial nn.CrossEntropyLoss summed over the trials, softmax / argmax per frame, frame
+ * accuracy against vad_labels) and train_bidirectional_model.py:165-188 (per-trial nn.MSELoss, averaged over the trials).
+ * Here a whole trial list is one call.  Trial k is rows first[k] .. first[k] + len[k] of d_frames, (N, n_inputs) float64
+ * (frames_are_f64 != 0) or float32; ranges may overlap and come in any order; first / len are HOST arrays.  Outputs are
+ * concatenated in list order: row sum(len[:k]) + t is frame t of trial k (the convention of dss_hga_extract_trials).  Every
+ * trial starts from the zero state (create_new_initial_state).  Training itself (gradients, optimiser, dropout) is not here.
+ * On one handle, trial-list calls are issued on one stream, or one after the other has finished: the handle keeps the
+ * call's trial table.
+ * ---------------------------------------------------------------------------------------------- */
+/* The argument checks of the two forward entry points on their own (no device needed): DSS_EINVAL with the reason in
+ * dss_last_error() for a NULL pointer, a negative count, len < 1, first < 0 or first + len > N; else 0 and *total = sum(len). */
+int dss_trials_check(long long N, int n_trials, const long long *first, const int *len, long long *total);
+/* The detector of Part 5 on every trial, one launch for any n_trials (it need not fit the handle's n_streams): a workgroup
+ * per trial, longest first.  d_labels int32[sum len]; d_logits float32[sum len][2] or NULL.  The handle's streaming state
+ * (dss_vad_step_dev, dss_vad_state) is neither read nor written.  A trial's labels and logits are bit-identical to
+ * dss_vad_step_dev on a one-stream handle that is given the trial's len[k] frames in one call from the zero state. */
+int dss_vad_forward_trials_dev(dss_vad *v, const void *d_frames, int frames_are_f64, long long N, int n_trials,
+                               const long long *first, const int *len, int *d_labels, float *d_logits, void *hip_stream);
+/* Scores of such logits and labels against d_targets, uint8[sum len] (0 / 1, vad_labels) in the same concatenated order; len is
+ * a HOST array.  Per frame, evaluated in float64 from the float32 logits z: d_prob[i] = softmax(z)[1] as float32 (or NULL).
+ * Per trial: d_loss[k] = the mean over its frames of logsumexp(z) - z[target], summed in frame order in float64 (the
+ * reference's cfunc on one trial); d_correct[k] = the number of its frames with label == target. */
+int dss_vad_score_trials_dev(const float *d_logits, const int *d_labels, const unsigned char *d_targets, int n_trials,
+                             const int *len, double *d_loss /* [n_trials] */, int *d_correct /* [n_trials] */,
+                             float *d_prob /* [sum len] or NULL */, void *hip_stream);
+/* The decoder of Part 6 on every trial, each as a whole from a fresh state (its backward direction starts at its own last
+ * frame): d_feats float32[sum len][n_outputs].  Lists longer than the handle's max_streams run in chunks inside the call; a
+ * trial longer than max_frames is an error (nothing is truncated); first[k] must be below 2^31.  A trial's features are
+ * bit-identical to dss_dec_forward_rows_dev on the same frames. */
+int dss_dec_forward_trials_dev(dss_dec *v, const void *d_frames, int frames_are_f64, long long N, int n_trials,
+                               const long long *first, const int *len, float *d_feats, void *hip_stream);
+/* d_mse[k] = the mean over trial k's len[k] x n_outputs elements of (d_feats - d_targets)^2, both float32[sum len][n_outputs],
+ * accumulated in float64 in a fixed order (256 strided running sums, then a halving tree). */
+int dss_dec_mse_trials_dev(const float *d_feats, const float *d_targets, int n_outputs, int n_trials, const int *len,
+                           double *d_mse /* [n_trials] */, void *hip_stream);
 
 #ifdef __cplusplus
 }
