@@ -2194,6 +2194,14 @@ struct dss_vad {
     size_t tdesc_cap = 0;
 };
 
+int dss_vad_device_weights(dss_vad *v, int *device, int *n_inputs, int *hidden_units, float *w[6])
+{
+    if (!v || !v->loaded) { dss_set_error("the detector handle is NULL or has no weights loaded (dss_vad_load_weights)"); return DSS_EINVAL; }
+    *device = v->device; *n_inputs = v->d.C; *hidden_units = v->d.H;
+    for (int k = 0; k < 6; ++k) w[k] = v->w[k];
+    return DSS_OK;
+}
+
 extern "C" dss_vad *dss_vad_create(int n_streams, int n_inputs, int hidden_units)
 {
     if (n_streams <= 0 || n_inputs <= 0 || hidden_units <= 0) { dss_set_error("VAD dims must be positive"); return nullptr; }

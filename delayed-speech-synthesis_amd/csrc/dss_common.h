@@ -202,6 +202,32 @@ struct DssTrialLens { long long base; int first_trial, n; int len[DSS_TRIAL_CHUN
 int dss_launch_vad_score_trials(const DssTrialLens &tl, const float *d_logits, const int *d_labels, const unsigned char *d_targets,
                                 double *d_loss, int *d_correct, float *d_prob, hipStream_t s);
 
+// ---- training of the neural detector (vad_train.hip; Part 9) -------------------------------------------------
+#define DSS_VAD_TRAIN_MAXT 4096   // largest max_window of a trainer (the workspace takes about 22 H + C floats per frame)
+struct DssVadTrainDev {
+    DssVadDev v;                  // S = 1.  What the forward half reads: the packed copies below; wc / bc point into p; h / c are the
+                                  //   carried state, [2 layers][H] each
+    int Tmax;                     // max_window: the rows of the workspace
+    float *p, *g, *sq;            // master parameters (torch layout), gradients of the last window, RMSprop square averages: flat, the
+                                  //   ten tensors in state_dict order (dss_vad_trainer_read)
+    float *wT0, *b0, *wT1, *b1;   // the packed copies (v.wT0 ...), writable: the step kernel refreshes them
+    // workspace of one window.  The forward pass leaves: the frames as float32; per layer the gate activations i, f, g, o and
+    // c and h with one row in front (row 0 = the window's initial state, row t + 1 = after frame t); layer 0's masked output
+    float *xs;                    // [Tmax][C]
+    float *act0, *act1;           // [Tmax][4H]
+    float *c0, *c1, *h0, *h1;     // [Tmax + 1][H]
+    float *h0m;                   // [Tmax][H]
+    float *logit, *dl;            // [Tmax][2]: logits; (softmax - onehot) / T
+    double *lossf;                // [Tmax]: per-frame cross-entropy
+    // ... and the backward pass: the gate gradients, and what layer 1 sends to layer 0's h (through W_ih_l1 and the mask)
+    float *dg0, *dg1;             // [Tmax][4H]
+    float *dh0m;                  // [Tmax][H]
+};
+long dss_vad_train_param_count(int C, int H);
+// one window: loss, gradients (d.g), the carried state advanced; parameters, square averages and packed copies updated if apply_step
+int dss_launch_vad_train_window(const DssVadTrainDev &d, const void *d_frames, int frames_f64, int T, const unsigned char *d_targets,
+                                const float *d_mask, int apply_step, double lr, double alpha, double eps, double *d_loss, hipStream_t s);
+
 // ---- bidirectional recurrent decoder (bilstm_decoder.hip) ----------------------------------------------------
 struct DssDecDev {
     int S_max, T_max, C, H, O;    // capacity (streams x frames per call), inputs per frame, hidden units per direction, outputs (20)

@@ -10,6 +10,11 @@ int dss_ensure_device(void);
 // DSS_EINVAL with a message otherwise (pageable or cached page-locked memory, a short block, misalignment).
 int dss_fine_host_view(void *p, size_t bytes, size_t align, const char *what, void **dev);
 
+// The device arrays of an inference detector (Part 5), for dss_vad_trainer_publish: the handle's device, its sizes and
+// the six weight arrays wT0, b0, wT1, b1, wc, bc, writable.  DSS_EINVAL with a message for NULL or a handle without weights.
+struct dss_vad;
+int dss_vad_device_weights(dss_vad *v, int *device, int *n_inputs, int *hidden_units, float *w[6]);
+
 // Small host -> device uploads that must not stall, and must not be overwritten, while earlier calls are still queued.
 //
 // hipMemcpyAsync from pageable memory may wait for the stream's earlier work (the runtime stages it), which would hold the

@@ -1,0 +1,364 @@
+// csrc/vad_train.hip -- one training step of the neural voice-activity detector (gfx950): truncated backpropagation through
+// time over one window, and the RMSprop update.
+//
+// Restates, for batch size 1 (the only one the reference's script uses),
+//   train_unidirectional_vad.py:155-175   per window of T frames: forward from the carried state, nn.CrossEntropyLoss (mean
+//                                         over the T frames), backward to all ten parameter tensors, optim.step(),
+//                                         state.detach() -- the gradient stops at the window's initial state
+//   torch.optim.RMSprop(lr, alpha, eps)   sq <- alpha sq + (1 - alpha) g^2;  p <- p - lr g / (sqrt(sq) + eps)
+//   nn.LSTM(dropout = p), train mode      layer 0's output, as layer 1 reads it, times a mask of 0 or 1 / (1 - p); the mask is an
+//                                         INPUT here, (T, H) multipliers or NULL -- the kernels hold no generator
+// Two launches per window ("Training the detector"):
+//   vad_train_window_kernel  one workgroup of 640 threads, everything that is serial in time: the forward pass (the chains of
+//                            vad_lstm.hip's kernels, vad_lstm_dot.h) with the stash the backward pass needs, the loss, dlogits,
+//                            and backward through time for layer 1, then layer 0 -- the gate gradients dG1[T][4H], dG0[T][4H]
+//   vad_train_step_kernel    one workgroup per gate row (and per class of the head): the weight gradients dG^T . inputs as sums
+//                            over t in frame order, the bias gradients, and, fused, the RMSprop update of the master parameters
+//                            (torch layout) and of the packed copies the forward pass reads
+// Every sum has a fixed order and there are no atomics: the same call from the same state gives the same bits.  Fused
+// multiply-adds are written out (__builtin_fmaf), as in vad_lstm.hip; the library is built with -ffp-contract=off.
+#include "vad_lstm_dot.h"
+
+// offsets of the ten tensors in the flat parameter array (state_dict order; also of the gradients and the square averages)
+struct VadTrainOff { int wih0, whh0, bih0, bhh0, wih1, whh1, bih1, bhh1, wc, bc, total; };
+__host__ __device__ static inline VadTrainOff vad_train_off(int C, int H)
+{
+    VadTrainOff o;
+    const int H4 = 4 * H;
+    o.wih0 = 0;
+    o.whh0 = o.wih0 + H4 * C;
+    o.bih0 = o.whh0 + H4 * H;
+    o.bhh0 = o.bih0 + H4;
+    o.wih1 = o.bhh0 + H4;
+    o.whh1 = o.wih1 + H4 * H;
+    o.bih1 = o.whh1 + H4 * H;
+    o.bhh1 = o.bih1 + H4;
+    o.wc = o.bhh1 + H4;
+    o.bc = o.wc + 2 * H;
+    o.total = o.bc + 2;
+    return o;
+}
+
+long dss_vad_train_param_count(int C, int H) { return vad_train_off(C, H).total; }
+
+// W^T dg for one gate's H rows of a row-major [4H][H] matrix: output column j = sum over the gate's rows r, IN ROW ORDER, of
+// W[r][j] dg[r].  Lanes run along the columns, so a wave's load is 256 consecutive bytes of one row; eight loads in flight.
+__device__ __forceinline__ float vad_tdot(const float *W, int H, int j, const float *dg)
+{
+    float acc = 0.f;
+    int r = 0;
+    for (; r + 8 <= H; r += 8) {
+        float w[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) w[u] = W[(size_t)(r + u) * H + j];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc = __builtin_fmaf(w[u], dg[r + u], acc);
+    }
+    for (; r < H; ++r) acc = __builtin_fmaf(W[(size_t)r * H + j], dg[r], acc);
+    return acc;
+}
+
+// Backward through time of one layer.  Thread u < H owns unit u: dh = (what the step after this one sends through W_hh) +
+// (what arrives from above: the head for layer 1, layer 1's W_ih through the mask for layer 0); dc likewise carries f dc of
+// the step after.  The four gate gradients of the step go to dgs (LDS) and to dG (the workspace); then all 640 threads form
+// W_hh^T dG for the step before: thread (gate q, column j) sums the H rows of gate q, and the owner adds the four parts as
+// (i + f) + (g + o).  Nothing is sent below step 0: the gradient stops at the window's initial state.
+template <int LAYER>
+__device__ __forceinline__ void vad_bptt_layer(const DssVadTrainDev &d, const VadTrainOff &o, int T, int tid, float *dgs,
+                                               float (*part)[VAD_MAXH])
+{
+    const int H = d.v.H, H4 = 4 * H;
+    const float *act = LAYER ? d.act1 : d.act0, *call = LAYER ? d.c1 : d.c0;
+    float *dG = LAYER ? d.dg1 : d.dg0;
+    const float *Whh = d.p + (LAYER ? o.whh1 : o.whh0);
+    const int q = tid / VAD_MAXH, j = tid - q * VAD_MAXH;
+    const bool own = tid < H;
+    float dcn = 0.f, wc0 = 0.f, wc1 = 0.f;
+    if (LAYER == 1 && own) { wc0 = d.p[o.wc + tid]; wc1 = d.p[o.wc + H + tid]; }
+    for (int t = T - 1; t >= 0; --t) {
+        if (own) {
+            float dh = t == T - 1 ? 0.f : (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
+            if (LAYER == 1) dh += __builtin_fmaf(wc1, d.dl[2 * t + 1], wc0 * d.dl[2 * t]);
+            else dh += d.dh0m[(size_t)t * H + tid];
+            const float *a = act + (size_t)t * H4;
+            const float gi = a[tid], gf = a[H + tid], gg = a[2 * H + tid], go = a[3 * H + tid];
+            const float c = call[(size_t)(t + 1) * H + tid], cp = call[(size_t)t * H + tid];
+            const float tc = tanhf(c);
+            const float dc = __builtin_fmaf(dh * go, 1.f - tc * tc, dcn);
+            const float di = dc * gg * (gi * (1.f - gi));
+            const float df = dc * cp * (gf * (1.f - gf));
+            const float dg = dc * gi * (1.f - gg * gg);
+            const float dO = dh * tc * (go * (1.f - go));
+            dcn = dc * gf;
+            dgs[tid] = di; dgs[H + tid] = df; dgs[2 * H + tid] = dg; dgs[3 * H + tid] = dO;
+            float *g = dG + (size_t)t * H4;
+            g[tid] = di; g[H + tid] = df; g[2 * H + tid] = dg; g[3 * H + tid] = dO;
+        }
+        __syncthreads();
+        if (t > 0 && j < H) part[q][j] = vad_tdot(Whh + (size_t)q * H * H, H, j, dgs + q * H);
+        __syncthreads();
+    }
+}
+
+template <typename FrameT>
+__global__ void __launch_bounds__(VAD_THREADS)
+vad_train_window_kernel(DssVadTrainDev d, const FrameT *__restrict__ frames, int T, const unsigned char *__restrict__ targets,
+                        const float *__restrict__ mask, double *__restrict__ loss)
+{
+    typedef typename VadVec<1>::type V;
+    __shared__ __attribute__((aligned(16))) V xin[VAD_TP][VAD_MAXC];
+    __shared__ __attribute__((aligned(16))) V h0s[VAD_TP][VAD_MAXH];      // layer 0's MASKED h of the chunk's frames (layer 1's inputs)
+    __shared__ __attribute__((aligned(16))) V hs[2][VAD_MAXH];            // the h each layer carries to its own next step (never masked)
+    __shared__ __attribute__((aligned(16))) V gates[4 * VAD_MAXH];
+    __shared__ float dgs[4 * VAD_MAXH];                                   // the gate gradients of the step in hand
+    __shared__ float part[4][VAD_MAXH];                                   // W^T dG per gate, before the owner adds them
+    __shared__ __attribute__((aligned(16))) float dg4[4 * VAD_MAXH][VAD_TP];     // dG1 of a chunk of frames, frames side by side
+    __shared__ __attribute__((aligned(16))) float part4[4][VAD_MAXH][VAD_TP];
+    const DssVadDev &v = d.v;
+    const int tid = threadIdx.x, C = v.C, H = v.H, H4 = 4 * H;
+    const int Cp = (C + 3) & ~3, Hp = (H + 3) & ~3;
+    const VadTrainOff o = vad_train_off(C, H);
+    const bool own = tid < H, rowt = tid < H4;
+
+    // ---- forward: vad_trials_kernel's chains from the carried state, with the stash ------------------------------------------
+    float c0 = 0.f, c1 = 0.f;
+    for (int k = tid; k < 2 * VAD_MAXH; k += VAD_THREADS) reinterpret_cast<float *>(hs)[k] = 0.f;
+    for (int k = tid; k < VAD_TP * VAD_MAXH; k += VAD_THREADS) reinterpret_cast<float *>(h0s)[k] = 0.f;
+    for (int k = tid; k < VAD_TP * VAD_MAXC; k += VAD_THREADS) reinterpret_cast<float *>(xin)[k] = 0.f;
+    __syncthreads();
+    if (own) {
+        const float ha = v.h[tid], hb = v.h[H + tid];
+        c0 = v.c[tid]; c1 = v.c[H + tid];
+        hs[0][tid].v = ha; hs[1][tid].v = hb;
+        d.h0[tid] = ha; d.h1[tid] = hb; d.c0[tid] = c0; d.c1[tid] = c1;     // row 0 of the stashes: the window's initial state
+    }
+    const float bias0 = rowt ? v.b0[tid] : 0.f, bias1 = rowt ? v.b1[tid] : 0.f;
+    for (int w0 = 0; w0 < T; w0 += VAD_TP) {
+        const int nst = min(VAD_TP, T - w0);
+        for (int idx = tid; idx < nst * C; idx += VAD_THREADS) {
+            const int tt = idx / C, k = idx - tt * C;
+            const float x = (float)frames[(size_t)(w0 + tt) * C + k];
+            xin[tt][k].v = x;
+            d.xs[(size_t)(w0 + tt) * C + k] = x;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int layer = 0; layer < 2; ++layer) {
+            V pre[VAD_TP];
+#pragma unroll
+            for (int tt = 0; tt < VAD_TP; ++tt) pre[tt].v = 0.f;
+            if (rowt) {
+                if (layer == 0) vad_dot_steps<1, V, VAD_MAXC>(pre, v.wT0, H4, tid, xin, Cp);
+                else vad_dot_steps<1, V, VAD_MAXH>(pre, v.wT1, H4, tid, h0s, Hp);
+            }
+#pragma unroll
+            for (int tt = 0; tt < VAD_TP; ++tt) {
+                if (tt >= nst) break;
+                const int t = w0 + tt;
+                if (rowt) {
+                    V acc = pre[tt];
+                    if (layer == 0) vad_dot<1, V>(acc, v.wT0 + (size_t)Cp * H4, H4, tid, hs[0], Hp);
+                    else vad_dot<1, V>(acc, v.wT1 + (size_t)Hp * H4, H4, tid, hs[1], Hp);
+                    acc.v += layer == 0 ? bias0 : bias1;
+                    gates[tid] = acc;
+                }
+                __syncthreads();
+                if (own) {
+                    const float gi = vad_sigmoid(gates[tid].v), gf = vad_sigmoid(gates[H + tid].v), gg = tanhf(gates[2 * H + tid].v),
+                                go = vad_sigmoid(gates[3 * H + tid].v);
+                    float &c = layer == 0 ? c0 : c1;
+                    c = gf * c + gi * gg;
+                    const float h = go * tanhf(c);
+                    hs[layer][tid].v = h;
+                    float *a = (layer == 0 ? d.act0 : d.act1) + (size_t)t * H4;
+                    a[tid] = gi; a[H + tid] = gf; a[2 * H + tid] = gg; a[3 * H + tid] = go;
+                    (layer == 0 ? d.c0 : d.c1)[(size_t)(t + 1) * H + tid] = c;
+                    (layer == 0 ? d.h0 : d.h1)[(size_t)(t + 1) * H + tid] = h;
+                    if (layer == 0) {
+                        const float hm = mask ? h * mask[(size_t)t * H + tid] : h;
+                        h0s[tt][tid].v = hm;
+                        d.h0m[(size_t)t * H + tid] = hm;
+                    }
+                }
+                __syncthreads();
+                if (layer == 1) {
+                    if (tid < 2) {
+                        float a = 0.f;
+                        for (int k = 0; k < H; ++k) a = __builtin_fmaf(v.wc[tid * H + k], hs[1][k].v, a);
+                        d.logit[2 * t + tid] = a + v.bc[tid];
+                    }
+                    // (the next step writes hs[1] only behind its own first barrier)
+                }
+            }
+        }
+    }
+    if (own) { v.h[tid] = hs[0][tid].v; v.h[H + tid] = hs[1][tid].v; v.c[tid] = c0; v.c[H + tid] = c1; }
+    __syncthreads();
+
+    // ---- loss and dlogits: per frame in float64 from the float32 logits, the mean summed in frame order ---------------------
+    for (int t = tid; t < T; t += VAD_THREADS) {
+        const double z0 = d.logit[2 * t], z1 = d.logit[2 * t + 1];
+        const int tg = targets[t] ? 1 : 0;
+        const double m = fmax(z0, z1);
+        const double lse = m + log(exp(z0 - m) + exp(z1 - m));
+        d.lossf[t] = lse - (tg ? z1 : z0);
+        d.dl[2 * t] = (float)((exp(z0 - lse) - (tg ? 0.0 : 1.0)) / (double)T);
+        d.dl[2 * t + 1] = (float)((exp(z1 - lse) - (tg ? 1.0 : 0.0)) / (double)T);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double acc = 0.0;
+        for (int t = 0; t < T; ++t) acc += d.lossf[t];
+        *loss = acc / (double)T;
+    }
+
+    // ---- backward: layer 1 through time, then what it sends down through W_ih_l1 and the mask, then layer 0 -----------------
+    vad_bptt_layer<1>(d, o, T, tid, dgs, part);
+    {
+        const float *Wih1 = d.p + o.wih1;
+        const int q = tid / VAD_MAXH, j = tid - q * VAD_MAXH;
+        for (int t0 = 0; t0 < T; t0 += VAD_TP) {
+            const int nst = min(VAD_TP, T - t0);
+            if (rowt) {
+#pragma unroll
+                for (int tt = 0; tt < VAD_TP; ++tt) dg4[tid][tt] = tt < nst ? d.dg1[(size_t)(t0 + tt) * H4 + tid] : 0.f;
+            }
+            __syncthreads();
+            if (j < H) {
+                const float *W = Wih1 + (size_t)q * H * H;
+                vf4 acc = {0.f, 0.f, 0.f, 0.f};
+                int r = 0;
+                for (; r + 4 <= H; r += 4) {
+                    float w[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) w[u] = W[(size_t)(r + u) * H + j];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const vf4 g = *reinterpret_cast<const vf4 *>(dg4[q * H + r + u]);
+                        acc.x = __builtin_fmaf(w[u], g.x, acc.x); acc.y = __builtin_fmaf(w[u], g.y, acc.y);
+                        acc.z = __builtin_fmaf(w[u], g.z, acc.z); acc.w = __builtin_fmaf(w[u], g.w, acc.w);
+                    }
+                }
+                for (; r < H; ++r) {
+                    const float w = W[(size_t)r * H + j];
+                    const vf4 g = *reinterpret_cast<const vf4 *>(dg4[q * H + r]);
+                    acc.x = __builtin_fmaf(w, g.x, acc.x); acc.y = __builtin_fmaf(w, g.y, acc.y);
+                    acc.z = __builtin_fmaf(w, g.z, acc.z); acc.w = __builtin_fmaf(w, g.w, acc.w);
+                }
+                *reinterpret_cast<vf4 *>(part4[q][j]) = acc;
+            }
+            __syncthreads();
+            if (own) {
+                for (int tt = 0; tt < nst; ++tt) {
+                    float s = (part4[0][tid][tt] + part4[1][tid][tt]) + (part4[2][tid][tt] + part4[3][tid][tt]);
+                    if (mask) s *= mask[(size_t)(t0 + tt) * H + tid];
+                    d.dh0m[(size_t)(t0 + tt) * H + tid] = s;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    vad_bptt_layer<0>(d, o, T, tid, dgs, part);
+}
+
+// ---- the parallel part: weight gradients and the RMSprop update --------------------------------------------------------------
+// Workgroup b < 8H is gate row r of layer L (b = L 4H + r): its columns are [W_ih row | W_hh row | bias], column k's gradient is
+// sum over t = 0 .. T-1, in that order, of dG[t][r] in[t][k] (one fused multiply-add per frame; the bias adds dG[t][r] itself).
+// Workgroups 8H and 8H + 1 are the two classes of the head: [classifier.weight row | classifier.bias] against dlogits.
+// The inputs: layer 0 reads the frames (xs) and its own h of the step before (row t of h0: row 0 is the window's initial h);
+// layer 1 the masked h of layer 0 (h0m) and its own h of the step before; the head h1 of the step itself (row t + 1).
+// The update is evaluated per element in float64 from the stored float32 values and rounded once: inside the bounds that
+// cover torch's own float32 sequence (mul, addcmul, sqrt, add, addcdiv).  bias_ih and bias_hh get the same g and each its own
+// square average; the packed bias is their float32 sum.
+#define VTS_THREADS 256
+
+__device__ __forceinline__ float vad_rmsprop(const DssVadTrainDev &d, int k, float g, int apply, double lr, double alpha, double eps)
+{
+    d.g[k] = g;
+    if (!apply) return d.p[k];
+    const float sq = (float)(alpha * (double)d.sq[k] + (1.0 - alpha) * ((double)g * (double)g));
+    d.sq[k] = sq;
+    const float p = (float)((double)d.p[k] - lr * (double)g / (sqrt((double)sq) + eps));
+    d.p[k] = p;
+    return p;
+}
+
+__global__ void __launch_bounds__(VTS_THREADS)
+vad_train_step_kernel(DssVadTrainDev d, int T, int apply, double lr, double alpha, double eps)
+{
+    __shared__ float dgt[VTS_THREADS];
+    const int tid = threadIdx.x, b = blockIdx.x, C = d.v.C, H = d.v.H, H4 = 4 * H;
+    const int Cp = (C + 3) & ~3, Hp = (H + 3) & ~3;
+    const VadTrainOff o = vad_train_off(C, H);
+    const bool head = b >= 2 * H4;
+    const int L = head ? 2 : b / H4, r = head ? b - 2 * H4 : b - L * H4;
+    const float *dg = head ? d.dl + r : (L ? d.dg1 : d.dg0) + r;
+    const int dgs = head ? 2 : H4;
+    const float *inA = head ? d.h1 + H : (L ? d.h0m : d.xs), *inB = L ? d.h1 : d.h0;
+    const int nA = head || L ? H : C, nB = head ? 0 : H, ncol = nA + nB + 1;
+    // two columns per thread: ncol <= 128 + 160 + 1
+    const float *src[2];
+    int stride[2], col[2];
+    bool live[2], bias[2];
+    float acc[2] = {0.f, 0.f};
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        col[u] = tid + u * VTS_THREADS;
+        live[u] = col[u] < ncol;
+        bias[u] = col[u] == ncol - 1;
+        const bool a = col[u] < nA;
+        src[u] = a ? inA + col[u] : inB + (col[u] - nA);
+        stride[u] = a ? nA : H;
+        if (!live[u] || bias[u]) { src[u] = inA; stride[u] = 0; }
+    }
+    for (int t0 = 0; t0 < T; t0 += VTS_THREADS) {
+        const int n = min(VTS_THREADS, T - t0);
+        if (tid < n) dgt[tid] = dg[(size_t)(t0 + tid) * dgs];
+        __syncthreads();
+        for (int tt = 0; tt < n; ++tt) {
+            const float g = dgt[tt];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const float x = bias[u] ? 1.f : src[u][(size_t)(t0 + tt) * stride[u]];
+                acc[u] = __builtin_fmaf(g, x, acc[u]);
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        if (!live[u]) continue;
+        const int k = col[u];
+        if (head) {
+            vad_rmsprop(d, bias[u] ? o.bc + r : o.wc + r * H + k, acc[u], apply, lr, alpha, eps);
+        } else if (bias[u]) {
+            const float bi = vad_rmsprop(d, (L ? o.bih1 : o.bih0) + r, acc[u], apply, lr, alpha, eps);
+            const float bh = vad_rmsprop(d, (L ? o.bhh1 : o.bhh0) + r, acc[u], apply, lr, alpha, eps);
+            if (apply) (L ? d.b1 : d.b0)[r] = bi + bh;
+        } else {
+            const bool a = k < nA;
+            const int pk = a ? (L ? o.wih1 : o.wih0) + r * nA + k : (L ? o.whh1 : o.whh0) + r * H + (k - nA);
+            const float p = vad_rmsprop(d, pk, acc[u], apply, lr, alpha, eps);
+            // the packed copy: [inputs / 4][4H rows][4 consecutive inputs], W_hh behind W_ih's padded inputs
+            const int ki = a ? k : (L ? Hp : Cp) + (k - nA);
+            if (apply) (L ? d.wT1 : d.wT0)[((size_t)(ki >> 2) * H4 + r) * 4 + (ki & 3)] = p;
+        }
+    }
+}
+
+int dss_launch_vad_train_window(const DssVadTrainDev &d, const void *d_frames, int frames_f64, int T, const unsigned char *d_targets,
+                                const float *d_mask, int apply_step, double lr, double alpha, double eps, double *d_loss, hipStream_t st)
+{
+    const int H = d.v.H, C = d.v.C;
+    if (H < 1 || H > VAD_MAXH || 4 * H > VAD_THREADS || C < 1 || C > VAD_MAXC || T < 1 || T > d.Tmax) {
+        dss_set_error("VAD training kernel: %d hidden units / %d inputs / %d frames out of range (<= %d / <= %d / <= %d)", H, C, T,
+                      VAD_MAXH, VAD_MAXC, d.Tmax);
+        return DSS_EINVAL;
+    }
+    if (frames_f64) hipLaunchKernelGGL((vad_train_window_kernel<double>), dim3(1), dim3(VAD_THREADS), 0, st, d, (const double *)d_frames, T, d_targets, d_mask, d_loss);
+    else hipLaunchKernelGGL((vad_train_window_kernel<float>), dim3(1), dim3(VAD_THREADS), 0, st, d, (const float *)d_frames, T, d_targets, d_mask, d_loss);
+    DSS_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(vad_train_step_kernel, dim3(8 * H + 2), dim3(VTS_THREADS), 0, st, d, T, apply_step, lr, alpha, eps);
+    DSS_HIP_CHECK(hipGetLastError());
+    return DSS_OK;
+}

@@ -134,6 +134,17 @@ def _declare(L):
         "dss_vad_score_trials_dev": (i, [vp, vp, vp, i, vp, vp, vp, vp, vp]),
         "dss_dec_forward_trials_dev": (i, [vp, vp, i, C.c_longlong, i, vp, vp, vp, vp]),
         "dss_dec_mse_trials_dev": (i, [vp, vp, i, i, vp, vp, vp]),
+        "dss_vad_trainer_check": (i, [i, i, i, i, i, i]),
+        "dss_vad_trainer_param_count": (C.c_long, [i, i]),
+        "dss_vad_trainer_create": (vp, [i, i, i]),
+        "dss_vad_trainer_destroy": (None, [vp]),
+        "dss_vad_trainer_load": (i, [vp] * 11),
+        "dss_vad_trainer_read": (i, [vp, i, vp]),
+        "dss_vad_trainer_state": (i, [vp, vp, vp, i]),
+        "dss_vad_trainer_reset_state": (i, [vp, vp]),
+        "dss_vad_trainer_window_dev": (i, [vp, vp, i, i, vp, vp, i, C.c_double, C.c_double, C.c_double, vp, vp]),
+        "dss_vad_trainer_trial_dev": (i, [vp, vp, i, i, vp, vp, i, C.c_double, C.c_double, C.c_double, vp, vp]),
+        "dss_vad_trainer_publish": (i, [vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

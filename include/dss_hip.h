@@ -16,7 +16,7 @@
  * local/units.py:97-161).
  * Parts 4-6 are the speech gate and the two recurrent models of the online path, Part 7 the acoustic labels of a
  * training corpus, Part 8 the two recurrent models over the trials of such a corpus (the validation passes of the
- * reference's training scripts), each described at its declarations.
+ * reference's training scripts), Part 9 the training of the neural detector, each described at its declarations.
  *
  * Error convention: functions returning int return 0 on success and a negative DSS_E* code on failure;
  * dss_last_error() gives a thread-local message.  Creators return NULL on failure (the reference's
@@ -492,7 +492,7 @@ int dss_avad_vote_host(const double *log_energy, int W, const dss_avad_params *p
  * Here a whole trial list is one call.  Trial k is rows first[k] .. first[k] + len[k] of d_frames, (N, n_inputs) float64
  * (frames_are_f64 != 0) or float32; ranges may overlap and come in any order; first / len are HOST arrays.  Outputs are
  * concatenated in list order: row sum(len[:k]) + t is frame t of trial k (the convention of dss_hga_extract_trials).  Every
- * trial starts from the zero state (create_new_initial_state).  Training itself (gradients, optimiser, dropout) is not here.
+ * trial starts from the zero state (create_new_initial_state).  The detector's training is Part 9; the decoder's is not here.
  * On one handle, trial-list calls are issued on one stream, or one after the other has finished: the handle keeps the
  * call's trial table.
  * ---------------------------------------------------------------------------------------------- */
@@ -522,6 +522,65 @@ int dss_dec_forward_trials_dev(dss_dec *v, const void *d_frames, int frames_are_
  * accumulated in float64 in a fixed order (256 strided running sums, then a halving tree). */
 int dss_dec_mse_trials_dev(const float *d_feats, const float *d_targets, int n_outputs, int n_trials, const int *len,
                            double *d_mse /* [n_trials] */, void *hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Part 9 -- training the neural detector of Part 5: the loop of train_unidirectional_vad.py:135-175 (truncated backpropagation
+ * through time with k1 == k2, batch size 1, torch.optim.RMSprop) as two launches per window (csrc/vad_train.hip).  A window is T
+ * frames of one trial (1 <= T <= max_window; the script uses 50) with 0 / 1 targets: forward from the carried state,
+ * nn.CrossEntropyLoss (the mean over the T frames), the gradient of that loss with respect to all ten parameter tensors,
+ * backpropagated through the window's T steps and stopped at its initial state (state.detach(), line 173), then
+ *     sq <- alpha sq + (1 - alpha) g^2;   p <- p - lr g / (sqrt(sq) + eps)       (momentum 0, not centred, no weight decay)
+ * per element; bias_ih and bias_hh have equal gradients and each its own square average.  The final (h, c) of both layers is
+ * carried to the next window.  Dropout (nn.LSTM(dropout = p) in train mode) multiplies layer 0's output, as layer 1 reads it, by a
+ * mask of 0 or 1 / (1 - p) -- not layer 1's output, not the h layer 0 carries to its own next step; the mask is an INPUT here,
+ * float32 (T, H) multipliers or NULL for none, and the backward pass uses the same one.  The kernels hold no generator.
+ * Every reduction has a fixed order: the same call from the same state gives the same bits.  Fused multiply-adds are used.
+ *
+ * Flat arrays (dss_vad_trainer_read) hold the ten tensors in state_dict order, each in torch's layout:
+ *     lstm.weight_ih_l0 [4H][C], lstm.weight_hh_l0 [4H][H], lstm.bias_ih_l0 [4H], lstm.bias_hh_l0 [4H],
+ *     lstm.weight_ih_l1 [4H][H], lstm.weight_hh_l1 [4H][H], lstm.bias_ih_l1 [4H], lstm.bias_hh_l1 [4H],
+ *     classifier.weight [2][H], classifier.bias [2]                  -- dss_vad_trainer_param_count(C, H) floats in all.
+ * Calls on one trainer are issued on one stream, or one after the other has finished.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct dss_vad_trainer dss_vad_trainer;
+/* The argument checks of this part on their own (no device needed): DSS_EINVAL with the reason in dss_last_error() for sizes that
+ * are not positive or beyond the kernels' capacities (hidden_units <= 160, n_inputs <= 128, max_window <= 4096), a window of T < 1
+ * or T > max_window frames, a trial of len < 1 frames, or trial windows of window < 1 or > max_window frames; else 0.  A caller
+ * that has no trial (or no single window) in hand passes 1 for the arguments it does not mean. */
+int dss_vad_trainer_check(int n_inputs, int hidden_units, int max_window, int T, int len, int window);
+long dss_vad_trainer_param_count(int n_inputs, int hidden_units);
+dss_vad_trainer *dss_vad_trainer_create(int n_inputs, int hidden_units, int max_window);
+void dss_vad_trainer_destroy(dss_vad_trainer *tr);
+/* The ten host arrays of dss_vad_load_weights.  Zeroes the square averages, the gradients and the carried state. */
+int dss_vad_trainer_load(dss_vad_trainer *tr, const float *w_ih0, const float *w_hh0, const float *b_ih0, const float *b_hh0,
+                         const float *w_ih1, const float *w_hh1, const float *b_ih1, const float *b_hh1,
+                         const float *cls_w, const float *cls_b);
+/* One flat host array (see above): what = 0 the parameters, 1 the gradients of the last window, 2 the square averages.  Waits
+ * for the device. */
+int dss_vad_trainer_read(dss_vad_trainer *tr, int what, float *out);
+/* Host copies of the carried state, [2 layers][H] each, either may be NULL; set == 0 reads, else writes.  Waits for the device.
+ * dss_vad_trainer_reset_state zeroes it (create_new_initial_state: a new trial), enqueued on hip_stream. */
+int dss_vad_trainer_state(dss_vad_trainer *tr, float *h, float *c, int set);
+int dss_vad_trainer_reset_state(dss_vad_trainer *tr, void *hip_stream);
+/* One window, enqueued on hip_stream.  Device pointers: d_frames (T, n_inputs) float64 (frames_are_f64 != 0; cast to float32
+ * like the script's .float()) or float32; d_targets uint8[T] (0 / 1); d_mask float32 (T, H) or NULL; *d_loss receives the
+ * window's loss (float64, from the float32 logits).  Always computes the loss and the gradients and advances the carried state;
+ * parameters, square averages and the packed copies the forward pass reads change only if apply_step != 0. */
+int dss_vad_trainer_window_dev(dss_vad_trainer *tr, const void *d_frames, int frames_are_f64, int T, const unsigned char *d_targets,
+                               const float *d_mask, int apply_step, double lr, double alpha, double eps, double *d_loss,
+                               void *hip_stream);
+/* One trial (the script's lines 146-175), enqueued on hip_stream with no host synchronisation between the windows: the state is
+ * reset, then windows of `window` frames are stepped in order, the last one being the remainder (len mod window, possibly one
+ * frame), each with apply_step.  d_frames (len, n_inputs), d_targets uint8[len], d_masks float32 (len, H) or NULL, d_losses
+ * float64[ceil(len / window)].  Returns the number of windows.  Bit-identical to dss_vad_trainer_reset_state followed by
+ * dss_vad_trainer_window_dev on the same slices. */
+int dss_vad_trainer_trial_dev(dss_vad_trainer *tr, const void *d_frames, int frames_are_f64, int len, const unsigned char *d_targets,
+                              const float *d_masks, int window, double lr, double alpha, double eps, double *d_losses,
+                              void *hip_stream);
+/* Copies the current weights, in the packed form the forward kernels read (b = bias_ih + bias_hh in float32), device to device
+ * into an inference handle of the same n_inputs and hidden_units that has weights loaded; enqueued on hip_stream.  After it Part 5
+ * and Part 8 run on the trained weights with no host round trip.  The handle's recurrent state is not touched. */
+int dss_vad_trainer_publish(dss_vad_trainer *tr, dss_vad *v, void *hip_stream);
 
 #ifdef __cplusplus
 }

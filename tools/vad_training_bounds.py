@@ -1,0 +1,48 @@
+#!/usr/bin/env python3
+"""Measure the gradient bound of the detector's training tests without a GPU.
+
+For every case of tests/vad_training_reference.GRAD_CASES, with and without a dropout mask, torch float32 CPU autograd is compared
+with the float64 reference (``autograd_window``) per tensor: max|g32 - g64| / max|g64|.  The bound of the GPU tests is 4 x the worst
+of these figures, rounded up to one significant digit; it is stored as ``GRAD_BOUND`` in the helper module, and this tool says
+whether the stored constant still equals what it measures.
+
+    python tools/vad_training_bounds.py
+"""
+import math
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "delayed-speech-synthesis_amd")]
+
+
+def round_up_1(x: float) -> float:
+    e = math.floor(math.log10(x))
+    return math.ceil(x / 10 ** e - 1e-9) * 10 ** e
+
+
+def main() -> int:
+    import torch
+    import vad_training_reference as V
+    torch.set_num_threads(min(8, os.cpu_count() or 1))
+    worst = (0.0, None)
+    runs = [(case, mask, "random") for case in V.GRAD_CASES for mask in (None, "random")]
+    runs += [(V.GRAD_CASES[0], "zero_row", "random"), (V.GRAD_CASES[0], "random", "one_class")]       # the two extra windows of the GPU test
+    for case, mask, targets in runs:
+        if True:
+            sd, x, y, state, m = V.case_inputs(case, mask, targets)
+            _, g64, _ = V.autograd_window(sd, x, y, state, m)
+            _, g32, _ = V.autograd_window(sd, x, y, state, m, dtype=torch.float32)
+            err = V.rel_errors(g32, g64)
+            k = max(err, key=err.get)
+            print(f"(H, C, T, scale) = {case}  mask = {mask!s:8} targets = {targets:9}  worst tensor {k:22} {err[k]:.3g}")
+            if err[k] > worst[0]:
+                worst = (err[k], (case, mask, k))
+    bound = round_up_1(4.0 * worst[0])
+    print(f"torch float32 worst: {worst[0]:.3g} at {worst[1]};  4 x = {4 * worst[0]:.3g}  ->  bound {bound:g}")
+    print(f"stored GRAD_BOUND = {V.GRAD_BOUND:g}" + ("" if math.isclose(bound, V.GRAD_BOUND, rel_tol=1e-9) else "   (differs: this CPU's torch rounds differently, or the cases changed)"))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
