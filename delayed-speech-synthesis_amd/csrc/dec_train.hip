@@ -1,0 +1,427 @@
+// csrc/dec_train.hip -- one training step of the bidirectional decoder (gfx950): backpropagation through a whole trial, and the
+// RMSprop update.
+//
+// Restates, for batch size 1 (the only one the reference's script uses),
+//   train_bidirectional_model.py:134-152  per trial of T frames: forward from the zero state, nn.MSELoss (the mean over the T x O
+//                                         elements), backward to all eighteen parameter tensors, optim.step()
+//   torch.optim.RMSprop(lr, alpha, eps)   sq <- alpha sq + (1 - alpha) g^2;  p <- p - lr g / (sqrt(sq) + eps)
+//   nn.LSTM(dropout = p), train mode      layer 0's output [h_forward(t) | h_backward(t)], as layer 1 reads it, times a mask of 0 or
+//                                         1 / (1 - p); the mask is an INPUT here, (T, 2H) multipliers or NULL
+// The steps of one direction of one layer are serial; the two directions of a layer are independent, and so are the frames
+// everywhere else.  Seven launches per trial on one stream ("Training the decoder"):
+//   dec_train_layer_kernel<0>, <1>   a workgroup per direction: bilstm_layer_kernel's chain for one stream (dec_lstm_dot.h, the
+//                                    row of W_hh in registers, the same cell update) with the stash the backward pass needs
+//   dec_train_head_kernel            a workgroup per 8 frames: features (dec_regress_kernel's dot product), dfeat, the per-frame
+//                                    loss terms, dtop = W_r^T dfeat
+//   dec_train_bptt_kernel<1>         a workgroup per direction: backward through time, the gate gradients dG1[dir][T][4H]; a
+//                                    third workgroup adds the per-frame loss terms in frame order
+//   dec_train_dmid_kernel            a workgroup per 8 frames: what layer 1 sends down through both W_ih_l1 and the mask
+//   dec_train_bptt_kernel<0>         dG0[dir][T][4H]
+//   dec_train_step_kernel            a workgroup per gate row of each (layer, direction) and per row of the regressor: the weight
+//                                    gradients as sums over t in frame order, the bias gradients and, fused, the RMSprop update
+//                                    of the master parameters (torch layout) and of the packed copies the forward pass reads
+// Every sum has a fixed order and there are no atomics: the same call from the same state gives the same bits.  Fused
+// multiply-adds are written out (__builtin_fmaf); the library is built with -ffp-contract=off.
+#include "dec_lstm_dot.h"
+
+// offsets of the eighteen tensors in the flat parameter array (state_dict order; also of the gradients and the square averages)
+__host__ __device__ static inline DssDecTrainOff dec_train_off(int C, int H, int O)
+{
+    DssDecTrainOff o;
+    const int H4 = 4 * H;
+    int k = 0;
+    for (int L = 0; L < 2; ++L)
+        for (int dir = 0; dir < 2; ++dir) {
+            o.wih[L][dir] = k; k += H4 * (L ? 2 * H : C);
+            o.whh[L][dir] = k; k += H4 * H;
+            o.bih[L][dir] = k; k += H4;
+            o.bhh[L][dir] = k; k += H4;
+        }
+    o.wr = k; k += O * 2 * H;
+    o.br = k; k += O;
+    o.total = k;
+    return o;
+}
+
+long dss_dec_train_param_count(int C, int H, int O) { return dec_train_off(C, H, O).total; }
+
+// ---- forward, one layer: bilstm_layer_kernel<., 1> for one stream, with the stash ---------------------------------------------
+// blockIdx.x is the direction; step s is frame s (forward) or T - 1 - s (backward).  The dot products, the bias add and the cell
+// update are the inference kernel's, term for term, so the features of a trial without a mask are its bits.
+template <typename InT, int LAYER>
+__global__ void __launch_bounds__(DEC_THREADS)
+dec_train_layer_kernel(DssDecTrainDev d, const InT *__restrict__ in, int T, const float *__restrict__ mask)
+{
+    typedef typename DecVec<1>::type V;
+    __shared__ __attribute__((aligned(16))) V xin[DEC_TP][DEC_MAXC];
+    __shared__ __attribute__((aligned(16))) V hs[DEC_MAXH];               // units H .. Hp-1 stay zero
+    __shared__ __attribute__((aligned(16))) V gates[4 * DEC_MAXH];
+    const int tid = threadIdx.x, H = d.H, H4 = 4 * H, dir = blockIdx.x;
+    const int Cin = LAYER ? 2 * H : d.C;
+    const int Cp = (Cin + 3) & ~3, Hp = (H + 3) & ~3;
+    const float *wT = d.wT[LAYER][dir];
+    const bool own = tid < H, rowt = tid < H4;
+    float *act = d.act[LAYER][dir], *cst = d.c[LAYER][dir], *hst = d.h[LAYER][dir];
+    float c = 0.f;
+    for (int k = tid; k < DEC_MAXH; k += DEC_THREADS) hs[k].v = 0.f;
+    for (int k = tid; k < DEC_TP * DEC_MAXC; k += DEC_THREADS) reinterpret_cast<float *>(xin)[k] = 0.f;
+    if (own) { cst[tid] = 0.f; hst[tid] = 0.f; }           // row 0 of the stashes: the zero state
+    const float bias = rowt ? d.b[LAYER][dir][tid] : 0.f;
+    df4 whh[DEC_MAXH / 4];                                 // this thread's row of W_hh, in registers for all steps
+    {
+        const df4 *wr = reinterpret_cast<const df4 *>(wT + (size_t)Cp * H4) + (rowt ? tid : 0);
+#pragma unroll
+        for (int q = 0; q < DEC_MAXH / 4; ++q) whh[q] = (rowt && 4 * q < Hp) ? wr[(size_t)q * H4] : (df4){0.f, 0.f, 0.f, 0.f};
+    }
+    __syncthreads();
+    for (int step0 = 0; step0 < T; step0 += DEC_TP) {
+        const int nst = min(DEC_TP, T - step0);
+        for (int idx = tid; idx < nst * Cin; idx += DEC_THREADS) {
+            const int tt = idx / Cin, k = idx - tt * Cin;
+            const int step = step0 + tt, t = dir ? T - 1 - step : step;
+            const float x = (float)in[(size_t)t * Cin + k];
+            xin[tt][k].v = x;
+            if (LAYER == 0 && dir == 0) d.xs[(size_t)t * Cin + k] = x;
+        }
+        __syncthreads();
+        V pre[DEC_TP];
+#pragma unroll
+        for (int tt = 0; tt < DEC_TP; ++tt) pre[tt].v = 0.f;
+        if (rowt) dec_dot_steps<1, V>(pre, wT, H4, tid, xin, Cp);          // (steps beyond nst: stale inputs, never used)
+#pragma unroll
+        for (int tt = 0; tt < DEC_TP; ++tt) {
+            if (tt >= nst) break;
+            const int step = step0 + tt, t = dir ? T - 1 - step : step;
+            if (rowt) {
+                V acc = pre[tt];
+#pragma unroll
+                for (int q = 0; q < DEC_MAXH / 4; ++q) {
+                    if (4 * q >= Hp) break;
+                    const V x0 = hs[4 * q], x1 = hs[4 * q + 1], x2 = hs[4 * q + 2], x3 = hs[4 * q + 3];
+                    acc.v = __builtin_fmaf(whh[q].x, x0.v, acc.v);
+                    acc.v = __builtin_fmaf(whh[q].y, x1.v, acc.v);
+                    acc.v = __builtin_fmaf(whh[q].z, x2.v, acc.v);
+                    acc.v = __builtin_fmaf(whh[q].w, x3.v, acc.v);
+                }
+                acc.v += bias;
+                gates[tid] = acc;
+            }
+            __syncthreads();
+            if (own) {
+                const float gi = dec_sigmoid(gates[tid].v), gf = dec_sigmoid(gates[H + tid].v), gg = tanhf(gates[2 * H + tid].v),
+                            go = dec_sigmoid(gates[3 * H + tid].v);
+                c = gf * c + gi * gg;
+                const float h = go * tanhf(c);
+                hs[tid].v = h;                             // the unmasked h is what the direction carries to its own next step
+                float *a = act + (size_t)step * H4;
+                a[tid] = gi; a[H + tid] = gf; a[2 * H + tid] = gg; a[3 * H + tid] = go;
+                cst[(size_t)(step + 1) * H + tid] = c;
+                hst[(size_t)(step + 1) * H + tid] = h;
+                const size_t oi = (size_t)t * (2 * H) + dir * H + tid;
+                if (LAYER == 0) d.midm[oi] = mask ? h * mask[oi] : h;
+                else d.top[oi] = h;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// ---- head, loss terms, gradient of the features ---------------------------------------------------------------------------------
+// A workgroup takes DTH_ROWS frames.  feat[t][o] = b[o] + sum_k w[o][k] top[t][k], dec_regress_kernel's dot product term for term;
+// dfeat = 2 (feat - target) / (T O), evaluated in float64 and rounded once; lossf[t] = sum over o, in that order, of the squared
+// differences in float64; dtop[t][k] = sum over o, in that order, of w[o][k] dfeat[t][o].
+#define DTH_ROWS 8
+__global__ void __launch_bounds__(256)
+dec_train_head_kernel(DssDecTrainDev d, int T, const float *__restrict__ targets)
+{
+    extern __shared__ __attribute__((aligned(16))) float rs[];             // [O][K + 1] weights, [DTH_ROWS][K] inputs, [DTH_ROWS][O] dfeat
+    __shared__ double es[DTH_ROWS][DSS_DEC_MAXO];
+    const int tid = threadIdx.x, K = 2 * d.H, O = d.O;
+    const DssDecTrainOff o = dec_train_off(d.C, d.H, O);
+    const float *w = d.p + o.wr, *b = d.p + o.br;
+    float *ws = rs, *xs = rs + (size_t)O * (K + 1), *dfs = xs + (size_t)DTH_ROWS * K;
+    const int t0 = blockIdx.x * DTH_ROWS, nst = min(DTH_ROWS, T - t0);
+    for (int k = tid; k < O * K; k += 256) { const int oo = k / K, j = k - oo * K; ws[oo * (K + 1) + j] = w[k]; }
+    for (int k = tid; k < DTH_ROWS * K; k += 256) xs[k] = k / K < nst ? d.top[(size_t)t0 * K + k] : 0.f;
+    __syncthreads();
+    for (int idx = tid; idx < nst * O; idx += 256) {
+        const int rr = idx / O, oo = idx - rr * O;
+        const float *x = xs + rr * K, *wr = ws + oo * (K + 1);
+        float a = 0.f;
+        for (int k = 0; k < K; ++k) a = __builtin_fmaf(wr[k], x[k], a);
+        const float f = a + b[oo];
+        const size_t fi = (size_t)(t0 + rr) * O + oo;
+        const double e = (double)f - (double)targets[fi];
+        const float df = (float)(2.0 * e / ((double)T * (double)O));
+        d.feat[fi] = f;
+        d.dfeat[fi] = df;
+        dfs[idx] = df;
+        es[rr][oo] = e;
+    }
+    __syncthreads();
+    if (tid < nst) {
+        double acc = 0.0;
+        for (int oo = 0; oo < O; ++oo) acc += es[tid][oo] * es[tid][oo];
+        d.lossf[t0 + tid] = acc;
+    }
+    for (int idx = tid; idx < nst * K; idx += 256) {
+        const int rr = idx / K, k = idx - rr * K;
+        float a = 0.f;
+        for (int oo = 0; oo < O; ++oo) a = __builtin_fmaf(ws[oo * (K + 1) + k], dfs[rr * O + oo], a);
+        d.dtop[(size_t)(t0 + rr) * K + k] = a;
+    }
+}
+
+// ---- backward through time of one (layer, direction) --------------------------------------------------------------------------
+// blockIdx.x is the direction.  Thread u < H owns unit u: dh = (what the step after this one sends through W_hh) + (what arrives
+// from above at the step's frame: dtop for layer 1, dmid for layer 0); dc likewise carries f dc of the step after, in a register.
+// "The step after" is in the direction's own time: frame t + 1 forward, frame t - 1 backward, so the backward direction walks the
+// frames upward.  The four gate gradients of the step go to LDS and to dG at the step's FRAME; then thread (gate q, column j)
+// forms its part of W_hh^T dG for the step before from column j of gate q's rows of the row-major master copy, which it holds in
+// registers for the whole trial (the H rows in row order), and the owner adds the four parts as (i + f) + (g + o).
+// The owner's seven stash values of a step are loaded one step ahead, so their latency is off the chain.
+// Layer 1's launch has a third workgroup: the trial's loss, the per-frame terms added in frame order in float64.
+template <int LAYER>
+__global__ void __launch_bounds__(DEC_THREADS)
+dec_train_bptt_kernel(DssDecTrainDev d, int T, double *__restrict__ loss)
+{
+    __shared__ __attribute__((aligned(16))) float dgs[4][DEC_MAXH];       // the gate gradients of the step in hand; units >= H stay zero
+    __shared__ float part[4][DEC_MAXH];                                   // W_hh^T dG per gate, before the owner adds them
+    const int tid = threadIdx.x, H = d.H, H4 = 4 * H;
+    if (LAYER == 1 && blockIdx.x == 2) {
+        __shared__ double ls[DSS_DEC_TRAIN_MAXT];
+        for (int t = tid; t < T; t += DEC_THREADS) ls[t] = d.lossf[t];
+        __syncthreads();
+        if (tid == 0) {
+            double acc = 0.0;
+            for (int t = 0; t < T; ++t) acc += ls[t];
+            *loss = acc / ((double)T * (double)d.O);
+        }
+        return;
+    }
+    const int dir = blockIdx.x;
+    const DssDecTrainOff o = dec_train_off(d.C, H, d.O);
+    const float *Whh = d.p + (dir ? o.whh[LAYER][1] : o.whh[LAYER][0]);
+    const int q = tid / DEC_MAXH, j = tid - q * DEC_MAXH;
+    const bool own = tid < H, colt = j < H;
+    float wt[DEC_MAXH];
+#pragma unroll
+    for (int r = 0; r < DEC_MAXH; ++r) wt[r] = (colt && r < H) ? Whh[((size_t)q * H + r) * H + j] : 0.f;
+    reinterpret_cast<float *>(dgs)[tid] = 0.f;             // (DEC_THREADS == 4 * DEC_MAXH)
+    const float *act = dir ? d.act[LAYER][1] : d.act[LAYER][0], *cst = dir ? d.c[LAYER][1] : d.c[LAYER][0];
+    const float *up = (LAYER ? d.dtop : d.dmid) + dir * H + tid;
+    float *dG = dir ? d.dg[LAYER][1] : d.dg[LAYER][0];
+    // the owner's stash values of step s, into seven registers
+#define DEC_LOAD_STEP(s)                                                                                                           \
+    do {                                                                                                                           \
+        const float *a_ = act + (size_t)(s) * H4;                                                                                  \
+        n_gi = a_[tid]; n_gf = a_[H + tid]; n_gg = a_[2 * H + tid]; n_go = a_[3 * H + tid];                                        \
+        n_c = cst[(size_t)((s) + 1) * H + tid]; n_cp = cst[(size_t)(s) * H + tid];                                                 \
+        n_up = up[(size_t)(dir ? T - 1 - (s) : (s)) * (2 * H)];                                                                    \
+    } while (0)
+    float n_gi = 0.f, n_gf = 0.f, n_gg = 0.f, n_go = 0.f, n_c = 0.f, n_cp = 0.f, n_up = 0.f;
+    if (own) DEC_LOAD_STEP(T - 1);
+    float dcn = 0.f;
+    __syncthreads();
+    for (int s = T - 1; s >= 0; --s) {
+        if (own) {
+            const float v_gi = n_gi, v_gf = n_gf, v_gg = n_gg, v_go = n_go, v_c = n_c, v_cp = n_cp, v_up = n_up;
+            if (s > 0) DEC_LOAD_STEP(s - 1);
+            const int t = dir ? T - 1 - s : s;
+            float dh = s == T - 1 ? 0.f : (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
+            dh += v_up;
+            const float tc = tanhf(v_c);
+            const float dc = __builtin_fmaf(dh * v_go, 1.f - tc * tc, dcn);
+            const float di = dc * v_gg * (v_gi * (1.f - v_gi));
+            const float df = dc * v_cp * (v_gf * (1.f - v_gf));
+            const float dg = dc * v_gi * (1.f - v_gg * v_gg);
+            const float dO = dh * tc * (v_go * (1.f - v_go));
+            dcn = dc * v_gf;
+            dgs[0][tid] = di; dgs[1][tid] = df; dgs[2][tid] = dg; dgs[3][tid] = dO;
+            float *g = dG + (size_t)t * H4;
+            g[tid] = di; g[H + tid] = df; g[2 * H + tid] = dg; g[3 * H + tid] = dO;
+        }
+        __syncthreads();
+        if (s > 0 && colt) {
+            float acc = 0.f;
+#pragma unroll
+            for (int k = 0; k < DEC_MAXH / 4; ++k) {
+                if (4 * k >= H) break;
+                const df4 g4 = *reinterpret_cast<const df4 *>(&dgs[q][4 * k]);
+                acc = __builtin_fmaf(wt[4 * k], g4.x, acc);
+                acc = __builtin_fmaf(wt[4 * k + 1], g4.y, acc);
+                acc = __builtin_fmaf(wt[4 * k + 2], g4.z, acc);
+                acc = __builtin_fmaf(wt[4 * k + 3], g4.w, acc);
+            }
+            part[q][j] = acc;
+        }
+        __syncthreads();
+    }
+#undef DEC_LOAD_STEP
+}
+
+// ---- what layer 1 sends down ------------------------------------------------------------------------------------------------------
+// dmid[t][k] = mask[t][k] (sum_r W_ih_l1[r][k] dG1[fwd][t][r] + sum_r W_ih_l1_reverse[r][k] dG1[bwd][t][r]), k < 2H: each sum over
+// the 4H gate rows in row order, the forward direction's first.  A workgroup takes DTM_FR frames; thread k owns column k, so a wave's
+// load of a weight row is consecutive bytes; the gate gradients of the frames sit side by side in LDS (broadcast reads).
+#define DTM_FR 8
+__global__ void __launch_bounds__(256)
+dec_train_dmid_kernel(DssDecTrainDev d, int T, const float *__restrict__ mask)
+{
+    __shared__ __attribute__((aligned(16))) float dgl[2][4 * DEC_MAXH][DTM_FR];
+    const int tid = threadIdx.x, H = d.H, H4 = 4 * H, K = 2 * H;
+    const DssDecTrainOff o = dec_train_off(d.C, H, d.O);
+    const int t0 = blockIdx.x * DTM_FR, nst = min(DTM_FR, T - t0);
+    for (int idx = tid; idx < 2 * DTM_FR * H4; idx += 256) {
+        const int dd = idx / (DTM_FR * H4), rem = idx - dd * (DTM_FR * H4);
+        const int tt = rem / H4, r = rem - tt * H4;
+        dgl[dd][r][tt] = tt < nst ? d.dg[1][dd][(size_t)(t0 + tt) * H4 + r] : 0.f;
+    }
+    __syncthreads();
+    if (tid >= K) return;
+    float acc[2][DTM_FR];
+#pragma unroll
+    for (int dd = 0; dd < 2; ++dd) {
+#pragma unroll
+        for (int tt = 0; tt < DTM_FR; ++tt) acc[dd][tt] = 0.f;
+        const float *W = d.p + o.wih[1][dd] + tid;
+        int r = 0;
+        for (; r + 4 <= H4; r += 4) {
+            float w[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) w[u] = W[(size_t)(r + u) * K];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const df4 g0 = *reinterpret_cast<const df4 *>(&dgl[dd][r + u][0]), g1 = *reinterpret_cast<const df4 *>(&dgl[dd][r + u][4]);
+                acc[dd][0] = __builtin_fmaf(w[u], g0.x, acc[dd][0]); acc[dd][1] = __builtin_fmaf(w[u], g0.y, acc[dd][1]);
+                acc[dd][2] = __builtin_fmaf(w[u], g0.z, acc[dd][2]); acc[dd][3] = __builtin_fmaf(w[u], g0.w, acc[dd][3]);
+                acc[dd][4] = __builtin_fmaf(w[u], g1.x, acc[dd][4]); acc[dd][5] = __builtin_fmaf(w[u], g1.y, acc[dd][5]);
+                acc[dd][6] = __builtin_fmaf(w[u], g1.z, acc[dd][6]); acc[dd][7] = __builtin_fmaf(w[u], g1.w, acc[dd][7]);
+            }
+        }                                                  // (4H is a multiple of 4: no remainder)
+    }
+#pragma unroll
+    for (int tt = 0; tt < DTM_FR; ++tt) {
+        if (tt >= nst) break;
+        const size_t oi = (size_t)(t0 + tt) * K + tid;
+        float s = acc[0][tt] + acc[1][tt];
+        if (mask) s *= mask[oi];
+        d.dmid[oi] = s;
+    }
+}
+
+// ---- the parallel part: weight gradients and the RMSprop update --------------------------------------------------------------
+// Workgroup b < 16H is gate row r of (layer L, direction dir), b = (2 L + dir) 4H + r: its columns are [W_ih row | W_hh row | bias],
+// column k's gradient is the sum over the frames t = 0 .. T-1, in that order, of dG[t][r] in[t][k] (one fused multiply-add per
+// frame; the bias adds dG[t][r] itself).  Workgroups 16H .. 16H + O - 1 are the rows of the regressor: [weight row | bias]
+// against dfeat.  The inputs: layer 0 reads the frames (xs), layer 1 the masked output of layer 0 (midm), the head layer 1's output
+// (top); the W_hh columns read the direction's own h of the step before -- frame t is step t forward, step T - 1 - t backward, and
+// row s of the stash is h before step s (row 0: zeros).
+// The update is evaluated per element in float64 from the stored float32 values and rounded once (vad_train.hip's vad_rmsprop).
+// bias_ih and bias_hh get the same g and each its own square average; the packed bias is their float32 sum.
+// Two columns per thread: a row has at most max(C, 2H) + H + 1 <= 256 + 128 + 1 = 385 <= 2 x 256 columns.
+#define DTS_THREADS 256
+
+__device__ __forceinline__ float dec_rmsprop(const DssDecTrainDev &d, int k, float g, int apply, double lr, double alpha, double eps)
+{
+    d.g[k] = g;
+    if (!apply) return d.p[k];
+    const float sq = (float)(alpha * (double)d.sq[k] + (1.0 - alpha) * ((double)g * (double)g));
+    d.sq[k] = sq;
+    const float p = (float)((double)d.p[k] - lr * (double)g / (sqrt((double)sq) + eps));
+    d.p[k] = p;
+    return p;
+}
+
+__global__ void __launch_bounds__(DTS_THREADS)
+dec_train_step_kernel(DssDecTrainDev d, int T, int apply, double lr, double alpha, double eps)
+{
+    __shared__ float dgt[DTS_THREADS];
+    const int tid = threadIdx.x, b = blockIdx.x, C = d.C, H = d.H, H4 = 4 * H, O = d.O;
+    const bool head = b >= 4 * H4;
+    const int LD = head ? 0 : b / H4, L = LD >> 1, dir = LD & 1, r = head ? b - 4 * H4 : b - LD * H4;
+    const float *dg = head ? d.dfeat + r : d.dg[L][dir] + r;
+    const int dgs = head ? O : H4;
+    const float *inA = head ? d.top : (L ? d.midm : d.xs), *inB = d.h[L][dir];
+    const int nA = head || L ? 2 * H : C, nB = head ? 0 : H, ncol = nA + nB + 1;
+    const int Cp = (nA + 3) & ~3;
+    // the flat offsets of this (layer, direction)'s four tensors, and of the head (dec_train_off, without an indexed table)
+    const int sz0 = H4 * (C + H + 2), sz1 = H4 * (3 * H + 2);
+    const int o_wih = LD < 2 ? LD * sz0 : 2 * sz0 + (LD - 2) * sz1, o_whh = o_wih + H4 * nA, o_bih = o_whh + H4 * H, o_bhh = o_bih + H4;
+    const int o_wr = 2 * sz0 + 2 * sz1, o_br = o_wr + O * 2 * H;
+    const float *src[2];
+    long stride[2];
+    int col[2];
+    bool live[2], bias[2];
+    float acc[2] = {0.f, 0.f};
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        col[u] = tid + u * DTS_THREADS;
+        live[u] = col[u] < ncol;
+        bias[u] = col[u] == ncol - 1;
+        const bool a = col[u] < nA;
+        if (!live[u] || bias[u]) { src[u] = inA; stride[u] = 0; }
+        else if (a) { src[u] = inA + col[u]; stride[u] = nA; }
+        else { src[u] = inB + (col[u] - nA) + (dir ? (size_t)(T - 1) * H : 0); stride[u] = dir ? -(long)H : (long)H; }
+    }
+    for (int t0 = 0; t0 < T; t0 += DTS_THREADS) {
+        const int n = min(DTS_THREADS, T - t0);
+        if (tid < n) dgt[tid] = dg[(size_t)(t0 + tid) * dgs];
+        __syncthreads();
+        for (int tt = 0; tt < n; ++tt) {
+            const float g = dgt[tt];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const float x = bias[u] ? 1.f : src[u][(long)(t0 + tt) * stride[u]];
+                acc[u] = __builtin_fmaf(g, x, acc[u]);
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        if (!live[u]) continue;
+        const int k = col[u];
+        if (head) {
+            dec_rmsprop(d, bias[u] ? o_br + r : o_wr + r * nA + k, acc[u], apply, lr, alpha, eps);
+        } else if (bias[u]) {
+            const float bi = dec_rmsprop(d, o_bih + r, acc[u], apply, lr, alpha, eps);
+            const float bh = dec_rmsprop(d, o_bhh + r, acc[u], apply, lr, alpha, eps);
+            if (apply) d.b[L][dir][r] = bi + bh;
+        } else {
+            const bool a = k < nA;
+            const int pk = a ? o_wih + r * nA + k : o_whh + r * H + (k - nA);
+            const float p = dec_rmsprop(d, pk, acc[u], apply, lr, alpha, eps);
+            // the packed copy: [inputs / 4][4H rows][4 consecutive inputs], W_hh behind W_ih's padded inputs
+            const int ki = a ? k : Cp + (k - nA);
+            if (apply) d.wT[L][dir][((size_t)(ki >> 2) * H4 + r) * 4 + (ki & 3)] = p;
+        }
+    }
+}
+
+int dss_launch_dec_train_trial(const DssDecTrainDev &d, const void *d_frames, int frames_f64, int T, const float *d_targets,
+                               const float *d_mask, int apply_step, double lr, double alpha, double eps, double *d_loss, hipStream_t st)
+{
+    const int H = d.H, C = d.C, O = d.O;
+    if (H < 1 || H > DEC_MAXH || 4 * H > DEC_THREADS || C < 1 || C > DEC_MAXC || 2 * H > DEC_MAXC || O < 1 || O > DSS_DEC_MAXO ||
+        d.Tmax > DSS_DEC_TRAIN_MAXT || T < 1 || T > d.Tmax) {
+        dss_set_error("decoder training kernels: %d hidden units / %d inputs / %d outputs / %d frames out of range (<= %d / <= %d / <= %d / <= %d)",
+                      H, C, O, T, DEC_MAXH, DEC_MAXC, DSS_DEC_MAXO, d.Tmax);
+        return DSS_EINVAL;
+    }
+    const dim3 two(2), block(DEC_THREADS);
+    if (frames_f64) hipLaunchKernelGGL((dec_train_layer_kernel<double, 0>), two, block, 0, st, d, (const double *)d_frames, T, d_mask);
+    else hipLaunchKernelGGL((dec_train_layer_kernel<float, 0>), two, block, 0, st, d, (const float *)d_frames, T, d_mask);
+    hipLaunchKernelGGL((dec_train_layer_kernel<float, 1>), two, block, 0, st, d, (const float *)d.midm, T, (const float *)nullptr);
+    DSS_HIP_CHECK(hipGetLastError());
+    const size_t hlds = ((size_t)O * (2 * H + 1) + (size_t)DTH_ROWS * 2 * H + (size_t)DTH_ROWS * O) * sizeof(float);
+    hipLaunchKernelGGL(dec_train_head_kernel, dim3((T + DTH_ROWS - 1) / DTH_ROWS), dim3(256), hlds, st, d, T, d_targets);
+    hipLaunchKernelGGL((dec_train_bptt_kernel<1>), dim3(3), block, 0, st, d, T, d_loss);
+    DSS_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(dec_train_dmid_kernel, dim3((T + DTM_FR - 1) / DTM_FR), dim3(256), 0, st, d, T, d_mask);
+    hipLaunchKernelGGL((dec_train_bptt_kernel<0>), two, block, 0, st, d, T, (double *)nullptr);
+    DSS_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(dec_train_step_kernel, dim3(16 * H + O), dim3(DTS_THREADS), 0, st, d, T, apply_step, lr, alpha, eps);
+    DSS_HIP_CHECK(hipGetLastError());
+    return DSS_OK;
+}

@@ -2344,6 +2344,14 @@ struct dss_dec {
     size_t tmeta_cap = 0, tout_cap = 0;
 };
 
+int dss_dec_device_weights(dss_dec *v, int *device, int *n_inputs, int *hidden_units, int *n_outputs, float *w[10])
+{
+    if (!v || !v->loaded) { dss_set_error("the decoder handle is NULL or has no weights loaded (dss_dec_load_weights)"); return DSS_EINVAL; }
+    *device = v->device; *n_inputs = v->d.C; *hidden_units = v->d.H; *n_outputs = v->d.O;
+    for (int k = 0; k < 10; ++k) w[k] = v->w[k];
+    return DSS_OK;
+}
+
 extern "C" dss_dec *dss_dec_create(int max_streams, int max_frames, int n_inputs, int hidden_units, int n_outputs)
 {
     if (max_streams <= 0 || max_frames <= 0 || n_inputs <= 0 || hidden_units <= 0 || n_outputs <= 0) {

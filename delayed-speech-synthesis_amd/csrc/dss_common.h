@@ -247,6 +247,32 @@ int dss_launch_decoder_trials(const DssDecDev &d, const void *d_frames, int fram
 int dss_launch_dec_mse_trials(const DssTrialLens &tl, const float *d_feats, const float *d_targets, int n_outputs, double *d_mse,
                               hipStream_t s);
 
+// ---- training of the decoder (dec_train.hip; Part 10) ---------------------------------------------------------
+#define DSS_DEC_TRAIN_MAXT 4096   // largest max_frames of a trainer (the workspace takes about 34 H + C + 3 O floats per frame)
+struct DssDecTrainDev {
+    int C, H, O, Tmax;            // inputs per frame, hidden units per direction, outputs, max_frames: the rows of the workspace
+    float *p, *g, *sq;            // master parameters (torch layout), gradients of the last trial, RMSprop square averages: flat, the
+                                  //   eighteen tensors in state_dict order (dss_dec_trainer_read)
+    float *wT[2][2], *b[2][2];    // [layer][direction]: the packed copies of DssDecDev, writable: the step kernel refreshes them
+    // workspace of one trial.  A direction's stash is in ITS OWN time order: step s is frame s forward, frame T - 1 - s backward.
+    // The forward pass leaves: the frames as float32; per (layer, direction) the gate activations i, f, g, o of every step and
+    // c and h with one row in front (row 0 = zeros, row s + 1 = after step s); layer 0's masked output, layer 1's output
+    float *xs;                    // [Tmax][C]
+    float *act[2][2];             // [Tmax][4H]
+    float *c[2][2], *h[2][2];     // [Tmax + 1][H]
+    float *midm, *top;            // [Tmax][2H], by frame: forward | backward
+    float *feat, *dfeat;          // [Tmax][O]: features; 2 (feat - target) / (T O)
+    double *lossf;                // [Tmax]: per-frame sum of squared differences
+    // ... and the backward pass, by frame: what the head sends to layer 1's h, the gate gradients, what layer 1 sends to layer 0's h
+    float *dtop, *dmid;           // [Tmax][2H]
+    float *dg[2][2];              // [Tmax][4H]
+};
+struct DssDecTrainOff { int wih[2][2], whh[2][2], bih[2][2], bhh[2][2], wr, br, total; };
+long dss_dec_train_param_count(int C, int H, int O);
+// one trial: loss, features (d.feat), gradients (d.g); parameters, square averages and packed copies updated if apply_step
+int dss_launch_dec_train_trial(const DssDecTrainDev &d, const void *d_frames, int frames_f64, int T, const float *d_targets,
+                               const float *d_mask, int apply_step, double lr, double alpha, double eps, double *d_loss, hipStream_t s);
+
 struct DssHgaDev {
     int S, C, fs, nsec;
     float wl, ws;

@@ -15,6 +15,11 @@ int dss_fine_host_view(void *p, size_t bytes, size_t align, const char *what, vo
 struct dss_vad;
 int dss_vad_device_weights(dss_vad *v, int *device, int *n_inputs, int *hidden_units, float *w[6]);
 
+// The same for an inference decoder (Part 6), for dss_dec_trainer_publish: the ten arrays wT[layer][direction] (four), b[layer][direction]
+// (four), wr, br.
+struct dss_dec;
+int dss_dec_device_weights(dss_dec *v, int *device, int *n_inputs, int *hidden_units, int *n_outputs, float *w[10]);
+
 // Small host -> device uploads that must not stall, and must not be overwritten, while earlier calls are still queued.
 //
 // hipMemcpyAsync from pageable memory may wait for the stream's earlier work (the runtime stages it), which would hold the

@@ -145,6 +145,15 @@ def _declare(L):
         "dss_vad_trainer_window_dev": (i, [vp, vp, i, i, vp, vp, i, C.c_double, C.c_double, C.c_double, vp, vp]),
         "dss_vad_trainer_trial_dev": (i, [vp, vp, i, i, vp, vp, i, C.c_double, C.c_double, C.c_double, vp, vp]),
         "dss_vad_trainer_publish": (i, [vp, vp, vp]),
+        "dss_dec_trainer_check": (i, [i, i, i, i, i]),
+        "dss_dec_trainer_param_count": (C.c_long, [i, i, i]),
+        "dss_dec_trainer_create": (vp, [i, i, i, i]),
+        "dss_dec_trainer_destroy": (None, [vp]),
+        "dss_dec_trainer_load": (i, [vp, vp]),
+        "dss_dec_trainer_read": (i, [vp, i, vp]),
+        "dss_dec_trainer_features": (i, [vp, i, vp]),
+        "dss_dec_trainer_trial_dev": (i, [vp, vp, i, i, vp, vp, i, C.c_double, C.c_double, C.c_double, vp, vp]),
+        "dss_dec_trainer_publish": (i, [vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -15,8 +15,7 @@ trials in one launch / one call) and the scores come from one reduction launch (
 already holds the weights: given a module or a state_dict every call creates a handle, uploads the weights and, for the
 decoder, allocates the two layer buffers (max_streams x longest trial x 2H floats each); a caller that validates every epoch
 keeps one handle and passes it in.  A module that is not the reference's architecture raises: there is no fallback to the module's
-own forward.  The detector's training is ``dss_amd.training``; the decoder's training (train_bidirectional_model.py) is not part
-of this package."""
+own forward.  The training of both models is ``dss_amd.training``."""
 from __future__ import annotations
 
 import ctypes as C

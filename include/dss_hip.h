@@ -492,7 +492,7 @@ int dss_avad_vote_host(const double *log_energy, int W, const dss_avad_params *p
  * Here a whole trial list is one call.  Trial k is rows first[k] .. first[k] + len[k] of d_frames, (N, n_inputs) float64
  * (frames_are_f64 != 0) or float32; ranges may overlap and come in any order; first / len are HOST arrays.  Outputs are
  * concatenated in list order: row sum(len[:k]) + t is frame t of trial k (the convention of dss_hga_extract_trials).  Every
- * trial starts from the zero state (create_new_initial_state).  The detector's training is Part 9; the decoder's is not here.
+ * trial starts from the zero state (create_new_initial_state).  The detector's training is Part 9, the decoder's Part 10.
  * On one handle, trial-list calls are issued on one stream, or one after the other has finished: the handle keeps the
  * call's trial table.
  * ---------------------------------------------------------------------------------------------- */
@@ -581,6 +581,53 @@ int dss_vad_trainer_trial_dev(dss_vad_trainer *tr, const void *d_frames, int fra
  * into an inference handle of the same n_inputs and hidden_units that has weights loaded; enqueued on hip_stream.  After it Part 5
  * and Part 8 run on the trained weights with no host round trip.  The handle's recurrent state is not touched. */
 int dss_vad_trainer_publish(dss_vad_trainer *tr, dss_vad *v, void *hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Part 10 -- training the decoder of Part 6: the loop of train_bidirectional_model.py:134-152 (batch size 1, one trial is one
+ * update step, torch.optim.RMSprop) as seven launches per trial on one stream (csrc/dec_train.hip).  A trial is T frames
+ * (1 <= T <= max_frames) with float32 targets (T, n_outputs): forward from the zero state through both layers and directions,
+ * nn.MSELoss (the mean over the T x n_outputs elements), the gradient of that loss with respect to all eighteen parameter tensors,
+ * backpropagated through the whole trial in both directions, then RMSprop per element as in Part 9; bias_ih and bias_hh have
+ * equal gradients and each its own square average.  Dropout (nn.LSTM(dropout = p) in train mode) multiplies layer 0's
+ * concatenated output [h_forward(t) | h_backward(t)], as layer 1 reads it, by a mask of 0 or 1 / (1 - p) -- not layer 1's
+ * output, not the h a direction carries to its own next step; the mask is an INPUT, float32 (T, 2H) multipliers or NULL for
+ * none, and the backward pass uses the same one.  The kernels hold no generator.  Every reduction has a fixed order: the same
+ * call from the same state gives the same bits.  Fused multiply-adds are used.  Without a mask the forward half computes the
+ * features of dss_dec_forward_dev on one stream, bit for bit.
+ *
+ * Flat arrays (dss_dec_trainer_read) hold the eighteen tensors in state_dict order, each in torch's layout:
+ *     for layer in (0, 1), for direction in (forward, reverse): weight_ih [4H][Cin], weight_hh [4H][H], bias_ih [4H], bias_hh [4H]
+ *     (Cin = n_inputs for layer 0, 2H for layer 1), then regressor.weight [O][2H], regressor.bias [O]
+ *                                                        -- dss_dec_trainer_param_count(C, H, O) floats in all.
+ * Calls on one trainer are issued on one stream, or one after the other has finished.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct dss_dec_trainer dss_dec_trainer;
+/* The argument checks of this part on their own (no device needed): DSS_EINVAL with the reason in dss_last_error() for sizes that
+ * are not positive or beyond the kernels' capacities (hidden_units <= 128, n_inputs <= 256, n_outputs <= 32, max_frames <= 4096)
+ * or a trial of T < 1 or T > max_frames frames; else 0. */
+int dss_dec_trainer_check(int n_inputs, int hidden_units, int n_outputs, int max_frames, int T);
+long dss_dec_trainer_param_count(int n_inputs, int hidden_units, int n_outputs);
+/* The workspace of a trial takes about (34 H + C + 3 O) x max_frames floats of device memory (13 MB at H 100, 1500 frames). */
+dss_dec_trainer *dss_dec_trainer_create(int n_inputs, int hidden_units, int n_outputs, int max_frames);
+void dss_dec_trainer_destroy(dss_dec_trainer *tr);
+/* The eighteen host arrays of dss_dec_load_weights.  Zeroes the square averages and the gradients. */
+int dss_dec_trainer_load(dss_dec_trainer *tr, const float *const *w);
+/* One flat host array (see above): what = 0 the parameters, 1 the gradients of the last trial, 2 the square averages.  Waits
+ * for the device. */
+int dss_dec_trainer_read(dss_dec_trainer *tr, int what, float *out);
+/* The features (T, n_outputs) the forward half of the last trial of T frames computed, to a host array.  Waits for the device. */
+int dss_dec_trainer_features(dss_dec_trainer *tr, int T, float *out);
+/* One trial, enqueued on hip_stream with no host synchronisation between its launches.  Device pointers: d_frames (T, n_inputs)
+ * float64 (frames_are_f64 != 0; cast to float32 like the script's .float()) or float32; d_targets float32 (T, n_outputs); d_mask
+ * float32 (T, 2H) or NULL; *d_loss receives the trial's loss (float64, from the float32 features).  Always computes the loss and
+ * the gradients; parameters, square averages and the packed copies the forward pass reads change only if apply_step != 0. */
+int dss_dec_trainer_trial_dev(dss_dec_trainer *tr, const void *d_frames, int frames_are_f64, int T, const float *d_targets,
+                              const float *d_mask, int apply_step, double lr, double alpha, double eps, double *d_loss,
+                              void *hip_stream);
+/* Copies the current weights, in the packed form the forward kernels read (b = bias_ih + bias_hh in float32), device to device
+ * into an inference handle of the same n_inputs, hidden_units and n_outputs that has weights loaded; enqueued on hip_stream.
+ * After it Part 6 and Part 8 run on the trained weights with no host round trip. */
+int dss_dec_trainer_publish(dss_dec_trainer *tr, dss_dec *v, void *hip_stream);
 
 #ifdef __cplusplus
 }
