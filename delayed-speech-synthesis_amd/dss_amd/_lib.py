@@ -154,6 +154,18 @@ def _declare(L):
         "dss_dec_trainer_features": (i, [vp, i, vp]),
         "dss_dec_trainer_trial_dev": (i, [vp, vp, i, i, vp, vp, i, C.c_double, C.c_double, C.c_double, vp, vp]),
         "dss_dec_trainer_publish": (i, [vp, vp, vp]),
+        "dss_spec_check_params": (i, [vp]),
+        "dss_spec_trial_frames_for": (C.c_longlong, [C.c_longlong, i, i]),
+        "dss_spec_check_trials": (C.c_longlong, [C.c_longlong, i, vp, vp, i, i]),
+        "dss_spec_check_locked": (i, [i, vp, vp, i, i, i, i]),
+        "dss_spec_create": (vp, [vp, vp]),
+        "dss_spec_destroy": (None, [vp]),
+        "dss_spec_trials": (C.c_longlong, [vp, vp, C.c_longlong, i, i, i, vp, vp, vp]),
+        "dss_spec_trials_dev": (C.c_longlong, [vp, vp, C.c_longlong, i, i, i, vp, vp, vp, vp]),
+        "dss_spec_locked": (i, [vp, vp, C.c_longlong, i, i, i, vp, vp, vp, i, i, vp]),
+        "dss_spec_locked_dev": (i, [vp, vp, C.c_longlong, i, i, i, vp, vp, vp, i, i, vp, vp]),
+        "dss_spec_mean": (i, [vp, vp, C.c_longlong, i, i, i, vp, vp, vp]),
+        "dss_spec_mean_dev": (i, [vp, vp, C.c_longlong, i, i, i, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

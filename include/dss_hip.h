@@ -16,7 +16,8 @@
  * local/units.py:97-161).
  * Parts 4-6 are the speech gate and the two recurrent models of the online path, Part 7 the acoustic labels of a
  * training corpus, Part 8 the two recurrent models over the trials of such a corpus (the validation passes of the
- * reference's training scripts), Part 9 the training of the neural detector, each described at its declarations.
+ * reference's training scripts), Part 9 the training of the neural detector, Part 10 that of the decoder, Part 11 the
+ * spectrograms behind the reference's spectral analyses, each described at its declarations.
  *
  * Error convention: functions returning int return 0 on success and a negative DSS_E* code on failure;
  * dss_last_error() gives a thread-local message.  Creators return NULL on failure (the reference's
@@ -628,6 +629,68 @@ int dss_dec_trainer_trial_dev(dss_dec_trainer *tr, const void *d_frames, int fra
  * into an inference handle of the same n_inputs, hidden_units and n_outputs that has weights loaded; enqueued on hip_stream.
  * After it Part 6 and Part 8 run on the trained weights with no host round trip. */
 int dss_dec_trainer_publish(dss_dec_trainer *tr, dss_dec *v, void *hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Part 11 -- spectrograms over the trials of a recording, and the two reductions the reference's per-electrode spectral analysis
+ * takes of them (eval/suppl_fig_2.py:41-92; eval/figure_2ab.py:30-31 needs the same operator on audio).  The reference calls
+ * scipy.signal.spectrogram once per trial and channel; here a trial list and all channels are one call (csrc/spectral.hip).
+ * The signals are a row-major (n_rows, ld) float64 array of which the first C <= ld columns are channels (the layout of
+ * dss_hga_extract_trials: a 129-column recording needs no copy).  Trial i is rows first[i] .. first[i] + length[i]; trials may
+ * overlap and differ in length; first / length are HOST arrays in every form.  Frame w of a trial is its rows w * hop ..
+ * w * hop + nperseg - 1, W = (length - nperseg) / hop + 1 frames, no padding and no boundary extension.  Per frame and channel:
+ * the frame's mean is removed (detrend = 1; scipy's detrend='constant'), the frame is multiplied by the window (data of the
+ * caller) and transformed at bins 0 .. nfft / 2, zero-padded to nfft >= nperseg.  DSS_SPEC_PSD gives (re^2 + im^2) /
+ * (fs * sum window^2), doubled except at bin 0 and, for even nfft, the last bin; DSS_SPEC_MAGNITUDE gives sqrt(re^2 + im^2) /
+ * sqrt(fs * sum window^2), scipy's mode='magnitude' with its default scaling='density'.  scipy's arithmetic is pocketfft: results
+ * agree with it within 2 (nperseg + 8) sqrt(nperseg) 2^-53 of the frame's largest bin (PSD; half that for the magnitude), not bit
+ * for bit; fused multiply-adds are used; the same frame gives the same bits alone or inside any list, in all three operations.
+ * Limits: nperseg >= 2, hop >= 1, nperseg <= nfft <= 2048, C >= 1.
+ * ---------------------------------------------------------------------------------------------- */
+#define DSS_SPEC_PSD 0
+#define DSS_SPEC_MAGNITUDE 1
+typedef struct dss_spec_params {
+    int nperseg, hop, nfft;            /* rows per frame, rows between frames (nperseg - noverlap), transform length */
+    int mode, detrend, reserved;       /* DSS_SPEC_PSD or DSS_SPEC_MAGNITUDE; 1 removes every frame's mean, 0 does not */
+    double fs;                         /* sampling rate */
+} dss_spec_params;
+typedef struct dss_spec dss_spec;
+/* The checks of dss_spec_create on their own (no device needed). */
+int dss_spec_check_params(const dss_spec_params *p);
+/* Frames of a trial of n rows, or DSS_EINVAL when n < nperseg, nperseg < 2 or hop < 1 (no device needed). */
+long long dss_spec_trial_frames_for(long long n, int nperseg, int hop);
+/* The argument checks of the trial-list entry points on their own (no device needed): frames of the whole list, or DSS_EINVAL
+ * with the reason in dss_last_error() -- NULL arrays, a negative count, first < 0, length < 0, a range that ends behind the
+ * signals, length < nperseg. */
+long long dss_spec_check_trials(long long n_rows, int n_trials, const long long *first, const long long *length, int nperseg, int hop);
+/* The checks of the onset-locked mean on their own (no device needed): pre + post, or DSS_EINVAL naming the trial whose onset
+ * frame has fewer than `pre` frames before it (onset - pre < 0) or fewer than `post` frames from it on (onset + post > W).  The
+ * reference slices Sxx[:, onset - pre : onset + post] there and silently gets a wrong or short slice. */
+int dss_spec_check_locked(int n_trials, const long long *length, const int *onset, int pre, int post, int nperseg, int hop);
+/* window: nperseg doubles (scipy.signal.get_window('hann', nperseg) in the reference; dss_amd.spectral.hann_periodic).  NULL on
+ * failure. */
+dss_spec *dss_spec_create(const dss_spec_params *p, const double *window);
+void dss_spec_destroy(dss_spec *h);
+/* Spectrograms: out is (sum W_i, C, nfft / 2 + 1) float64, frame after frame, trial after trial in list order.  Returns the
+ * number of frames.  Host buffers; only the rows the trials span are copied to the device. */
+long long dss_spec_trials(dss_spec *h, const double *x, long long n_rows, int ld, int C, int n_trials, const long long *first,
+                          const long long *length, double *out);
+/* Device-resident: d_x and d_out are device pointers.  Returns once the launch is queued on hip_stream; one call per handle may
+ * be in flight. */
+long long dss_spec_trials_dev(dss_spec *h, const double *d_x, long long n_rows, int ld, int C, int n_trials, const long long *first,
+                              const long long *length, double *d_out, void *hip_stream);
+/* The mean over the trials of the frames around each trial's own onset frame, without storing any spectrogram: out is
+ * (C, nfft / 2 + 1, pre + post) float64, column j the mean over i of frame onset[i] - pre + j of trial i -- the trials' values
+ * added in list order, then divided by n_trials.  onset is a HOST array.  Returns pre + post. */
+int dss_spec_locked(dss_spec *h, const double *x, long long n_rows, int ld, int C, int n_trials, const long long *first,
+                    const long long *length, const int *onset, int pre, int post, double *out);
+int dss_spec_locked_dev(dss_spec *h, const double *d_x, long long n_rows, int ld, int C, int n_trials, const long long *first,
+                        const long long *length, const int *onset, int pre, int post, double *d_out, void *hip_stream);
+/* The mean spectrum over ALL frames of all trials: out is (C, nfft / 2 + 1) float64 -- every trial's frames added in frame order,
+ * the trials' sums added in list order, divided by the number of frames (two launches).  Returns 0. */
+int dss_spec_mean(dss_spec *h, const double *x, long long n_rows, int ld, int C, int n_trials, const long long *first,
+                  const long long *length, double *out);
+int dss_spec_mean_dev(dss_spec *h, const double *d_x, long long n_rows, int ld, int C, int n_trials, const long long *first,
+                      const long long *length, double *d_out, void *hip_stream);
 
 #ifdef __cplusplus
 }
