@@ -120,6 +120,31 @@ extern "C" void dss_spec_destroy(dss_spec *h)
     delete h;
 }
 
+// The part of the device view that the parameters alone decide: what dss_spec_pick_geom reads.
+static void spec_shape(const dss_spec_params &p, DssSpecDev *d)
+{
+    d->nperseg = p.nperseg; d->hop = p.hop; d->nfft = p.nfft; d->bins = p.nfft / 2 + 1; d->nblk = (d->bins + 15) / 16;
+    d->K4 = (p.nperseg + 3) & ~3; d->sh = std::min(p.hop, d->K4);
+    d->mode = p.mode; d->detrend = p.detrend; d->odd = p.nfft & 1;
+}
+
+extern "C" int dss_spec_geometry(const dss_spec_params *p, int n_channels, int kind, int out[5])
+{
+    if (dss_spec_check_params(p)) return DSS_EINVAL;
+    if (n_channels < 1) { dss_set_error("spectrogram: %d channels", n_channels); return DSS_EINVAL; }
+    if (kind != SPEC_KIND_TRIALS && kind != SPEC_KIND_LOCKED && kind != SPEC_KIND_MEAN) {
+        dss_set_error("spectrogram: unknown kernel kind %d (0 trials, 1 onset-locked mean, 2 mean spectrum)", kind);
+        return DSS_EINVAL;
+    }
+    if (!out) { dss_set_error("bad arguments"); return DSS_EINVAL; }
+    DssSpecDev d = {};
+    spec_shape(*p, &d);
+    DssSpecGeom g;
+    if (!dss_spec_pick_geom(d, n_channels, kind, &g)) { dss_set_error("spectrogram: the frame shape does not fit the kernel"); return DSS_EINVAL; }
+    out[0] = g.F; out[1] = g.CG; out[2] = g.NB; out[3] = d.nblk; out[4] = (int)g.lds_bytes;
+    return DSS_OK;
+}
+
 static int spec_setup(dss_spec *h, const double *window)
 {
     const dss_spec_params &p = h->p;
@@ -142,9 +167,7 @@ static int spec_setup(dss_spec *h, const double *window)
     DSS_HIP_CHECK(hipMemcpy(h->d_win, win.data(), win.size() * sizeof(double), hipMemcpyHostToDevice));
     DSS_HIP_CHECK(hipMemcpy(h->d_tw, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice));
     DssSpecDev &d = h->d;
-    d.nperseg = p.nperseg; d.hop = p.hop; d.nfft = p.nfft; d.bins = p.nfft / 2 + 1; d.nblk = (d.bins + 15) / 16;
-    d.K4 = K4; d.sh = std::min(p.hop, K4);
-    d.mode = p.mode; d.detrend = p.detrend; d.odd = p.nfft & 1;
+    spec_shape(p, &d);
     const double scale = 1.0 / (p.fs * sq);          // scipy: scale = 1.0 / (fs * (win * win).sum())
     d.scale = p.mode == DSS_SPEC_MAGNITUDE ? sqrt(scale) : scale;
     d.win = h->d_win; d.tw = h->d_tw;

@@ -5,8 +5,7 @@
 #include "dss_common.h"
 
 #define SPEC_THREADS 256
-#define SPEC_LDS_SOFT 81920       // preferred bytes of LDS per workgroup: two workgroups share a CU
-#define SPEC_LDS_LIMIT 163840     // bytes of LDS one workgroup may take on gfx950
+#define SPEC_LDS_SOFT 81920       // bytes of LDS per workgroup, half of gfx950's 160 KB: two workgroups share a CU
 #define SPEC_KIND_TRIALS 0
 #define SPEC_KIND_LOCKED 1
 #define SPEC_KIND_MEAN 2

@@ -302,21 +302,21 @@ bool dss_spec_pick_geom(const DssSpecDev &v, int C, int kind, DssSpecGeom *g)
 {
     int cg_max = 1;
     while (cg_max < 16 && cg_max < C) cg_max <<= 1;
-    // the first that fits, most frames first (the MFMA's 16 rows filled), then most bin blocks (the rows staged once), then channels
-    for (size_t limit : {(size_t)SPEC_LDS_SOFT, (size_t)SPEC_LDS_LIMIT}) {
-        for (int F = 32; F >= 1; F >>= 1) {
-            for (int NB = v.nblk;; NB = (NB + 1) / 2) {
-                for (int CG = cg_max; CG >= 1; CG >>= 1) {
-                    const size_t bytes = spec_lds_bytes(v, kind, F, CG, NB);
-                    if (bytes > limit) continue;
-                    g->F = F; g->CG = CG; g->NB = NB;
-                    g->f_shift = __builtin_ctz((unsigned)F); g->cg_shift = __builtin_ctz((unsigned)CG);
-                    g->rows = (F - 1) * v.sh + v.K4; g->RS = g->rows | 1;
-                    g->lds_bytes = (unsigned)bytes;
-                    return true;
-                }
-                if (NB == 1 || kind == SPEC_KIND_TRIALS) break;
+    // the first that fits, most frames first (the MFMA's 16 rows filled), then most bin blocks (the rows staged once), then channels.
+    // Inside the limits of dss_spec_check_params the last candidate always fits: F = CG = 1 with NB = 1 (all nblk blocks for the
+    // spectrograms, which keep nothing per block) asks for at most 2 * 2048 + 2048 + 1 + 2049 + 512 doubles = 69648 bytes.
+    for (int F = 32; F >= 1; F >>= 1) {
+        for (int NB = v.nblk;; NB = (NB + 1) / 2) {
+            for (int CG = cg_max; CG >= 1; CG >>= 1) {
+                const size_t bytes = spec_lds_bytes(v, kind, F, CG, NB);
+                if (bytes > SPEC_LDS_SOFT) continue;
+                g->F = F; g->CG = CG; g->NB = NB;
+                g->f_shift = __builtin_ctz((unsigned)F); g->cg_shift = __builtin_ctz((unsigned)CG);
+                g->rows = (F - 1) * v.sh + v.K4; g->RS = g->rows | 1;
+                g->lds_bytes = (unsigned)bytes;
+                return true;
             }
+            if (NB == 1 || kind == SPEC_KIND_TRIALS) break;
         }
     }
     return false;

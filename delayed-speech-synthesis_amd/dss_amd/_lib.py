@@ -166,6 +166,7 @@ def _declare(L):
         "dss_spec_locked_dev": (i, [vp, vp, C.c_longlong, i, i, i, vp, vp, vp, i, i, vp, vp]),
         "dss_spec_mean": (i, [vp, vp, C.c_longlong, i, i, i, vp, vp, vp]),
         "dss_spec_mean_dev": (i, [vp, vp, C.c_longlong, i, i, i, vp, vp, vp, vp]),
+        "dss_spec_geometry": (i, [vp, i, i, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -14,6 +14,7 @@ The window is computed here, from its definition, and handed to the library as d
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 
@@ -70,6 +71,22 @@ def check_locked(ranges, onsets, pre: int, post: int, nperseg: int, hop: int) ->
         raise ValueError("onsets must hold one frame index per trial")
     return _lib.check(_lib.load().dss_spec_check_locked(len(length), length.ctypes.data, on.ctypes.data, int(pre), int(post),
                                                         int(nperseg), int(hop)))
+
+
+KINDS = {"trials": 0, "locked": 1, "mean": 2}
+Geometry = collections.namedtuple("Geometry", "F CG NB nblk lds_bytes")
+
+
+def geometry(nperseg: int, hop: int, nfft: int, n_channels: int, kind, mode: str = "psd", detrend="constant",
+             fs: float = 1000.0) -> Geometry:
+    """How ``SpectrogramGPU(fs, nperseg, nperseg - hop, nfft, ...)`` will cut the workgroups of ``trials`` (kind 'trials' or
+    0), ``locked`` ('locked', 1) or ``mean`` ('mean', 2) for ``n_channels`` channels: F frames x CG channels x NB blocks of 16
+    bins per workgroup, ``nblk`` blocks in all, bytes of LDS.  It is the library's own choice (``dss_spec_geometry``), not a
+    copy of it; DssError for parameters the library refuses (needs no GPU)."""
+    p = SpecParams(int(nperseg), int(hop), int(nfft), MODES[mode], 1 if detrend == "constant" else 0, 0, float(fs))
+    out = (C.c_int * 5)()
+    _lib.check(_lib.load().dss_spec_geometry(C.addressof(p), int(n_channels), int(KINDS.get(kind, kind)), C.addressof(out)))
+    return Geometry(*out)
 
 
 class SpectrogramGPU:

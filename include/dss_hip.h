@@ -666,6 +666,12 @@ long long dss_spec_check_trials(long long n_rows, int n_trials, const long long 
  * frame has fewer than `pre` frames before it (onset - pre < 0) or fewer than `post` frames from it on (onset + post > W).  The
  * reference slices Sxx[:, onset - pre : onset + post] there and silently gets a wrong or short slice. */
 int dss_spec_check_locked(int n_trials, const long long *length, const int *onset, int pre, int post, int nperseg, int hop);
+/* How a call with these parameters and n_channels channels will cut its workgroups (no device needed): the very choice the
+ * launches make, for tests that must know which shape a case runs.  kind: 0 spectrograms (dss_spec_trials), 1 onset-locked mean
+ * (dss_spec_locked), 2 mean spectrum (dss_spec_mean).  out = F frames, CG channels, NB blocks of 16 bins per workgroup, the
+ * number of 16-bin blocks of nfft / 2 + 1 bins, bytes of LDS per workgroup.  0, or DSS_EINVAL with the reason in
+ * dss_last_error(): what dss_spec_check_params refuses, n_channels < 1, an unknown kind. */
+int dss_spec_geometry(const dss_spec_params *p, int n_channels, int kind, int out[5]);
 /* window: nperseg doubles (scipy.signal.get_window('hann', nperseg) in the reference; dss_amd.spectral.hann_periodic).  NULL on
  * failure. */
 dss_spec *dss_spec_create(const dss_spec_params *p, const double *window);

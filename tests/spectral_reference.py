@@ -50,20 +50,20 @@ def trials(x, ranges, fs, window, nperseg, hop, nfft, mode="psd", detrend=True):
     return np.concatenate([spectrogram(x[a:a + n], fs, window, nperseg, hop, nfft, mode, detrend) for a, n in ranges])
 
 
-def locked(x, ranges, onsets, pre, post, fs, window, nperseg, hop, nfft):
+def locked(x, ranges, onsets, pre, post, fs, window, nperseg, hop, nfft, mode="psd", detrend=True):
     """((C, bins, pre + post) mean, the same shape of bounds): the mean over the trials of frames onset - pre .. onset + post."""
-    cut = [spectrogram(x[a:a + n], fs, window, nperseg, hop, nfft)[o - pre:o + post] for (a, n), o in zip(ranges, onsets)]
+    cut = [spectrogram(x[a:a + n], fs, window, nperseg, hop, nfft, mode, detrend)[o - pre:o + post] for (a, n), o in zip(ranges, onsets)]
     assert all(len(c) == pre + post for c in cut)
     mean = np.mean(np.stack(cut), axis=0)                                           # (J, C, bins)
-    bound = np.mean(np.stack([np.broadcast_to(frame_bound(c, nperseg), c.shape) for c in cut]), axis=0) + len(cut) * U * np.abs(mean)
+    bound = np.mean(np.stack([np.broadcast_to(frame_bound(c, nperseg, mode), c.shape) for c in cut]), axis=0) + len(cut) * U * np.abs(mean)
     return mean.transpose(1, 2, 0), bound.transpose(1, 2, 0)
 
 
-def mean(x, ranges, fs, window, nperseg, hop, nfft):
+def mean(x, ranges, fs, window, nperseg, hop, nfft, mode="psd", detrend=True):
     """((C, bins) mean over all frames of all trials, bounds)."""
-    s = trials(x, ranges, fs, window, nperseg, hop, nfft)                           # (frames, C, bins)
+    s = trials(x, ranges, fs, window, nperseg, hop, nfft, mode, detrend)            # (frames, C, bins)
     m = np.mean(s, axis=0)
-    return m, np.mean(np.broadcast_to(frame_bound(s, nperseg), s.shape), axis=0) + len(s) * U * np.abs(m)
+    return m, np.mean(np.broadcast_to(frame_bound(s, nperseg, mode), s.shape), axis=0) + len(s) * U * np.abs(m)
 
 
 def speech_locked_power(cal, cal_ranges, x, ranges, onsets, fs=1000, window_size=0.05, nb_fft_bins=100, pre_onset=0.5, post_onset=1.5):

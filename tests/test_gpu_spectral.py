@@ -10,10 +10,15 @@ of the frames' bounds plus N 2^-53 |value|.  Every frame, channel and bin is com
 
 Orders of the reductions, which the bit-for-bit tests restate on the host: `locked` adds the trials' frames in list order, from
 0.0, and divides by the number of trials; `mean` adds every trial's frames in frame order, from 0.0, then the trials' sums in
-list order, from 0.0, and divides by the number of frames."""
+list order, from 0.0, and divides by the number of frames.
+
+The second half runs the cases of tests/spectral_cases.py: every workgroup shape the picker can choose (F below 32, a partial
+last group of bin blocks beside several channel groups, CG = 8), with the same bounds.  tests/test_cpu_spectral.py proves
+without a GPU that the list reaches those shapes; every test here asserts its case's shape first."""
 import numpy as np
 import pytest
 
+import spectral_cases as sc
 import spectral_reference as ref
 
 pytestmark = pytest.mark.gpu
@@ -242,3 +247,102 @@ def test_speech_locked_power():
     import torch
     dev = speech_locked_power(torch.from_numpy(cal).cuda(), cal_ranges, torch.from_numpy(rec).cuda(), ranges, onsets)
     assert np.array_equal(dev, got)
+
+
+# ---- every workgroup shape the picker can choose (tests/spectral_cases.py) -----------------------------------------------
+@pytest.fixture(scope="module", params=sc.NAMES)
+def shaped(request):
+    """One case: its handle, signals, trial list, trials() of the whole list (computed once, shared, never written) and where
+    each trial's frames start in it."""
+    from dss_amd.spectral import SpectrogramGPU
+    name = request.param
+    _, nperseg, hop, nfft, n_ch, mode, detrend = sc.params(name)
+    s = SpectrogramGPU(sc.FS, nperseg, nperseg - hop, nfft=nfft, mode=mode, detrend="constant" if detrend else False)
+    x, ranges = sc.signals(name), sc.ranges(name)
+    frames = s.trials(x, ranges)
+    frames.setflags(write=False)
+    at = np.concatenate([[0], np.cumsum([ref.frames_of(n, nperseg, hop) for _, n in ranges])])
+    yield {"name": name, "sp": s, "x": x, "ranges": ranges, "frames": frames, "at": at, "ref": (sc.FS, s.window, nperseg, hop, nfft, mode, detrend)}
+    s.close()
+
+
+def _assert_shape(name):
+    """The case still runs the workgroup shape it is named for: otherwise the test no longer tests what it says."""
+    from dss_amd.spectral import geometry
+    _, nperseg, hop, nfft, n_ch, mode, detrend = sc.params(name)
+    got = tuple(geometry(nperseg, hop, nfft, n_ch, kind, mode, "constant" if detrend else False).F for kind in sc.KINDS)
+    assert got == sc.EXPECTED_F[name], (name, got)
+
+
+def test_shapes_trials_against_scipy(shaped):
+    name, frames = shaped["name"], shaped["frames"]
+    _assert_shape(name)
+    _, nperseg, hop, nfft, n_ch, mode, _ = sc.params(name)
+    want = sc.scipy_trials(name)
+    assert frames.shape == want.shape == (shaped["at"][-1], n_ch, nfft // 2 + 1) and frames.dtype == np.float64
+    _report(f"{name} trials", frames, want, nperseg, mode)
+    assert np.all(np.abs(frames - want) <= ref.frame_bound(want, nperseg, mode))    # every frame, channel and bin
+
+
+def test_shapes_locked_and_mean(shaped):
+    name, sp, x, frames, at = (shaped[k] for k in ("name", "sp", "x", "frames", "at"))
+    _assert_shape(name)
+    lr, onsets, pre, post = sc.locked(name)
+    got = sp.locked(x, lr, onsets, pre, post)
+    want, bound = ref.locked(x, lr, onsets, pre, post, *shaped["ref"])
+    assert got.shape == want.shape
+    print(f"{name} locked: max |difference| / bound {np.max(np.abs(got - want) / bound):.3g}")
+    assert np.all(np.abs(got - want) <= bound)
+    # the kernel's order, on frames that another workgroup shape computed: list order from 0.0, then / trials
+    acc = np.zeros((pre + post,) + frames.shape[1:])
+    for r, o in zip(lr, onsets):
+        k = shaped["ranges"].index(r)
+        acc = acc + frames[at[k] + o - pre:at[k] + o + post]
+    assert np.array_equal(got, (acc / len(lr)).transpose(1, 2, 0))
+
+    got = sp.mean(x, shaped["ranges"])
+    want, bound = ref.mean(x, shaped["ranges"], *shaped["ref"])
+    assert got.shape == want.shape
+    print(f"{name} mean: max |difference| / bound {np.max(np.abs(got - want) / bound):.3g}")
+    assert np.all(np.abs(got - want) <= bound)
+    # frames in order from 0.0, then the trials' sums in list order from 0.0, then / frames
+    total = np.zeros(frames.shape[1:])
+    for k in range(len(at) - 1):
+        part = np.zeros(frames.shape[1:])
+        for f in range(at[k], at[k + 1]):
+            part = part + frames[f]
+        total = total + part
+    assert np.array_equal(got, total / at[-1])
+
+
+def test_shapes_locked_of_one_trial_is_its_frames(shaped):
+    name, sp, x, frames, at = (shaped[k] for k in ("name", "sp", "x", "frames", "at"))
+    _assert_shape(name)
+    for k, r in enumerate(shaped["ranges"]):
+        W = at[k + 1] - at[k]
+        for pre in sorted({0, W // 2}):                                             # the onset does not matter, only onset - pre
+            assert np.array_equal(sp.locked(x, [r], [pre], pre, W - pre), frames[at[k]:at[k + 1]].transpose(1, 2, 0)), (k, pre)
+
+
+def test_shapes_channels_do_not_depend_on_their_group(shaped):
+    name, sp, x, frames = (shaped[k] for k in ("name", "sp", "x", "frames"))
+    _assert_shape(name)
+    n_ch = x.shape[1]
+    for cols in (slice(1, None, 2), slice(n_ch - 2, n_ch), slice(None, None, 3)):    # copied; read in place from the wide rows; copied
+        assert np.array_equal(sp.trials(x[:, cols], shaped["ranges"]), frames[:, cols]), cols
+    assert np.array_equal(sp.trials(x[:, n_ch - 1], shaped["ranges"]), frames[:, n_ch - 1:])
+    assert np.array_equal(sp.mean(x[:, 1::2], shaped["ranges"]), sp.mean(x, shaped["ranges"])[1::2])
+
+
+def test_shapes_lists_do_not_matter(shaped):
+    name, sp, x, frames, at, ranges = (shaped[k] for k in ("name", "sp", "x", "frames", "at", "ranges"))
+    _assert_shape(name)
+    for k, r in enumerate(ranges):
+        assert np.array_equal(sp.trials(x, [r]), frames[at[k]:at[k + 1]]), k
+    rev = sp.trials(x, ranges[::-1])
+    assert len(rev) == len(frames)
+    pos = 0
+    for k in reversed(range(len(ranges))):
+        n = at[k + 1] - at[k]
+        assert np.array_equal(rev[pos:pos + n], frames[at[k]:at[k + 1]]), k
+        pos += n
