@@ -167,6 +167,15 @@ def _declare(L):
         "dss_spec_mean": (i, [vp, vp, C.c_longlong, i, i, i, vp, vp, vp]),
         "dss_spec_mean_dev": (i, [vp, vp, C.c_longlong, i, i, i, vp, vp, vp, vp]),
         "dss_spec_geometry": (i, [vp, i, i, vp]),
+        "dss_contam_check_params": (i, [vp]),
+        "dss_contam_check_window": (i, [vp, vp]),
+        "dss_contam_frames_for": (C.c_longlong, [C.c_longlong, i, i, i]),
+        "dss_contam_check_call": (C.c_longlong, [vp, C.c_longlong, i, i]),
+        "dss_contam_result_size": (C.c_longlong, [vp, i, vp]),
+        "dss_contam_create": (vp, [vp, vp]),
+        "dss_contam_destroy": (None, [vp]),
+        "dss_contam_moments": (i, [vp, vp, C.c_longlong, i, i, vp, vp, vp]),
+        "dss_contam_moments_dev": (i, [vp, vp, C.c_longlong, i, i, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

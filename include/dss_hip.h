@@ -698,6 +698,58 @@ int dss_spec_mean(dss_spec *h, const double *x, long long n_rows, int ld, int C,
 int dss_spec_mean_dev(dss_spec *h, const double *d_x, long long n_rows, int ld, int C, int n_trials, const long long *first,
                       const long long *length, double *d_out, void *hip_stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Part 12 -- the lagged audio-ECoG spectrogram correlation sums of the acoustic contamination analysis (stage 1 of the reference's
+ * replicate.sh; eval/contamination/run_contamination_analysis.m drives a MATLAB toolbox after Roussel et al. that the reference
+ * does not ship, so the definition is this project's own restatement of the published method: DESIGN.md and
+ * tests/contamination_reference.py; parity with the toolbox's output is not pinned).  The brain signals are a row-major
+ * (n_rows, ld) float64 array of which the first C <= ld columns are channels, the audio n_rows float64 values at the same rate.
+ * Frame t is rows t * hop .. t * hop + nperseg - 1, W = (n_rows - nperseg) / hop + 1 frames, no padding; per frame the rows
+ * times the window (data of the caller), the DFT of length nperseg, the magnitude at bins bin_lo .. bin_lo + n_bins - 1, no
+ * detrending and no scale factor (a Pearson correlation does not see one).  With A[t][i] the audio's magnitudes less shift[i],
+ * N_c[t][j] those of channel c, keep[t] the frame mask, a call gives for every lag l in -max_lag .. max_lag, over the frames t
+ * with 0 <= t + l < W, keep[t] and keep[t + l]:
+ *     n[l] the number of such frames, sa[l][i] = sum A[t+l][i], saa[l][i] = sum A[t+l][i]^2,
+ *     sb[l][c][j] = sum N_c[t][j], sbb[l][c][j] = sum N_c[t][j]^2, sab[l][c][i][j] = sum A[t+l][i] N_c[t][j],
+ * and shift[i], the mean of the audio's bin i over the kept frames, which the library subtracts so that sab - sa sb / n does not
+ * cancel.  The result is ONE float64 array: n (2 max_lag + 1), shift (n_bins), sa, saa (lags, n_bins), sb, sbb (lags, C, n_bins),
+ * sab (lags, C, n_bins, n_bins), at the offsets dss_contam_result_size reports.  No spectrogram of a channel is ever stored.
+ * No atomics; every sum has one fixed order: the same call gives the same bits, from host or device buffers.  Fused multiply-adds
+ * are used.  A lag with |l| >= W has n = 0 and sums of 0.
+ * Limits: 2 <= nperseg <= 2048, hop >= 1, 1 <= n_bins <= 31, 0 <= max_lag <= 4096, C <= 65535, and 32 frames of one channel
+ * (31 min(hop, nperseg) + nperseg rows) beside the tables within the kernel's 80 KB of LDS.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct dss_contam_params {
+    int nperseg, hop;                  /* rows per frame (also the transform length), rows between frames */
+    int bin_lo, n_bins;                /* kept DFT bins bin_lo .. bin_lo + n_bins - 1 */
+    int max_lag, reserved;             /* lags -max_lag .. max_lag, in frames */
+} dss_contam_params;
+typedef struct dss_contam dss_contam;
+/* The checks of dss_contam_create on their own (no device needed). */
+int dss_contam_check_params(const dss_contam_params *p);
+/* Those, and the window's own: nperseg finite doubles, not all zero (no device needed; dss_contam_create runs it first). */
+int dss_contam_check_window(const dss_contam_params *p, const double *window);
+/* Frames of a recording of n_rows rows, or DSS_EINVAL: n_rows < nperseg, nperseg < 2, hop < 1, max_lag < 0, or frames plus lags
+ * beyond the kernels' 32-bit frame index (no device needed).  max_lag >= the frame count is allowed: the outer lags are empty. */
+long long dss_contam_frames_for(long long n_rows, int nperseg, int hop, int max_lag);
+/* The checks both calls make of their sizes before they touch the device, on their own: what dss_contam_check_params and
+ * dss_contam_frames_for refuse, n_channels < 1, ld < n_channels, n_channels > 65535.  The number of frames, or DSS_EINVAL (no
+ * device needed). */
+long long dss_contam_check_call(const dss_contam_params *p, long long n_rows, int ld, int n_channels);
+/* Doubles of the result for n_channels channels, and (offsets != NULL) where n, shift, sa, saa, sb, sbb, sab start in it (no
+ * device needed).  DSS_EINVAL for n_channels outside 1 .. 65535. */
+long long dss_contam_result_size(const dss_contam_params *p, int n_channels, long long offsets[7]);
+/* window: nperseg doubles (dss_amd.contamination.hamming_symmetric).  NULL on failure. */
+dss_contam *dss_contam_create(const dss_contam_params *p, const double *window);
+void dss_contam_destroy(dss_contam *h);
+/* Host buffers.  keep_frames: W bytes, 0 drops the frame, or NULL for all frames (a HOST array in both forms).  Returns 0. */
+int dss_contam_moments(dss_contam *h, const double *brain, long long n_rows, int ld, int C, const double *audio,
+                       const unsigned char *keep_frames, double *out);
+/* Device-resident: d_brain, d_audio and d_out are device pointers.  Returns once the launches are queued on hip_stream; one call
+ * per handle may be in flight. */
+int dss_contam_moments_dev(dss_contam *h, const double *d_brain, long long n_rows, int ld, int C, const double *d_audio,
+                           const unsigned char *keep_frames, double *d_out, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
