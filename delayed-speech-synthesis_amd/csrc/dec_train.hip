@@ -22,6 +22,10 @@
 //                                    of the master parameters (torch layout) and of the packed copies the forward pass reads
 // Every sum has a fixed order and there are no atomics: the same call from the same state gives the same bits.  Fused
 // multiply-adds are written out (__builtin_fmaf); the library is built with -ffp-contract=off.
+// Each kernel's body is a __device__ __forceinline__ function that takes the descriptor by reference and the block's index as an
+// argument, because two kernels run it: the single trainer's (above), and the group form at the end of this file, which steps
+// several trainers in one launch (blockIdx.y is the model; DESIGN.md, "Training several decoders at once").  The arithmetic is
+// stated once, so a model's bits do not depend on which of the two ran it.
 #include "dec_lstm_dot.h"
 
 // offsets of the eighteen tensors in the flat parameter array (state_dict order; also of the gradients and the square averages)
@@ -45,28 +49,38 @@ __host__ __device__ static inline DssDecTrainOff dec_train_off(int C, int H, int
 
 long dss_dec_train_param_count(int C, int H, int O) { return dec_train_off(C, H, O).total; }
 
+// A pointer read from the descriptor or from a trial table, as a pointer to global memory.  The compiler knows that of a kernel
+// argument's members, not of a pointer it loaded from a table (the group kernels at the end of this file), which it would address
+// through the flat aperture: those loads also count as LDS traffic in the waits of the serial chains.  Changes no value.
+template <typename P>
+__device__ __forceinline__ P *dec_gp(P *p)
+{
+    typedef __attribute__((address_space(1))) P *G;
+    return (P *)(G)(unsigned long long)p;
+}
+
 // ---- forward, one layer: bilstm_layer_kernel<., 1> for one stream, with the stash ---------------------------------------------
 // blockIdx.x is the direction; step s is frame s (forward) or T - 1 - s (backward).  The dot products, the bias add and the cell
 // update are the inference kernel's, term for term, so the features of a trial without a mask are its bits.
 template <typename InT, int LAYER>
-__global__ void __launch_bounds__(DEC_THREADS)
-dec_train_layer_kernel(DssDecTrainDev d, const InT *__restrict__ in, int T, const float *__restrict__ mask)
+__device__ __forceinline__ void dec_train_layer_body(const DssDecTrainDev &d, const int dir, const InT *__restrict__ in, const int T,
+                                                     const float *__restrict__ mask)
 {
     typedef typename DecVec<1>::type V;
     __shared__ __attribute__((aligned(16))) V xin[DEC_TP][DEC_MAXC];
     __shared__ __attribute__((aligned(16))) V hs[DEC_MAXH];               // units H .. Hp-1 stay zero
     __shared__ __attribute__((aligned(16))) V gates[4 * DEC_MAXH];
-    const int tid = threadIdx.x, H = d.H, H4 = 4 * H, dir = blockIdx.x;
+    const int tid = threadIdx.x, H = d.H, H4 = 4 * H;
     const int Cin = LAYER ? 2 * H : d.C;
     const int Cp = (Cin + 3) & ~3, Hp = (H + 3) & ~3;
-    const float *wT = d.wT[LAYER][dir];
+    const float *wT = dec_gp(d.wT[LAYER][dir]);
     const bool own = tid < H, rowt = tid < H4;
-    float *act = d.act[LAYER][dir], *cst = d.c[LAYER][dir], *hst = d.h[LAYER][dir];
+    float *act = dec_gp(d.act[LAYER][dir]), *cst = dec_gp(d.c[LAYER][dir]), *hst = dec_gp(d.h[LAYER][dir]);
     float c = 0.f;
     for (int k = tid; k < DEC_MAXH; k += DEC_THREADS) hs[k].v = 0.f;
     for (int k = tid; k < DEC_TP * DEC_MAXC; k += DEC_THREADS) reinterpret_cast<float *>(xin)[k] = 0.f;
     if (own) { cst[tid] = 0.f; hst[tid] = 0.f; }           // row 0 of the stashes: the zero state
-    const float bias = rowt ? d.b[LAYER][dir][tid] : 0.f;
+    const float bias = rowt ? dec_gp(d.b[LAYER][dir])[tid] : 0.f;
     df4 whh[DEC_MAXH / 4];                                 // this thread's row of W_hh, in registers for all steps
     {
         const df4 *wr = reinterpret_cast<const df4 *>(wT + (size_t)Cp * H4) + (rowt ? tid : 0);
@@ -81,7 +95,7 @@ dec_train_layer_kernel(DssDecTrainDev d, const InT *__restrict__ in, int T, cons
             const int step = step0 + tt, t = dir ? T - 1 - step : step;
             const float x = (float)in[(size_t)t * Cin + k];
             xin[tt][k].v = x;
-            if (LAYER == 0 && dir == 0) d.xs[(size_t)t * Cin + k] = x;
+            if (LAYER == 0 && dir == 0) dec_gp(d.xs)[(size_t)t * Cin + k] = x;
         }
         __syncthreads();
         V pre[DEC_TP];
@@ -118,12 +132,19 @@ dec_train_layer_kernel(DssDecTrainDev d, const InT *__restrict__ in, int T, cons
                 cst[(size_t)(step + 1) * H + tid] = c;
                 hst[(size_t)(step + 1) * H + tid] = h;
                 const size_t oi = (size_t)t * (2 * H) + dir * H + tid;
-                if (LAYER == 0) d.midm[oi] = mask ? h * mask[oi] : h;
-                else d.top[oi] = h;
+                if (LAYER == 0) dec_gp(d.midm)[oi] = mask ? h * mask[oi] : h;
+                else dec_gp(d.top)[oi] = h;
             }
             __syncthreads();
         }
     }
+}
+
+template <typename InT, int LAYER>
+__global__ void __launch_bounds__(DEC_THREADS)
+dec_train_layer_kernel(DssDecTrainDev d, const InT *__restrict__ in, int T, const float *__restrict__ mask)
+{
+    dec_train_layer_body<InT, LAYER>(d, blockIdx.x, in, T, mask);
 }
 
 // ---- head, loss terms, gradient of the features ---------------------------------------------------------------------------------
@@ -131,18 +152,17 @@ dec_train_layer_kernel(DssDecTrainDev d, const InT *__restrict__ in, int T, cons
 // dfeat = 2 (feat - target) / (T O), evaluated in float64 and rounded once; lossf[t] = sum over o, in that order, of the squared
 // differences in float64; dtop[t][k] = sum over o, in that order, of w[o][k] dfeat[t][o].
 #define DTH_ROWS 8
-__global__ void __launch_bounds__(256)
-dec_train_head_kernel(DssDecTrainDev d, int T, const float *__restrict__ targets)
+__device__ __forceinline__ void dec_train_head_body(const DssDecTrainDev &d, const int blk, const int T, const float *__restrict__ targets)
 {
     extern __shared__ __attribute__((aligned(16))) float rs[];             // [O][K + 1] weights, [DTH_ROWS][K] inputs, [DTH_ROWS][O] dfeat
     __shared__ double es[DTH_ROWS][DSS_DEC_MAXO];
     const int tid = threadIdx.x, K = 2 * d.H, O = d.O;
     const DssDecTrainOff o = dec_train_off(d.C, d.H, O);
-    const float *w = d.p + o.wr, *b = d.p + o.br;
+    const float *w = dec_gp(d.p) + o.wr, *b = dec_gp(d.p) + o.br;
     float *ws = rs, *xs = rs + (size_t)O * (K + 1), *dfs = xs + (size_t)DTH_ROWS * K;
-    const int t0 = blockIdx.x * DTH_ROWS, nst = min(DTH_ROWS, T - t0);
+    const int t0 = blk * DTH_ROWS, nst = min(DTH_ROWS, T - t0);
     for (int k = tid; k < O * K; k += 256) { const int oo = k / K, j = k - oo * K; ws[oo * (K + 1) + j] = w[k]; }
-    for (int k = tid; k < DTH_ROWS * K; k += 256) xs[k] = k / K < nst ? d.top[(size_t)t0 * K + k] : 0.f;
+    for (int k = tid; k < DTH_ROWS * K; k += 256) xs[k] = k / K < nst ? dec_gp(d.top)[(size_t)t0 * K + k] : 0.f;
     __syncthreads();
     for (int idx = tid; idx < nst * O; idx += 256) {
         const int rr = idx / O, oo = idx - rr * O;
@@ -153,8 +173,8 @@ dec_train_head_kernel(DssDecTrainDev d, int T, const float *__restrict__ targets
         const size_t fi = (size_t)(t0 + rr) * O + oo;
         const double e = (double)f - (double)targets[fi];
         const float df = (float)(2.0 * e / ((double)T * (double)O));
-        d.feat[fi] = f;
-        d.dfeat[fi] = df;
+        dec_gp(d.feat)[fi] = f;
+        dec_gp(d.dfeat)[fi] = df;
         dfs[idx] = df;
         es[rr][oo] = e;
     }
@@ -162,14 +182,20 @@ dec_train_head_kernel(DssDecTrainDev d, int T, const float *__restrict__ targets
     if (tid < nst) {
         double acc = 0.0;
         for (int oo = 0; oo < O; ++oo) acc += es[tid][oo] * es[tid][oo];
-        d.lossf[t0 + tid] = acc;
+        dec_gp(d.lossf)[t0 + tid] = acc;
     }
     for (int idx = tid; idx < nst * K; idx += 256) {
         const int rr = idx / K, k = idx - rr * K;
         float a = 0.f;
         for (int oo = 0; oo < O; ++oo) a = __builtin_fmaf(ws[oo * (K + 1) + k], dfs[rr * O + oo], a);
-        d.dtop[(size_t)(t0 + rr) * K + k] = a;
+        dec_gp(d.dtop)[(size_t)(t0 + rr) * K + k] = a;
     }
+}
+
+__global__ void __launch_bounds__(256)
+dec_train_head_kernel(DssDecTrainDev d, int T, const float *__restrict__ targets)
+{
+    dec_train_head_body(d, blockIdx.x, T, targets);
 }
 
 // ---- backward through time of one (layer, direction) --------------------------------------------------------------------------
@@ -181,36 +207,36 @@ dec_train_head_kernel(DssDecTrainDev d, int T, const float *__restrict__ targets
 // registers for the whole trial (the H rows in row order), and the owner adds the four parts as (i + f) + (g + o).
 // The owner's seven stash values of a step are loaded one step ahead, so their latency is off the chain.
 // Layer 1's launch has a third workgroup: the trial's loss, the per-frame terms added in frame order in float64.
+__device__ __forceinline__ void dec_train_loss_body(const DssDecTrainDev &d, const int T, double *__restrict__ loss)
+{
+    __shared__ double ls[DSS_DEC_TRAIN_MAXT];
+    const int tid = threadIdx.x;
+    for (int t = tid; t < T; t += DEC_THREADS) ls[t] = dec_gp(d.lossf)[t];
+    __syncthreads();
+    if (tid == 0) {
+        double acc = 0.0;
+        for (int t = 0; t < T; ++t) acc += ls[t];
+        *loss = acc / ((double)T * (double)d.O);
+    }
+}
+
 template <int LAYER>
-__global__ void __launch_bounds__(DEC_THREADS)
-dec_train_bptt_kernel(DssDecTrainDev d, int T, double *__restrict__ loss)
+__device__ __forceinline__ void dec_train_bptt_body(const DssDecTrainDev &d, const int dir, const int T)
 {
     __shared__ __attribute__((aligned(16))) float dgs[4][DEC_MAXH];       // the gate gradients of the step in hand; units >= H stay zero
     __shared__ float part[4][DEC_MAXH];                                   // W_hh^T dG per gate, before the owner adds them
     const int tid = threadIdx.x, H = d.H, H4 = 4 * H;
-    if (LAYER == 1 && blockIdx.x == 2) {
-        __shared__ double ls[DSS_DEC_TRAIN_MAXT];
-        for (int t = tid; t < T; t += DEC_THREADS) ls[t] = d.lossf[t];
-        __syncthreads();
-        if (tid == 0) {
-            double acc = 0.0;
-            for (int t = 0; t < T; ++t) acc += ls[t];
-            *loss = acc / ((double)T * (double)d.O);
-        }
-        return;
-    }
-    const int dir = blockIdx.x;
     const DssDecTrainOff o = dec_train_off(d.C, H, d.O);
-    const float *Whh = d.p + (dir ? o.whh[LAYER][1] : o.whh[LAYER][0]);
+    const float *Whh = dec_gp(d.p) + (dir ? o.whh[LAYER][1] : o.whh[LAYER][0]);
     const int q = tid / DEC_MAXH, j = tid - q * DEC_MAXH;
     const bool own = tid < H, colt = j < H;
     float wt[DEC_MAXH];
 #pragma unroll
     for (int r = 0; r < DEC_MAXH; ++r) wt[r] = (colt && r < H) ? Whh[((size_t)q * H + r) * H + j] : 0.f;
     reinterpret_cast<float *>(dgs)[tid] = 0.f;             // (DEC_THREADS == 4 * DEC_MAXH)
-    const float *act = dir ? d.act[LAYER][1] : d.act[LAYER][0], *cst = dir ? d.c[LAYER][1] : d.c[LAYER][0];
-    const float *up = (LAYER ? d.dtop : d.dmid) + dir * H + tid;
-    float *dG = dir ? d.dg[LAYER][1] : d.dg[LAYER][0];
+    const float *act = dec_gp(dir ? d.act[LAYER][1] : d.act[LAYER][0]), *cst = dec_gp(dir ? d.c[LAYER][1] : d.c[LAYER][0]);
+    const float *up = dec_gp(LAYER ? d.dtop : d.dmid) + dir * H + tid;
+    float *dG = dec_gp(dir ? d.dg[LAYER][1] : d.dg[LAYER][0]);
     // the owner's stash values of step s, into seven registers
 #define DEC_LOAD_STEP(s)                                                                                                           \
     do {                                                                                                                           \
@@ -260,22 +286,32 @@ dec_train_bptt_kernel(DssDecTrainDev d, int T, double *__restrict__ loss)
 #undef DEC_LOAD_STEP
 }
 
+template <int LAYER>
+__global__ void __launch_bounds__(DEC_THREADS)
+dec_train_bptt_kernel(DssDecTrainDev d, int T, double *__restrict__ loss)
+{
+    if (LAYER == 1 && blockIdx.x == 2) {
+        dec_train_loss_body(d, T, loss);
+        return;
+    }
+    dec_train_bptt_body<LAYER>(d, blockIdx.x, T);
+}
+
 // ---- what layer 1 sends down ------------------------------------------------------------------------------------------------------
 // dmid[t][k] = mask[t][k] (sum_r W_ih_l1[r][k] dG1[fwd][t][r] + sum_r W_ih_l1_reverse[r][k] dG1[bwd][t][r]), k < 2H: each sum over
 // the 4H gate rows in row order, the forward direction's first.  A workgroup takes DTM_FR frames; thread k owns column k, so a wave's
 // load of a weight row is consecutive bytes; the gate gradients of the frames sit side by side in LDS (broadcast reads).
 #define DTM_FR 8
-__global__ void __launch_bounds__(256)
-dec_train_dmid_kernel(DssDecTrainDev d, int T, const float *__restrict__ mask)
+__device__ __forceinline__ void dec_train_dmid_body(const DssDecTrainDev &d, const int blk, const int T, const float *__restrict__ mask)
 {
     __shared__ __attribute__((aligned(16))) float dgl[2][4 * DEC_MAXH][DTM_FR];
     const int tid = threadIdx.x, H = d.H, H4 = 4 * H, K = 2 * H;
     const DssDecTrainOff o = dec_train_off(d.C, H, d.O);
-    const int t0 = blockIdx.x * DTM_FR, nst = min(DTM_FR, T - t0);
+    const int t0 = blk * DTM_FR, nst = min(DTM_FR, T - t0);
     for (int idx = tid; idx < 2 * DTM_FR * H4; idx += 256) {
         const int dd = idx / (DTM_FR * H4), rem = idx - dd * (DTM_FR * H4);
         const int tt = rem / H4, r = rem - tt * H4;
-        dgl[dd][r][tt] = tt < nst ? d.dg[1][dd][(size_t)(t0 + tt) * H4 + r] : 0.f;
+        dgl[dd][r][tt] = tt < nst ? dec_gp(d.dg[1][dd])[(size_t)(t0 + tt) * H4 + r] : 0.f;
     }
     __syncthreads();
     if (tid >= K) return;
@@ -284,7 +320,7 @@ dec_train_dmid_kernel(DssDecTrainDev d, int T, const float *__restrict__ mask)
     for (int dd = 0; dd < 2; ++dd) {
 #pragma unroll
         for (int tt = 0; tt < DTM_FR; ++tt) acc[dd][tt] = 0.f;
-        const float *W = d.p + o.wih[1][dd] + tid;
+        const float *W = dec_gp(d.p) + o.wih[1][dd] + tid;
         int r = 0;
         for (; r + 4 <= H4; r += 4) {
             float w[4];
@@ -306,8 +342,14 @@ dec_train_dmid_kernel(DssDecTrainDev d, int T, const float *__restrict__ mask)
         const size_t oi = (size_t)(t0 + tt) * K + tid;
         float s = acc[0][tt] + acc[1][tt];
         if (mask) s *= mask[oi];
-        d.dmid[oi] = s;
+        dec_gp(d.dmid)[oi] = s;
     }
+}
+
+__global__ void __launch_bounds__(256)
+dec_train_dmid_kernel(DssDecTrainDev d, int T, const float *__restrict__ mask)
+{
+    dec_train_dmid_body(d, blockIdx.x, T, mask);
 }
 
 // ---- the parallel part: weight gradients and the RMSprop update --------------------------------------------------------------
@@ -324,25 +366,26 @@ dec_train_dmid_kernel(DssDecTrainDev d, int T, const float *__restrict__ mask)
 
 __device__ __forceinline__ float dec_rmsprop(const DssDecTrainDev &d, int k, float g, int apply, double lr, double alpha, double eps)
 {
-    d.g[k] = g;
-    if (!apply) return d.p[k];
-    const float sq = (float)(alpha * (double)d.sq[k] + (1.0 - alpha) * ((double)g * (double)g));
-    d.sq[k] = sq;
-    const float p = (float)((double)d.p[k] - lr * (double)g / (sqrt((double)sq) + eps));
-    d.p[k] = p;
+    float *dp = dec_gp(d.p), *dsq = dec_gp(d.sq);
+    dec_gp(d.g)[k] = g;
+    if (!apply) return dp[k];
+    const float sq = (float)(alpha * (double)dsq[k] + (1.0 - alpha) * ((double)g * (double)g));
+    dsq[k] = sq;
+    const float p = (float)((double)dp[k] - lr * (double)g / (sqrt((double)sq) + eps));
+    dp[k] = p;
     return p;
 }
 
-__global__ void __launch_bounds__(DTS_THREADS)
-dec_train_step_kernel(DssDecTrainDev d, int T, int apply, double lr, double alpha, double eps)
+__device__ __forceinline__ void dec_train_step_body(const DssDecTrainDev &d, const int b, const int T, const int apply, const double lr,
+                                                    const double alpha, const double eps)
 {
     __shared__ float dgt[DTS_THREADS];
-    const int tid = threadIdx.x, b = blockIdx.x, C = d.C, H = d.H, H4 = 4 * H, O = d.O;
+    const int tid = threadIdx.x, C = d.C, H = d.H, H4 = 4 * H, O = d.O;
     const bool head = b >= 4 * H4;
     const int LD = head ? 0 : b / H4, L = LD >> 1, dir = LD & 1, r = head ? b - 4 * H4 : b - LD * H4;
-    const float *dg = head ? d.dfeat + r : d.dg[L][dir] + r;
+    const float *dg = dec_gp(head ? d.dfeat : d.dg[L][dir]) + r;
     const int dgs = head ? O : H4;
-    const float *inA = head ? d.top : (L ? d.midm : d.xs), *inB = d.h[L][dir];
+    const float *inA = dec_gp(head ? d.top : (L ? d.midm : d.xs)), *inB = dec_gp(d.h[L][dir]);
     const int nA = head || L ? 2 * H : C, nB = head ? 0 : H, ncol = nA + nB + 1;
     const int Cp = (nA + 3) & ~3;
     // the flat offsets of this (layer, direction)'s four tensors, and of the head (dec_train_off, without an indexed table)
@@ -372,7 +415,7 @@ dec_train_step_kernel(DssDecTrainDev d, int T, int apply, double lr, double alph
             const float g = dgt[tt];
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                const float x = bias[u] ? 1.f : src[u][(long)(t0 + tt) * stride[u]];
+                const float x = bias[u] ? 1.f : dec_gp(src[u])[(long)(t0 + tt) * stride[u]];
                 acc[u] = __builtin_fmaf(g, x, acc[u]);
             }
         }
@@ -387,16 +430,22 @@ dec_train_step_kernel(DssDecTrainDev d, int T, int apply, double lr, double alph
         } else if (bias[u]) {
             const float bi = dec_rmsprop(d, o_bih + r, acc[u], apply, lr, alpha, eps);
             const float bh = dec_rmsprop(d, o_bhh + r, acc[u], apply, lr, alpha, eps);
-            if (apply) d.b[L][dir][r] = bi + bh;
+            if (apply) dec_gp(d.b[L][dir])[r] = bi + bh;
         } else {
             const bool a = k < nA;
             const int pk = a ? o_wih + r * nA + k : o_whh + r * H + (k - nA);
             const float p = dec_rmsprop(d, pk, acc[u], apply, lr, alpha, eps);
             // the packed copy: [inputs / 4][4H rows][4 consecutive inputs], W_hh behind W_ih's padded inputs
             const int ki = a ? k : Cp + (k - nA);
-            if (apply) d.wT[L][dir][((size_t)(ki >> 2) * H4 + r) * 4 + (ki & 3)] = p;
+            if (apply) dec_gp(d.wT[L][dir])[((size_t)(ki >> 2) * H4 + r) * 4 + (ki & 3)] = p;
         }
     }
+}
+
+__global__ void __launch_bounds__(DTS_THREADS)
+dec_train_step_kernel(DssDecTrainDev d, int T, int apply, double lr, double alpha, double eps)
+{
+    dec_train_step_body(d, blockIdx.x, T, apply, lr, alpha, eps);
 }
 
 int dss_launch_dec_train_trial(const DssDecTrainDev &d, const void *d_frames, int frames_f64, int T, const float *d_targets,
@@ -422,6 +471,97 @@ int dss_launch_dec_train_trial(const DssDecTrainDev &d, const void *d_frames, in
     hipLaunchKernelGGL((dec_train_bptt_kernel<0>), two, block, 0, st, d, T, (double *)nullptr);
     DSS_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(dec_train_step_kernel, dim3(16 * H + O), dim3(DTS_THREADS), 0, st, d, T, apply_step, lr, alpha, eps);
+    DSS_HIP_CHECK(hipGetLastError());
+    return DSS_OK;
+}
+
+// ---- several trainers in one launch (Part 13) ---------------------------------------------------------------------------------
+// The same seven launches with a model axis: blockIdx.y is the model, blockIdx.x keeps its meaning.  A workgroup reads its model's
+// descriptor from a device table of M and its model's entry of the step's trial table (uniform addresses: scalar loads), then runs
+// the body the single-trainer kernel runs, so a model's numbers do not depend on M, on its place in the group or on what the others
+// do.  The grids of the head and of dmid cover the longest trial of the step; workgroups past their own model's T return at once,
+// and T == 0 is a model that sits the step out: none of its workgroups writes anything.
+// Layer 1's BPTT launch is (2, M + ceil(M / 2)): rows y < M are the chains of model y, the rows behind them are the loss-adding
+// workgroups of models 2 (y - M) + x, so that every chain is dispatched before the first of them.
+template <typename InT, int LAYER>
+__global__ void __launch_bounds__(DEC_THREADS)
+dec_group_layer_kernel(const DssDecTrainDev *__restrict__ models, const DssDecGroupTrial *__restrict__ trials)
+{
+    const DssDecGroupTrial tr = trials[blockIdx.y];
+    if (tr.T <= 0) return;
+    const DssDecTrainDev &d = models[blockIdx.y];
+    if (LAYER) dec_train_layer_body<InT, LAYER>(d, blockIdx.x, dec_gp((const InT *)d.midm), tr.T, (const float *)nullptr);
+    else dec_train_layer_body<InT, LAYER>(d, blockIdx.x, dec_gp((const InT *)tr.frames), tr.T, dec_gp(tr.mask));
+}
+
+__global__ void __launch_bounds__(256)
+dec_group_head_kernel(const DssDecTrainDev *__restrict__ models, const DssDecGroupTrial *__restrict__ trials)
+{
+    const DssDecGroupTrial tr = trials[blockIdx.y];
+    if ((int)blockIdx.x * DTH_ROWS >= tr.T) return;
+    const DssDecTrainDev &d = models[blockIdx.y];
+    dec_train_head_body(d, blockIdx.x, tr.T, dec_gp(tr.targets));
+}
+
+template <int LAYER>
+__global__ void __launch_bounds__(DEC_THREADS)
+dec_group_bptt_kernel(const DssDecTrainDev *__restrict__ models, const DssDecGroupTrial *__restrict__ trials, int M)
+{
+    if (LAYER == 1 && (int)blockIdx.y >= M) {
+        const int m = 2 * ((int)blockIdx.y - M) + (int)blockIdx.x;
+        if (m >= M) return;
+        const DssDecGroupTrial tr = trials[m];
+        if (tr.T <= 0) return;
+        const DssDecTrainDev &d = models[m];
+        dec_train_loss_body(d, tr.T, dec_gp(tr.loss));
+        return;
+    }
+    const DssDecGroupTrial tr = trials[blockIdx.y];
+    if (tr.T <= 0) return;
+    const DssDecTrainDev &d = models[blockIdx.y];
+    dec_train_bptt_body<LAYER>(d, blockIdx.x, tr.T);
+}
+
+__global__ void __launch_bounds__(256)
+dec_group_dmid_kernel(const DssDecTrainDev *__restrict__ models, const DssDecGroupTrial *__restrict__ trials)
+{
+    const DssDecGroupTrial tr = trials[blockIdx.y];
+    if ((int)blockIdx.x * DTM_FR >= tr.T) return;
+    const DssDecTrainDev &d = models[blockIdx.y];
+    dec_train_dmid_body(d, blockIdx.x, tr.T, dec_gp(tr.mask));
+}
+
+__global__ void __launch_bounds__(DTS_THREADS)
+dec_group_step_kernel(const DssDecTrainDev *__restrict__ models, const DssDecGroupTrial *__restrict__ trials)
+{
+    const DssDecGroupTrial tr = trials[blockIdx.y];
+    if (tr.T <= 0) return;
+    const DssDecTrainDev &d = models[blockIdx.y];
+    dec_train_step_body(d, blockIdx.x, tr.T, tr.apply, tr.lr, tr.alpha, tr.eps);
+}
+
+int dss_launch_dec_train_group(const DssDecTrainDev *d_models, const DssDecGroupTrial *d_trials, int M, int C, int H, int O, int max_T,
+                               int frames_f64, hipStream_t st)
+{
+    if (M < 1 || M > DSS_DEC_GROUP_MAXM || H < 1 || H > DEC_MAXH || 4 * H > DEC_THREADS || C < 1 || C > DEC_MAXC || 2 * H > DEC_MAXC ||
+        O < 1 || O > DSS_DEC_MAXO || max_T < 1 || max_T > DSS_DEC_TRAIN_MAXT) {
+        dss_set_error("decoder group kernels: %d models / %d hidden units / %d inputs / %d outputs / %d frames out of range (<= %d / <= %d / <= %d / <= %d / <= %d)",
+                      M, H, C, O, max_T, DSS_DEC_GROUP_MAXM, DEC_MAXH, DEC_MAXC, DSS_DEC_MAXO, DSS_DEC_TRAIN_MAXT);
+        return DSS_EINVAL;
+    }
+    const dim3 two(2, M), block(DEC_THREADS);
+    if (frames_f64) hipLaunchKernelGGL((dec_group_layer_kernel<double, 0>), two, block, 0, st, d_models, d_trials);
+    else hipLaunchKernelGGL((dec_group_layer_kernel<float, 0>), two, block, 0, st, d_models, d_trials);
+    hipLaunchKernelGGL((dec_group_layer_kernel<float, 1>), two, block, 0, st, d_models, d_trials);
+    DSS_HIP_CHECK(hipGetLastError());
+    const size_t hlds = ((size_t)O * (2 * H + 1) + (size_t)DTH_ROWS * 2 * H + (size_t)DTH_ROWS * O) * sizeof(float);
+    hipLaunchKernelGGL(dec_group_head_kernel, dim3((max_T + DTH_ROWS - 1) / DTH_ROWS, M), dim3(256), hlds, st, d_models, d_trials);
+    hipLaunchKernelGGL((dec_group_bptt_kernel<1>), dim3(2, M + (M + 1) / 2), block, 0, st, d_models, d_trials, M);
+    DSS_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(dec_group_dmid_kernel, dim3((max_T + DTM_FR - 1) / DTM_FR, M), dim3(256), 0, st, d_models, d_trials);
+    hipLaunchKernelGGL((dec_group_bptt_kernel<0>), two, block, 0, st, d_models, d_trials, M);
+    DSS_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(dec_group_step_kernel, dim3(16 * H + O, M), dim3(DTS_THREADS), 0, st, d_models, d_trials);
     DSS_HIP_CHECK(hipGetLastError());
     return DSS_OK;
 }

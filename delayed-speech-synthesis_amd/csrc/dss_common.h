@@ -273,6 +273,19 @@ long dss_dec_train_param_count(int C, int H, int O);
 int dss_launch_dec_train_trial(const DssDecTrainDev &d, const void *d_frames, int frames_f64, int T, const float *d_targets,
                                const float *d_mask, int apply_step, double lr, double alpha, double eps, double *d_loss, hipStream_t s);
 
+// ---- several trainers of equal sizes stepped by one set of launches (dec_train.hip; Part 13) -------------------------------
+#define DSS_DEC_GROUP_MAXM 64     // 3 x 64 workgroups of 512 threads in the widest serial launch: all resident on 256 CUs
+struct DssDecGroupTrial {         // one model's entry of a step's trial table (64 bytes); T == 0: the model sits the step out
+    const void *frames;           // (T, C) float32 or float64 (one dtype per step)
+    const float *targets, *mask;  // (T, O); (T, 2H) or NULL
+    double *loss;                 // where the model's loss goes
+    double lr, alpha, eps;
+    int T, apply;
+};
+// one step of M trainers: d_models[M] and d_trials[M] are device tables; max_T is the longest T of the step (>= 1)
+int dss_launch_dec_train_group(const DssDecTrainDev *d_models, const DssDecGroupTrial *d_trials, int M, int C, int H, int O, int max_T,
+                               int frames_f64, hipStream_t s);
+
 struct DssHgaDev {
     int S, C, fs, nsec;
     float wl, ws;

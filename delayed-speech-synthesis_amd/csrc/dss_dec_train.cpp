@@ -179,6 +179,15 @@ extern "C" int dss_dec_trainer_trial_dev(dss_dec_trainer *tr, const void *d_fram
                                       (hipStream_t)hip_stream);
 }
 
+int dss_dec_trainer_view(dss_dec_trainer *tr, DssDecTrainDev *d, int *device, int *loaded)
+{
+    if (!tr || !d || !device || !loaded) { dss_set_error("dss_dec_trainer_view: null argument"); return DSS_EINVAL; }
+    *d = tr->d;
+    *device = tr->device;
+    *loaded = tr->loaded ? 1 : 0;
+    return DSS_OK;
+}
+
 extern "C" int dss_dec_trainer_publish(dss_dec_trainer *tr, dss_dec *v, void *hip_stream)
 {
     if (!tr || !tr->loaded) { dss_set_error("dss_dec_trainer_publish: the trainer is NULL or has no parameters loaded"); return DSS_EINVAL; }

@@ -20,6 +20,11 @@ int dss_vad_device_weights(dss_vad *v, int *device, int *n_inputs, int *hidden_u
 struct dss_dec;
 int dss_dec_device_weights(dss_dec *v, int *device, int *n_inputs, int *hidden_units, int *n_outputs, float *w[10]);
 
+// The device descriptor of a decoder's trainer (Part 10), the device it lives on and whether parameters are loaded, for the
+// group of Part 13, which steps several trainers with one set of launches.
+struct dss_dec_trainer;
+int dss_dec_trainer_view(dss_dec_trainer *tr, DssDecTrainDev *d, int *device, int *loaded);
+
 // Small host -> device uploads that must not stall, and must not be overwritten, while earlier calls are still queued.
 //
 // hipMemcpyAsync from pageable memory may wait for the stream's earlier work (the runtime stages it), which would hold the

@@ -154,6 +154,14 @@ def _declare(L):
         "dss_dec_trainer_features": (i, [vp, i, vp]),
         "dss_dec_trainer_trial_dev": (i, [vp, vp, i, i, vp, vp, i, C.c_double, C.c_double, C.c_double, vp, vp]),
         "dss_dec_trainer_publish": (i, [vp, vp, vp]),
+        "dss_dec_group_check": (i, [i, i, i, i, i]),
+        "dss_dec_group_create": (vp, [i, i, i, i, i]),
+        "dss_dec_group_destroy": (None, [vp]),
+        "dss_dec_group_load": (i, [vp, i, vp]),
+        "dss_dec_group_read": (i, [vp, i, i, vp]),
+        "dss_dec_group_features": (i, [vp, i, i, vp]),
+        "dss_dec_group_publish": (i, [vp, i, vp, vp]),
+        "dss_dec_group_step_dev": (i, [vp, vp, i, vp, vp]),
         "dss_spec_check_params": (i, [vp]),
         "dss_spec_trial_frames_for": (C.c_longlong, [C.c_longlong, i, i]),
         "dss_spec_check_trials": (C.c_longlong, [C.c_longlong, i, vp, vp, i, i]),

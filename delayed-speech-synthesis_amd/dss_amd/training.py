@@ -21,6 +21,11 @@ and no windows: a whole trial (250-1500 frames) is forward from the zero state, 
 (``decoder_dropout_mask``).  ``train_decoder`` is the epoch loop, validating with ``dss_amd.validation.decoder_validation`` on a kept
 ``BiLstmDecoderGPU`` and keeping the weights with the lowest validation loss (``StoreBestModel``).
 
+``DecoderGroupTrainerGPU`` steps up to 64 decoders of equal sizes in the same seven launches (the model is ``blockIdx.y``; the kernels'
+bodies are the single trainer's, so every model's numbers are its bits), and ``train_decoders`` is that many ``train_decoder`` loops
+in lock step: the fold loop of train_bidirectional_model.py:65-78 (``leave_one_day_out``, ``join_corpora``), seeds and learning
+rates as one run.
+
 No HDF files, tensorboard, plots, ``torchinfo`` summary or per-epoch ``.npy`` dumps are produced, and the decoder script's
 vocoding of validation samples (``AsynchronousSynthesisQueue``) is not part of the loop: ``dss_amd.lpcnet.LPCNetBatch`` vocodes
 the ``features`` that ``decoder_validation`` returns."""
@@ -423,5 +428,358 @@ def train_decoder(state_dict, train_corpus, valid_corpus, epochs: int = 8, dropo
     return (best_sd if best_sd is not None else tr.state_dict()), history
 
 
+
+
+# ---- several decoders at once ------------------------------------------------------------------------------------------------------
+
+class _GroupTrial(C.Structure):
+    """``dss_dec_group_trial`` of include/dss_hip.h."""
+    _fields_ = [("d_frames", C.c_void_p), ("T", C.c_int), ("d_targets", C.c_void_p), ("d_mask", C.c_void_p), ("apply_step", C.c_int),
+                ("lr", C.c_double), ("alpha", C.c_double), ("eps", C.c_double)]
+
+
+def _per_model(v, n, what):
+    """A scalar for every model, or one entry per model."""
+    if np.ndim(v) == 0:
+        return [float(v)] * n
+    v = list(v)
+    if len(v) != n:
+        raise ValueError(f"{what}: {len(v)} entries for {n} models")
+    return [float(e) for e in v]
+
+
+class DecoderGroupTrainerGPU:
+    """The trainers of M decoders of equal sizes, stepped together: one trial for each model in ONE set of ``DecoderTrainerGPU``'s
+    seven launches, with the model as ``blockIdx.y`` (``dss_dec_group_step_dev``, csrc/dec_train.hip), so the serial chains of all
+    models run side by side on different compute units.  Every model's numbers are bit for bit those of a ``DecoderTrainerGPU``
+    with the same weights given the same trials in the same order.  1 <= M <= 64; more models are more groups."""
+
+    def __init__(self, state_dicts, max_frames: int = 2048):
+        state_dicts = list(state_dicts)
+        ws = []
+        for sd in state_dicts:
+            sd = _state_dict(sd, _decoder.fits, "DecoderGroupTrainerGPU")
+            ws.append([np.ascontiguousarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], dtype=np.float32)
+                       for k in _decoder._KEYS])
+        self._L = L = _lib.load()
+        self.M, self.max_frames = len(ws), int(max_frames)
+        if not ws:
+            _lib.check(L.dss_dec_group_check(0, 1, 1, 1, self.max_frames))
+        h4, c = ws[0][0].shape
+        self.C, self.H, self.O = int(c), int(h4 // 4), int(ws[0][16].shape[0])
+        shapes = [tuple(a.shape) for a in ws[0]]
+        for m, w in enumerate(ws):
+            if [tuple(a.shape) for a in w] != shapes:
+                raise ValueError(f"DecoderGroupTrainerGPU: model {m} has other sizes than model 0 (one group, one size)")
+        _lib.check(L.dss_dec_group_check(self.M, self.C, self.H, self.O, self.max_frames))
+        _lib.require_gpu()
+        self._n = int(L.dss_dec_trainer_param_count(self.C, self.H, self.O))
+        self._h = L.dss_dec_group_create(self.M, self.C, self.H, self.O, self.max_frames)
+        if not self._h:
+            raise MemoryError(L.dss_last_error().decode())
+        self._last = [0] * self.M
+        self._stage, self._stage_ev, self._stage_k, self._dev_masks = [None, None], [None, None], 0, None
+        for m, w in enumerate(ws):
+            _lib.check(L.dss_dec_group_load(self._h, m, (C.c_void_p * 18)(*[a.ctypes.data for a in w])))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._L.dss_dec_group_destroy(self._h)
+            self._h = None
+
+    def __len__(self):
+        return self.M
+
+    def _member(self, m):
+        m = int(m)
+        if not 0 <= m < self.M:
+            raise IndexError(f"model {m} of a group of {self.M}")
+        return m
+
+    def _upload_masks(self, host, device):
+        """The step's host masks ([(m, (T, 2H) float32 CPU tensor)]) through one page-locked buffer and one copy; returns
+        {m: device tensor}.  Two buffers take turns, each guarded by an event behind its copy, so filling the next step's masks does
+        not wait for the step in flight."""
+        import torch
+        total = sum(t.numel() for _, t in host)
+        k = self._stage_k
+        self._stage_k = 1 - k
+        if self._stage_ev[k] is not None:
+            self._stage_ev[k].synchronize()
+        if self._stage[k] is None or self._stage[k].numel() < total:
+            self._stage[k] = torch.empty((total,), dtype=torch.float32).pin_memory()
+        if self._dev_masks is None or self._dev_masks.numel() < total:
+            self._dev_masks = torch.empty((total,), dtype=torch.float32, device=device)
+        out, o = {}, 0
+        for m, t in host:
+            n = t.numel()
+            self._stage[k][o:o + n].copy_(t.reshape(-1))
+            out[m] = self._dev_masks[o:o + n]
+            o += n
+        self._dev_masks[:total].copy_(self._stage[k][:total], non_blocking=True)
+        ev = self._stage_ev[k] = self._stage_ev[k] or torch.cuda.Event()
+        ev.record()
+        return out
+
+    def step(self, xs, ys, masks=None, apply: bool = True, lr=LR, alpha=ALPHA, eps=EPS, losses=None):
+        """One step: model m runs the trial ``xs[m]`` (T_m, C) frames / ``ys[m]`` (T_m, O) targets / ``masks[m]`` (T_m, 2H)
+        multipliers or None, from the zero state, as ``DecoderTrainerGPU.trial`` would; ``xs[m] is None``: the model sits out and
+        nothing of it changes.  All frames of a step have one dtype.  ``lr``, ``alpha``, ``eps``: a scalar or one per model.
+        Returns the device tensor of M float64 losses: ``losses`` if given (a CUDA float64 tensor of M entries), else a new one
+        filled with NaN; the entries of models that sat out are not written.  Nothing synchronises with the host: steps may be
+        enqueued back to back."""
+        import torch
+        M = self.M
+        xs, ys = list(xs), list(ys)
+        masks = [None] * M if masks is None else list(masks)
+        for what, seq in (("xs", xs), ("ys", ys), ("masks", masks)):
+            if len(seq) != M:
+                raise ValueError(f"{what}: {len(seq)} entries for {M} models")
+        lrs, alphas, epss = (_per_model(v, M, w) for v, w in ((lr, "lr"), (alpha, "alpha"), (eps, "eps")))
+        table = (_GroupTrial * M)()
+        keep, host_masks, dtype, device = [], [], None, None
+        for m in range(M):
+            if xs[m] is None:
+                continue
+            x = xs[m] if isinstance(xs[m], torch.Tensor) else torch.from_numpy(np.ascontiguousarray(xs[m]))
+            if x.dtype not in (torch.float64, torch.float32):
+                raise TypeError("frames must be float64 or float32")
+            if x.dim() != 2 or x.shape[1] != self.C:
+                raise ValueError(f"model {m}: frames must be (T, {self.C})")
+            if dtype is not None and x.dtype != dtype:
+                raise TypeError("the frames of one step must have one dtype")
+            dtype = x.dtype
+            n = int(x.shape[0])
+            if not 1 <= n <= self.max_frames:
+                raise ValueError(f"model {m}: a trial of {n} frames: must be 1 .. max_frames = {self.max_frames}")
+            x = x.cuda().contiguous()
+            device = x.device
+            y = ys[m] if isinstance(ys[m], torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ys[m]))
+            if tuple(y.shape) != (n, self.O):
+                raise ValueError(f"model {m}: the targets must be ({n}, {self.O})")
+            y = y.to(dtype=torch.float32).cuda().contiguous()
+            k = masks[m]
+            if k is not None:
+                k = k if isinstance(k, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(k))
+                if tuple(k.shape) != (n, 2 * self.H):
+                    raise ValueError(f"model {m}: the mask must be ({n}, {2 * self.H})")
+                k = k.to(dtype=torch.float32).contiguous()
+                if not k.is_cuda:
+                    host_masks.append((m, k))
+            keep += [x, y, k]
+            table[m] = _GroupTrial(x.data_ptr(), n, y.data_ptr(), k.data_ptr() if k is not None and k.is_cuda else None,
+                                   int(bool(apply)), lrs[m], alphas[m], epss[m])
+        if dtype is None:
+            raise ValueError("every model sits out: a step needs at least one trial")
+        if host_masks:
+            for m, k in self._upload_masks(host_masks, device).items():
+                table[m].d_mask = k.data_ptr()
+        if losses is None:
+            losses = torch.full((M,), float("nan"), dtype=torch.float64, device=device)
+        elif not (isinstance(losses, torch.Tensor) and losses.is_cuda and losses.dtype == torch.float64 and losses.is_contiguous()
+                  and tuple(losses.shape) == (M,)):
+            raise ValueError(f"losses must be a contiguous CUDA float64 tensor of {M} entries")
+        _lib.check(self._L.dss_dec_group_step_dev(self._h, table, int(dtype == torch.float64), losses.data_ptr(),
+                                                  torch.cuda.current_stream().cuda_stream))
+        for m in range(M):
+            if table[m].T:
+                self._last[m] = int(table[m].T)
+        return losses
+
+    # ---- what the group holds, per model ----
+    def _read(self, m: int, what: int) -> dict:
+        flat = np.empty(self._n, np.float32)
+        _lib.check(self._L.dss_dec_group_read(self._h, self._member(m), what, flat.ctypes.data))
+        out, o = {}, 0
+        for k, shp in zip(_decoder._KEYS, _dec_shapes(self.C, self.H, self.O)):
+            cnt = int(np.prod(shp))
+            out[k] = flat[o:o + cnt].reshape(shp).copy()
+            o += cnt
+        return out
+
+    def gradients(self, m: int) -> dict:
+        """The gradients of model m's last trial, float32 arrays keyed by the torch names."""
+        return self._read(m, 1)
+
+    def square_avg(self, m: int) -> dict:
+        """Model m's RMSprop square averages."""
+        return self._read(m, 2)
+
+    def state_dict(self, m: int) -> dict:
+        """Model m's current parameters as float32 torch tensors."""
+        import torch
+        return {k: torch.from_numpy(v) for k, v in self._read(m, 0).items()}
+
+    def features(self, m: int) -> np.ndarray:
+        """The float32 (T, O) features of the forward half of model m's last trial."""
+        m = self._member(m)
+        if not self._last[m]:
+            raise ValueError(f"no trial has run on model {m}")
+        out = np.empty((self._last[m], self.O), np.float32)
+        _lib.check(self._L.dss_dec_group_features(self._h, m, self._last[m], out.ctypes.data))
+        return out
+
+    def publish(self, m: int, decoder: "_decoder.BiLstmDecoderGPU"):
+        """Copy model m's current weights device to device into an inference handle of the same sizes."""
+        import torch
+        if not isinstance(decoder, _decoder.BiLstmDecoderGPU):
+            raise TypeError("publish takes a BiLstmDecoderGPU")
+        _lib.check(self._L.dss_dec_group_publish(self._h, self._member(m), decoder._h, torch.cuda.current_stream().cuda_stream))
+
+
+def lockstep_schedule(orders):
+    """The steps of one epoch of several training runs in lock step: ``orders[m]`` is model m's trial order; step k holds every
+    model's k-th trial, and None for the models whose trials have run out.  [[trial or None] * M] * max(len(order))."""
+    orders = [list(o) for o in orders]
+    return [[o[k] if k < len(o) else None for o in orders] for k in range(max([len(o) for o in orders] + [0]))]
+
+
+def _group_epoch(step, gens, n_trials, lengths, hidden_units, dropout, shuffle):
+    """One epoch of M runs in lock step.  Model m's generator ``gens[m]`` draws what ``train_decoder``'s generator draws in an
+    epoch, in its order: the permutation of its ``n_trials[m]`` trials first, then the mask of each trial as its turn comes
+    (``lengths[m][trial]`` frames).  ``step(trials, masks)`` gets, per step, every model's trial index (or None) and mask (or
+    None) and returns the step's losses.  Returns ([per step: trials], [per step: what step returned])."""
+    import torch
+    orders = [torch.randperm(n, generator=g).tolist() if shuffle else list(range(n)) for n, g in zip(n_trials, gens)]
+    steps, out = lockstep_schedule(orders), []
+    for trials in steps:
+        masks = [None if k is None else decoder_dropout_mask(lengths[m][k], hidden_units, dropout, gens[m]) for m, k in enumerate(trials)]
+        out.append(step(trials, masks))
+    return steps, out
+
+
+def train_decoders(state_dicts, train_corpora, valid_corpora, epochs: int = 8, dropout: float = 0.5, lr=LR, seeds=None, columns=None,
+                   shuffle: bool = True, alpha: float = ALPHA, eps: float = EPS, max_streams: int = 256):
+    """M ``train_decoder`` loops in lock step on one ``DecoderGroupTrainerGPU``: the folds of train_bidirectional_model.py:65-68,
+    seeds or learning rates as one run.  ``state_dicts[m]``, ``train_corpora[m]``, ``valid_corpora[m]`` and ``seeds[m]`` (default
+    0 .. M - 1) are model m's arguments of ``train_decoder``; ``lr`` is a scalar or one per model; ``columns`` is shared.
+
+    Model m owns a generator seeded with ``seeds[m]`` that draws its epoch's permutation and then its masks exactly as
+    ``train_decoder`` does, and step k of an epoch runs every model's k-th trial, models with fewer trials sitting out the rest of
+    the epoch: every model's history and best weights are those of ``train_decoder`` run alone with its seed and corpora, bit
+    for bit.  After an epoch each model is published into one kept ``BiLstmDecoderGPU`` and validated on its own corpus.
+    Returns [(best state_dict, history)], one pair per model."""
+    import torch
+    from .validation import _corpus_frames
+    state_dicts, train_corpora, valid_corpora = list(state_dicts), list(train_corpora), list(valid_corpora)
+    M = len(state_dicts)
+    seeds = list(range(M)) if seeds is None else list(seeds)
+    for what, seq in (("train_corpora", train_corpora), ("valid_corpora", valid_corpora), ("seeds", seeds)):
+        if len(seq) != M:
+            raise ValueError(f"{what}: {len(seq)} entries for {M} models")
+    lrs = _per_model(lr, M, "lr")
+    xs, ys, ranges, valid, longest = [], [], [], [], 1
+    for m in range(M):
+        hx, hy, hid = _dec_corpus(train_corpora[m])
+        x, r = _corpus_frames(hx, hid, columns)
+        vx, vy, vid = _dec_corpus(valid_corpora[m])
+        vr = trial_bounds(vid.cpu().numpy() if isinstance(vid, torch.Tensor) else vid)
+        longest = max([longest] + [n for _, n in r] + [n for _, n in vr])
+        xs.append(x); ranges.append(r); valid.append((vx, vy, vid, len(vr)))
+        ys.append(hy if isinstance(hy, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(hy)))
+    if len({x.dtype for x in xs}) > 1:
+        xs = [x.double() for x in xs]
+    tr = DecoderGroupTrainerGPU(state_dicts, max_frames=longest)
+    for m in range(M):
+        if ys[m].dim() != 2 or ys[m].shape[0] != xs[m].shape[0] or ys[m].shape[1] != tr.O:
+            raise ValueError(f"model {m}: lpc_coefficients must be ({xs[m].shape[0]}, {tr.O})")
+        ys[m] = ys[m].to(device=xs[m].device, dtype=torch.float32).contiguous()
+    gens = [torch.Generator().manual_seed(int(s)) for s in seeds]
+    dec = _decoder.BiLstmDecoderGPU(max(1, min(max(v[3] for v in valid), int(max_streams))), longest, state_dict=tr.state_dict(0))
+    lengths = [[n for _, n in r] for r in ranges]
+
+    def step(trials, masks):
+        sl = [None if k is None else slice(ranges[m][k][0], ranges[m][k][0] + ranges[m][k][1]) for m, k in enumerate(trials)]
+        return tr.step([None if s is None else xs[m][s] for m, s in enumerate(sl)], [None if s is None else ys[m][s] for m, s in enumerate(sl)],
+                       masks, True, lrs, alpha, eps)
+
+    best = [(None, np.inf)] * M
+    n_steps, history = [0] * M, [[] for _ in range(M)]
+    for _ in range(int(epochs)):
+        steps, losses = _group_epoch(step, gens, [len(r) for r in ranges], lengths, tr.H, dropout, shuffle)
+        losses = torch.stack(losses).cpu().numpy() if losses else np.zeros((0, M))     # the losses stay on the device until here
+        for m in range(M):
+            mine = np.array([losses[k, m] for k, trials in enumerate(steps) if trials[m] is not None])
+            n_steps[m] += len(mine)
+            tr.publish(m, dec)
+            vx, vy, vid, _ = valid[m]
+            v = decoder_validation(dec, vx, vy, vid, columns=columns)
+            keep = v["loss"] < best[m][1]                   # StoreBestModel.update: strictly less
+            if keep:
+                best[m] = (tr.state_dict(m), v["loss"])
+            history[m].append(dict(train_loss=float(mine.mean()) if len(mine) else float("nan"), valid_loss=v["loss"],
+                                   update_steps=n_steps[m], best=bool(keep)))
+    return [(best[m][0] if best[m][0] is not None else tr.state_dict(m), history[m]) for m in range(M)]
+
+
+def leave_one_day_out(days, start_with_day=None):
+    """The folds of the reference's ``LeaveOneDayOut().split`` (local/common.py:73-101): the days sorted, rotated so that
+    ``start_with_day`` (if given) comes first, then every day in turn as the test day against all the others, in that order.
+    Yields (train_days, test_day); ValueError for a ``start_with_day`` that is not among the days."""
+    ordered = sorted(days)
+    if start_with_day is not None:
+        if start_with_day not in ordered:
+            raise ValueError(f"start_with_day {start_with_day!r} is not one of the days {ordered}")
+        k = ordered.index(start_with_day)
+        ordered = ordered[k:] + ordered[:k]
+    for k, test_day in enumerate(ordered):
+        yield ordered[:k] + ordered[k + 1:], test_day
+
+
+def join_corpora(corpora):
+    """Several corpora (one per recording file, mappings or objects as ``train_decoder`` takes them) as one: ``hga_activity``,
+    ``lpc_coefficients``, ``vad_labels`` (where every corpus has them) and ``trial_ids`` concatenated in the given order.
+
+    A trial border is a change of id, so two files that meet with equal ids would lose the border between them: where a file's
+    first id equals the last id of what has been joined before it, the whole file's ids are negated.  The borders inside the file
+    survive the sign flip, and |id| stays the stimulus code (the reference's ``_squeeze_trial_ids`` takes the absolute value too),
+    so ``trial_bounds`` of the result is the per-file bounds laid end to end.  A zero id at such a border cannot be negated and
+    raises ValueError, as do corpora whose column counts differ."""
+    import torch
+
+    def get(c, k):
+        try:
+            v = c[k]
+        except (KeyError, TypeError, IndexError):
+            v = getattr(c, k, None)
+        return None if v is None else (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v))
+
+    corpora = list(corpora)
+    if not corpora:
+        raise ValueError("join_corpora: no corpus given")
+    cols = {k: [get(c, k) for c in corpora] for k in ("hga_activity", "lpc_coefficients", "vad_labels", "trial_ids")}
+    if any(v is None for v in cols["hga_activity"] + cols["trial_ids"]):
+        raise ValueError("join_corpora: every corpus needs hga_activity and trial_ids")
+    out, ids, last = {}, [], None
+    for f, (x, t) in enumerate(zip(cols["hga_activity"], cols["trial_ids"])):
+        t = t.ravel()
+        if x.ndim != 2 or len(t) != x.shape[0]:
+            raise ValueError(f"join_corpora: corpus {f}: hga_activity must be (N, C) with N trial ids")
+        if x.shape[1] != cols["hga_activity"][0].shape[1]:
+            raise ValueError(f"join_corpora: corpus {f} has {x.shape[1]} columns of hga_activity, corpus 0 has {cols['hga_activity'][0].shape[1]}")
+        if len(t) and last is not None and t[0] == last:
+            if t[0] == 0:
+                raise ValueError(f"join_corpora: corpus {f} starts with the id 0 its predecessor ends with: the border cannot be kept")
+            t = -t
+        if len(t):
+            last = t[-1]
+        ids.append(t)
+    out["hga_activity"] = np.concatenate(cols["hga_activity"])
+    out["trial_ids"] = np.concatenate(ids)
+    for k in ("lpc_coefficients", "vad_labels"):
+        have = [v is not None for v in cols[k]]
+        if k == "lpc_coefficients" and any(have) and not all(have):
+            raise ValueError("join_corpora: some corpora have lpc_coefficients and some do not")
+        if not all(have):
+            continue
+        for f, v in enumerate(cols[k]):
+            if len(v) != len(cols["trial_ids"][f].ravel()):
+                raise ValueError(f"join_corpora: corpus {f}: {k} has {len(v)} rows for {len(cols['trial_ids'][f].ravel())} trial ids")
+            if v.ndim == 2 and v.shape[1] != cols[k][0].shape[1]:
+                raise ValueError(f"join_corpora: corpus {f} has {v.shape[1]} columns of {k}, corpus 0 has {cols[k][0].shape[1]}")
+        out[k] = np.concatenate(cols[k])
+    return out
+
+
 __all__ = ["VadTrainerGPU", "train_vad", "dropout_mask", "DecoderTrainerGPU", "train_decoder", "decoder_dropout_mask", "trial_bounds",
-           "LR", "ALPHA", "EPS"]
+           "DecoderGroupTrainerGPU", "train_decoders", "lockstep_schedule", "leave_one_day_out", "join_corpora", "LR", "ALPHA", "EPS"]

@@ -17,7 +17,8 @@
  * Parts 4-6 are the speech gate and the two recurrent models of the online path, Part 7 the acoustic labels of a
  * training corpus, Part 8 the two recurrent models over the trials of such a corpus (the validation passes of the
  * reference's training scripts), Part 9 the training of the neural detector, Part 10 that of the decoder, Part 11 the
- * spectrograms behind the reference's spectral analyses, each described at its declarations.
+ * spectrograms behind the reference's spectral analyses, Part 13 several decoders trained side by side, each described at its
+ * declarations.
  *
  * Error convention: functions returning int return 0 on success and a negative DSS_E* code on failure;
  * dss_last_error() gives a thread-local message.  Creators return NULL on failure (the reference's
@@ -749,6 +750,48 @@ int dss_contam_moments(dss_contam *h, const double *brain, long long n_rows, int
  * per handle may be in flight. */
 int dss_contam_moments_dev(dss_contam *h, const double *d_brain, long long n_rows, int ld, int C, const double *d_audio,
                            const unsigned char *keep_frames, double *d_out, void *hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Part 13 -- several decoders of Part 10 trained side by side: the folds of train_bidirectional_model.py:65-68 (one decoder per
+ * held-out day), seeds, learning rates.  Batch size 1 is a property of one training run; the runs are independent.  A group is
+ * n_models trainers of equal sizes, and a step is one trial for each of them in ONE set of Part 10's seven launches with a model
+ * axis on the grid (csrc/dec_train.hip), so the serial chains of all models run at the same time on different compute units.
+ * The arithmetic is Part 10's, shared term for term: after any sequence of steps, every model's loss, features, gradients,
+ * square averages, parameters and packed copies are bit for bit those of a dss_dec_trainer given the same weights and the same
+ * trials in the same order, whatever n_models is, wherever the model sits in the group and whatever the others do.
+ * 1 <= n_models <= 64: with 64 models every serial workgroup of a launch is resident at once on 256 compute units; more models
+ * are more groups.  Calls on one group are issued on one stream, or one after the other has finished.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct dss_dec_group dss_dec_group;
+/* One model's part of a step.  T == 0: the model sits the step out -- its parameters, square averages, gradients, packed copies,
+ * workspace, the features of its last trial and its loss slot all stay as they were, and its pointers are not looked at.
+ * Else Part 10's trial: device pointers d_frames (T, n_inputs), d_targets float32 (T, n_outputs), d_mask float32 (T, 2H) or NULL. */
+typedef struct {
+    const void *d_frames;
+    int T;
+    const float *d_targets;
+    const float *d_mask;
+    int apply_step;
+    double lr, alpha, eps;
+} dss_dec_group_trial;
+/* The argument checks on their own (no device needed): Part 10's limits on the sizes, and 1 <= n_models <= 64. */
+int dss_dec_group_check(int n_models, int n_inputs, int hidden_units, int n_outputs, int max_frames);
+/* n_models times Part 10's device memory, plus the tables. */
+dss_dec_group *dss_dec_group_create(int n_models, int n_inputs, int hidden_units, int n_outputs, int max_frames);
+void dss_dec_group_destroy(dss_dec_group *g);
+/* dss_dec_trainer_load / _read / _features / _publish for model m (0 <= m < n_models). */
+int dss_dec_group_load(dss_dec_group *g, int m, const float *const *w);
+int dss_dec_group_read(dss_dec_group *g, int m, int what, float *out);
+int dss_dec_group_features(dss_dec_group *g, int m, int T, float *out);
+int dss_dec_group_publish(dss_dec_group *g, int m, dss_dec *dec, void *hip_stream);
+/* One step: trials is a HOST array of n_models entries, read before the call returns; the frames of all models have one dtype
+ * (frames_are_f64).  d_losses is a device array of n_models float64; entry m is written only if trials[m].T > 0.  Seven launches
+ * on hip_stream with no host synchronisation: the entries travel in a ring of eight page-locked tables, copied in stream order,
+ * so steps may be enqueued back to back (the ninth step in flight waits for the first to finish).  DSS_EINVAL before any launch
+ * for a model with T > 0 that has no parameters loaded, T < 0 or T > max_frames, null frames or targets on a model with T > 0, or
+ * a call in which every T is 0. */
+int dss_dec_group_step_dev(dss_dec_group *g, const dss_dec_group_trial *trials, int frames_are_f64, double *d_losses,
+                           void *hip_stream);
 
 #ifdef __cplusplus
 }
