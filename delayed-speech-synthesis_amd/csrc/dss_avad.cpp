@@ -15,6 +15,7 @@ struct dss_avad {
     int device = 0;
     dss_avad_params p;
     DssAvadDev d;
+    DssDevBlocks blocks;
     double *d_win = nullptr, *d_tw = nullptr, *d_mel_w = nullptr;
     int *d_band_lo = nullptr, *d_band_off = nullptr;
     // per call (one call per handle in flight)
@@ -29,28 +30,6 @@ struct dss_avad {
     double *d_le_out = nullptr;          size_t le_out_cap = 0;
     double *d_thr = nullptr;             size_t thr_cap = 0;
 };
-
-template <typename T>
-static int avad_grow(T **p, size_t *cap, size_t need)
-{
-    if (need <= *cap) return DSS_OK;
-    if (*p) hipFree(*p);
-    *p = nullptr; *cap = 0;
-    const size_t n = need + need / 4 + 64;
-    DSS_HIP_CHECK(hipMalloc((void **)p, n * sizeof(T)));
-    *cap = n;
-    return DSS_OK;
-}
-
-template <typename T>
-static int avad_upload(const T *host, size_t count, T **out)
-{
-    T *d = nullptr;
-    DSS_HIP_CHECK(hipMalloc((void **)&d, count * sizeof(T) + 16));
-    DSS_HIP_CHECK(hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice));
-    *out = d;
-    return DSS_OK;
-}
 
 extern "C" int dss_avad_check_params(const dss_avad_params *p)
 {
@@ -141,9 +120,7 @@ extern "C" void dss_avad_destroy(dss_avad *h)
     if (!h) return;
     hipSetDevice(h->device);
     hipDeviceSynchronize();
-    for (void *q : {(void *)h->d_win, (void *)h->d_tw, (void *)h->d_mel_w, (void *)h->d_band_lo, (void *)h->d_band_off, (void *)h->d_desc,
-                    (void *)h->d_tiles, (void *)h->d_le, (void *)h->d_audio, (void *)h->d_labels, (void *)h->d_le_out, (void *)h->d_thr})
-        if (q) hipFree(q);
+    h->blocks.free_all();
     delete h;
 }
 
@@ -174,11 +151,11 @@ static int avad_setup(dss_avad *h, const double *window_fn, const double *mel)
     }
     off[p.n_bands] = (int)mel_w.size();
     if (mel_w.empty()) mel_w.push_back(0.0);
-    int rc = avad_upload(win.data(), win.size(), &h->d_win);
-    if (!rc) rc = avad_upload(tw.data(), tw.size(), &h->d_tw);
-    if (!rc) rc = avad_upload(mel_w.data(), mel_w.size(), &h->d_mel_w);
-    if (!rc) rc = avad_upload(lo.data(), lo.size(), &h->d_band_lo);
-    if (!rc) rc = avad_upload(off.data(), off.size(), &h->d_band_off);
+    int rc = h->blocks.upload(win.data(), win.size(), &h->d_win);
+    if (!rc) rc = h->blocks.upload(tw.data(), tw.size(), &h->d_tw);
+    if (!rc) rc = h->blocks.upload(mel_w.data(), mel_w.size(), &h->d_mel_w);
+    if (!rc) rc = h->blocks.upload(lo.data(), lo.size(), &h->d_band_lo);
+    if (!rc) rc = h->blocks.upload(off.data(), off.size(), &h->d_band_off);
     if (rc) return rc;
     DssAvadDev &d = h->d;
     d.N = N; d.shift = p.shift; d.bins = p.n_bins; d.bands = p.n_bands; d.context = p.frames_context;
@@ -205,9 +182,7 @@ static int avad_run(dss_avad *h, const short *d_audio, long long audio_base, int
 {
     const int N = h->p.window, shift = h->p.shift;
     // descriptor table, longest trial first: the long trials' tiles start first and the short ones fill the tail
-    std::vector<int> order((size_t)n_trials);
-    for (int i = 0; i < n_trials; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return len[a] > len[b]; });
+    const std::vector<int> order = trials_longest_first(n_trials, len);
     std::vector<long long> out_frame((size_t)n_trials);
     long long total = 0;
     for (int i = 0; i < n_trials; ++i) { out_frame[i] = total; total += (len[i] - N) / shift + 1; }
@@ -221,9 +196,9 @@ static int avad_run(dss_avad *h, const short *d_audio, long long audio_base, int
         for (int f0 = 0; f0 < t.W; f0 += AVAD_TILE_FRAMES) h->tiles.push_back(DssAvadTile{k, f0});
     }
     if (h->tiles.size() > 0x7fffffffULL) { dss_set_error("acoustic VAD: too many tiles for one launch"); return DSS_EINVAL; }
-    int rc = avad_grow(&h->d_desc, &h->desc_cap, h->desc.size());
-    if (!rc) rc = avad_grow(&h->d_tiles, &h->tiles_cap, h->tiles.size());
-    if (!rc && !d_le) { rc = avad_grow(&h->d_le, &h->le_cap, (size_t)total); d_le = h->d_le; }
+    int rc = h->blocks.grow_headroom(&h->d_desc, &h->desc_cap, h->desc.size());
+    if (!rc) rc = h->blocks.grow_headroom(&h->d_tiles, &h->tiles_cap, h->tiles.size());
+    if (!rc && !d_le) { rc = h->blocks.grow_headroom(&h->d_le, &h->le_cap, (size_t)total); d_le = h->d_le; }
     if (rc) return rc;
     DSS_HIP_CHECK(hipMemcpyAsync(h->d_desc, h->desc.data(), sizeof(DssAvadTrialDesc) * h->desc.size(), hipMemcpyHostToDevice, st));
     DSS_HIP_CHECK(hipMemcpyAsync(h->d_tiles, h->tiles.data(), sizeof(DssAvadTile) * h->tiles.size(), hipMemcpyHostToDevice, st));
@@ -254,15 +229,12 @@ extern "C" int dss_avad_labels_trials(dss_avad *h, const int16_t *audio, long lo
     if (!audio || !labels) { dss_set_error("bad arguments"); return DSS_EINVAL; }
     DSS_HIP_CHECK(hipSetDevice(h->device));
     // only the samples the trials span cross the bus, once, however the trials overlap
-    long long lo = first[0], hi = first[0] + (len[0] - lead[0]);
-    for (int i = 1; i < n_trials; ++i) {
-        lo = std::min(lo, first[i]);
-        hi = std::max(hi, first[i] + (long long)(len[i] - lead[i]));
-    }
-    int rc = avad_grow(&h->d_audio, &h->audio_cap, (size_t)(hi - lo) + 1);
-    if (!rc) rc = avad_grow(&h->d_labels, &h->labels_cap, (size_t)total);
-    if (!rc) rc = avad_grow(&h->d_le_out, &h->le_out_cap, (size_t)total);
-    if (!rc) rc = avad_grow(&h->d_thr, &h->thr_cap, (size_t)n_trials);
+    long long lo, hi;
+    trials_hull(n_trials, first, len, lead, &lo, &hi);
+    int rc = h->blocks.grow_headroom(&h->d_audio, &h->audio_cap, (size_t)(hi - lo) + 1);
+    if (!rc) rc = h->blocks.grow_headroom(&h->d_labels, &h->labels_cap, (size_t)total);
+    if (!rc) rc = h->blocks.grow_headroom(&h->d_le_out, &h->le_out_cap, (size_t)total);
+    if (!rc) rc = h->blocks.grow_headroom(&h->d_thr, &h->thr_cap, (size_t)n_trials);
     if (rc) return rc;
     if (hi > lo) DSS_HIP_CHECK(hipMemcpy(h->d_audio, audio + lo, sizeof(short) * (size_t)(hi - lo), hipMemcpyHostToDevice));
     rc = avad_run(h, h->d_audio, lo, n_trials, first, len, lead, silence, h->d_labels, h->d_le_out, h->d_thr, nullptr);

@@ -18,6 +18,7 @@ struct dss_contam {
     int device = 0;
     dss_contam_params p;
     DssContamDev v;
+    DssDevBlocks blocks;
     double *d_win = nullptr, *d_tw = nullptr, *d_shift = nullptr;
     // per call (one call per handle in flight)
     std::vector<unsigned char> keep;
@@ -29,18 +30,6 @@ struct dss_contam {
     double *d_audio = nullptr;       size_t audio_cap = 0;
     double *d_out = nullptr;         size_t out_cap = 0;
 };
-
-template <typename T>
-static int contam_grow(T **p, size_t *cap, size_t need)
-{
-    if (need <= *cap) return DSS_OK;
-    if (*p) hipFree(*p);
-    *p = nullptr; *cap = 0;
-    const size_t n = need + need / 4 + 64;
-    DSS_HIP_CHECK(hipMalloc((void **)p, n * sizeof(T)));
-    *cap = n;
-    return DSS_OK;
-}
 
 extern "C" int dss_contam_check_params(const dss_contam_params *p)
 {
@@ -129,9 +118,7 @@ extern "C" void dss_contam_destroy(dss_contam *h)
     if (!h) return;
     hipSetDevice(h->device);
     hipDeviceSynchronize();
-    for (void *q : {(void *)h->d_win, (void *)h->d_tw, (void *)h->d_shift, (void *)h->d_keep, (void *)h->d_aud, (void *)h->d_partial,
-                    (void *)h->d_x, (void *)h->d_audio, (void *)h->d_out})
-        if (q) hipFree(q);
+    h->blocks.free_all();
     delete h;
 }
 
@@ -147,9 +134,10 @@ static int contam_setup(dss_contam *h, const double *window)
         tw[2 * j] = cos(a);
         tw[2 * j + 1] = sin(a);
     }
-    DSS_HIP_CHECK(hipMalloc((void **)&h->d_win, win.size() * sizeof(double)));
-    DSS_HIP_CHECK(hipMalloc((void **)&h->d_tw, tw.size() * sizeof(double)));
-    DSS_HIP_CHECK(hipMalloc((void **)&h->d_shift, CONTAM_PAD * sizeof(double)));
+    int rc = h->blocks.alloc_bytes(win.size() * sizeof(double), (void **)&h->d_win);
+    if (!rc) rc = h->blocks.alloc_bytes(tw.size() * sizeof(double), (void **)&h->d_tw);
+    if (!rc) rc = h->blocks.alloc_bytes(CONTAM_PAD * sizeof(double), (void **)&h->d_shift);
+    if (rc) return rc;
     DSS_HIP_CHECK(hipMemcpy(h->d_win, win.data(), win.size() * sizeof(double), hipMemcpyHostToDevice));
     DSS_HIP_CHECK(hipMemcpy(h->d_tw, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice));
     h->v.spec.win = h->d_win; h->v.spec.tw = h->d_tw;
@@ -188,9 +176,9 @@ static int contam_run(dss_contam *h, const double *d_x, int ld, int C, const dou
     int chunks = (int)std::max(1LL, std::min((long long)n_tiles, (512 + per_chunk - 1) / per_chunk));
     const int tiles_per_chunk = (n_tiles + chunks - 1) / chunks;
     chunks = (n_tiles + tiles_per_chunk - 1) / tiles_per_chunk;
-    int rc = contam_grow(&h->d_keep, &h->keep_cap, (size_t)W);
-    if (!rc) rc = contam_grow(&h->d_aud, &h->aud_cap, (size_t)W * CONTAM_PAD);
-    if (!rc) rc = contam_grow(&h->d_partial, &h->partial_cap, (size_t)chunks * v.nlag * C * contam_record(v.B));
+    int rc = h->blocks.grow_headroom(&h->d_keep, &h->keep_cap, (size_t)W);
+    if (!rc) rc = h->blocks.grow_headroom(&h->d_aud, &h->aud_cap, (size_t)W * CONTAM_PAD);
+    if (!rc) rc = h->blocks.grow_headroom(&h->d_partial, &h->partial_cap, (size_t)chunks * v.nlag * C * contam_record(v.B));
     if (rc) return rc;
     DSS_HIP_CHECK(hipMemcpyAsync(h->d_keep, h->keep.data(), (size_t)W, hipMemcpyHostToDevice, st));
     return dss_launch_contam(v, d_x, ld, C, d_audio, T, W, h->d_keep, h->d_aud, h->d_shift, h->d_partial, chunks, tiles_per_chunk, d_out, st);
@@ -215,9 +203,9 @@ extern "C" int dss_contam_moments(dss_contam *h, const double *brain, long long 
     DSS_HIP_CHECK(hipSetDevice(h->device));
     long long off[8];
     dss_contam_layout(h->v, C, off);
-    int rc = contam_grow(&h->d_x, &h->x_cap, (size_t)n_rows * ld + 1);
-    if (!rc) rc = contam_grow(&h->d_audio, &h->audio_cap, (size_t)n_rows);
-    if (!rc) rc = contam_grow(&h->d_out, &h->out_cap, (size_t)off[7]);
+    int rc = h->blocks.grow_headroom(&h->d_x, &h->x_cap, (size_t)n_rows * ld + 1);
+    if (!rc) rc = h->blocks.grow_headroom(&h->d_audio, &h->audio_cap, (size_t)n_rows);
+    if (!rc) rc = h->blocks.grow_headroom(&h->d_out, &h->out_cap, (size_t)off[7]);
     if (rc) return rc;
     // the last row ends behind its C channels: the caller's array may be a view that ends there
     DSS_HIP_CHECK(hipMemcpy(h->d_x, brain, sizeof(double) * ((size_t)(n_rows - 1) * ld + C), hipMemcpyHostToDevice));

@@ -14,6 +14,7 @@ struct dss_dec_group {
     std::vector<dss_dec_trainer *> tr;
     DssDecTrainDev *d_models = nullptr;                   // [M]
     DssDecGroupTrial *d_trials[DssPinnedRing::K] = {};    // [K][M]
+    DssDevBlocks blocks;                                  // the two kinds of table; a member's memory is the member's
     DssPinnedRing ring;
     bool ring_ok = false;
 };
@@ -34,9 +35,8 @@ extern "C" void dss_dec_group_destroy(dss_dec_group *g)
     if (!g) return;
     hipSetDevice(g->device);
     hipDeviceSynchronize();
+    g->blocks.free_all();
     if (g->ring_ok) g->ring.destroy();
-    for (int k = 0; k < DssPinnedRing::K; ++k) if (g->d_trials[k]) hipFree(g->d_trials[k]);
-    if (g->d_models) hipFree(g->d_models);
     for (dss_dec_trainer *t : g->tr) dss_dec_trainer_destroy(t);
     delete g;
 }
@@ -57,10 +57,10 @@ extern "C" dss_dec_group *dss_dec_group_create(int n_models, int n_inputs, int h
         dss_dec_trainer_view(t, &table[m], &device, &loaded);
     }
     const size_t tb = (size_t)n_models * sizeof(DssDecGroupTrial);
-    bool ok = hipMalloc((void **)&g->d_models, table.size() * sizeof(DssDecTrainDev)) == hipSuccess &&
+    bool ok = g->blocks.alloc_bytes(table.size() * sizeof(DssDecTrainDev), (void **)&g->d_models) == DSS_OK &&
               hipMemcpy(g->d_models, table.data(), table.size() * sizeof(DssDecTrainDev), hipMemcpyHostToDevice) == hipSuccess;
     for (int k = 0; ok && k < DssPinnedRing::K; ++k)
-        ok = hipMalloc((void **)&g->d_trials[k], tb) == hipSuccess && hipMemset(g->d_trials[k], 0, tb) == hipSuccess;
+        ok = g->blocks.alloc_bytes(tb, (void **)&g->d_trials[k]) == DSS_OK && hipMemset(g->d_trials[k], 0, tb) == hipSuccess;
     g->ring_ok = true;
     if (ok) ok = g->ring.init((tb + sizeof(int) - 1) / sizeof(int)) == DSS_OK;
     if (!ok) {

@@ -11,7 +11,7 @@ struct dss_dec_trainer {
     long np = 0;                       // elements of the flat parameter array
     size_t n_wT[2] = {0, 0};           // elements of a packed copy, per layer
     DssDecTrainDev d;
-    std::vector<void *> blocks;        // every device allocation of the handle
+    DssDevBlocks blocks;               // every device allocation of the handle
     bool loaded = false;
 };
 
@@ -51,23 +51,12 @@ extern "C" long dss_dec_trainer_param_count(int n_inputs, int hidden_units, int 
     return dss_dec_train_param_count(n_inputs, hidden_units, n_outputs);
 }
 
-template <typename T>
-static int tr_alloc(dss_dec_trainer *tr, size_t count, T **out)
-{
-    void *p = nullptr;
-    DSS_HIP_CHECK(hipMalloc(&p, count * sizeof(T) + 16));
-    tr->blocks.push_back(p);
-    DSS_HIP_CHECK(hipMemset(p, 0, count * sizeof(T)));
-    *out = (T *)p;
-    return DSS_OK;
-}
-
 extern "C" void dss_dec_trainer_destroy(dss_dec_trainer *tr)
 {
     if (!tr) return;
     hipSetDevice(tr->device);
     hipDeviceSynchronize();
-    for (void *p : tr->blocks) hipFree(p);
+    tr->blocks.free_all();
     delete tr;
 }
 
@@ -86,16 +75,16 @@ extern "C" dss_dec_trainer *dss_dec_trainer_create(int n_inputs, int hidden_unit
     DssDecTrainDev &d = tr->d;
     memset(&d, 0, sizeof(d));
     d.C = C; d.H = H; d.O = O; d.Tmax = max_frames;
-    int rc = tr_alloc(tr, (size_t)tr->np, &d.p) | tr_alloc(tr, (size_t)tr->np, &d.g) | tr_alloc(tr, (size_t)tr->np, &d.sq);
+    int rc = tr->blocks.alloc((size_t)tr->np, &d.p) | tr->blocks.alloc((size_t)tr->np, &d.g) | tr->blocks.alloc((size_t)tr->np, &d.sq);
     for (int L = 0; L < 2; ++L)
         for (int dir = 0; dir < 2; ++dir) {
-            rc |= tr_alloc(tr, tr->n_wT[L], &d.wT[L][dir]) | tr_alloc(tr, (size_t)H4, &d.b[L][dir]);
-            rc |= tr_alloc(tr, Tm * H4, &d.act[L][dir]) | tr_alloc(tr, (Tm + 1) * H, &d.c[L][dir]) | tr_alloc(tr, (Tm + 1) * H, &d.h[L][dir]);
-            rc |= tr_alloc(tr, Tm * H4, &d.dg[L][dir]);
+            rc |= tr->blocks.alloc(tr->n_wT[L], &d.wT[L][dir]) | tr->blocks.alloc((size_t)H4, &d.b[L][dir]);
+            rc |= tr->blocks.alloc(Tm * H4, &d.act[L][dir]) | tr->blocks.alloc((Tm + 1) * H, &d.c[L][dir]) | tr->blocks.alloc((Tm + 1) * H, &d.h[L][dir]);
+            rc |= tr->blocks.alloc(Tm * H4, &d.dg[L][dir]);
         }
-    rc |= tr_alloc(tr, Tm * C, &d.xs) | tr_alloc(tr, Tm * 2 * H, &d.midm) | tr_alloc(tr, Tm * 2 * H, &d.top);
-    rc |= tr_alloc(tr, Tm * O, &d.feat) | tr_alloc(tr, Tm * O, &d.dfeat) | tr_alloc(tr, Tm, &d.lossf);
-    rc |= tr_alloc(tr, Tm * 2 * H, &d.dtop) | tr_alloc(tr, Tm * 2 * H, &d.dmid);
+    rc |= tr->blocks.alloc(Tm * C, &d.xs) | tr->blocks.alloc(Tm * 2 * H, &d.midm) | tr->blocks.alloc(Tm * 2 * H, &d.top);
+    rc |= tr->blocks.alloc(Tm * O, &d.feat) | tr->blocks.alloc(Tm * O, &d.dfeat) | tr->blocks.alloc(Tm, &d.lossf);
+    rc |= tr->blocks.alloc(Tm * 2 * H, &d.dtop) | tr->blocks.alloc(Tm * 2 * H, &d.dmid);
     if (rc) {
         dss_set_error("device allocation failed for the decoder's trainer (%d inputs, %d hidden units, %d outputs, max_frames %d)", C, H, O,
                       max_frames);

@@ -1,0 +1,63 @@
+// csrc/dss_host.cpp -- what dss_host.h declares and no single operator owns: the owner of device memory, and trial lists.
+#include <algorithm>
+
+#include "dss_host.h"
+
+int DssDevBlocks::alloc_bytes(size_t bytes, void **p)
+{
+    void *d = nullptr;
+    DSS_HIP_CHECK(hipMalloc(&d, bytes));
+    blocks.push_back(d);
+    *p = d;
+    return DSS_OK;
+}
+
+void DssDevBlocks::release(const void *p)
+{
+    auto it = std::find(blocks.begin(), blocks.end(), p);
+    if (!p || it == blocks.end()) return;
+    blocks.erase(it);
+    hipFree(const_cast<void *>(p));
+}
+
+void DssDevBlocks::free_all()
+{
+    for (void *p : blocks) hipFree(p);
+    blocks.clear();
+}
+
+extern "C" int dss_trials_check(long long N, int n_trials, const long long *first, const int *len, long long *total)
+{
+    if (!first || !len || !total) { dss_set_error("trial list: null argument"); return DSS_EINVAL; }
+    if (n_trials < 0 || N < 0) { dss_set_error("trial list: negative count"); return DSS_EINVAL; }
+    long long sum = 0;
+    for (int i = 0; i < n_trials; ++i) {
+        if (len[i] < 1) { dss_set_error("trial %d: %d frames (at least 1)", i, len[i]); return DSS_EINVAL; }
+        if (first[i] < 0) { dss_set_error("trial %d: first row %lld is negative", i, first[i]); return DSS_EINVAL; }
+        if (first[i] > N - len[i]) {
+            dss_set_error("trial %d: rows %lld .. %lld end behind the %lld rows of the array", i, first[i], first[i] + len[i], N);
+            return DSS_EINVAL;
+        }
+        sum += len[i];
+    }
+    *total = sum;
+    return DSS_OK;
+}
+
+// list positions, longest trial first (ties in list order): the long trials start first, the short ones fill the tail
+std::vector<int> trials_longest_first(int n_trials, const int *len)
+{
+    std::vector<int> order((size_t)n_trials);
+    for (int i = 0; i < n_trials; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return len[a] > len[b]; });
+    return order;
+}
+
+void trials_hull(int n_trials, const long long *first, const int *len, const int *lead, long long *lo, long long *hi)
+{
+    *lo = first[0]; *hi = first[0] + (len[0] - (lead ? lead[0] : 0));
+    for (int i = 1; i < n_trials; ++i) {
+        *lo = std::min(*lo, first[i]);
+        *hi = std::max(*hi, first[i] + (long long)(len[i] - (lead ? lead[i] : 0)));
+    }
+}

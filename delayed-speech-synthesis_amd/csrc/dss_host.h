@@ -1,10 +1,105 @@
-// csrc/dss_host.h -- host-side helpers shared by the C ABI's translation units (dss_capi.cpp, dss_async.cpp).
+// csrc/dss_host.h -- host-side helpers shared by the C ABI's translation units (one dss_*.cpp per operator).
 #pragma once
+
+#include <algorithm>
+#include <vector>
 
 #include "dss_common.h"
 
+// What crosses from one host file to another without being part of the library's interface stays out of its symbol table.
+#define DSS_LOCAL __attribute__((visibility("hidden")))
+
 // Selects (and on first use picks: LOCAL_RANK, else 0) this thread's device; DSS_ENODEV without one.
 int dss_ensure_device(void);
+
+// The loaded LPCNet model (dss_lpcnet_model.cpp) and its copy on the calling thread's device.  With acquire set the caller owns
+// one reference from then on (release_model()); a superseded model dies with its last user.
+struct HostModel;
+DSS_LOCAL int get_model(HostModel **out_hm, const DssModelDev **out, bool acquire);
+DSS_LOCAL void release_model(HostModel *hm);
+
+// Trial lists (Part 8; the acoustic VAD's tables): list positions, longest trial first (ties in list order): the long trials start
+// first, the short ones fill the tail.
+DSS_LOCAL std::vector<int> trials_longest_first(int n_trials, const int *len);
+
+// the chunks of a reduction over a trial list: DSS_TRIAL_CHUNK trials per launch, their lengths as kernel arguments
+template <typename F>
+static int trials_reduce(const char *what, int n_trials, const int *len, F launch)
+{
+    if (n_trials < 0 || (n_trials && !len)) { dss_set_error("%s: bad trial list", what); return DSS_EINVAL; }
+    for (int i = 0; i < n_trials; ++i)
+        if (len[i] < 1) { dss_set_error("%s: trial %d has %d frames (at least 1)", what, i, len[i]); return DSS_EINVAL; }
+    if (dss_ensure_device()) return DSS_ENODEV;
+    DssTrialLens tl;
+    long long base = 0;
+    for (int i0 = 0; i0 < n_trials; i0 += DSS_TRIAL_CHUNK) {
+        tl.base = base; tl.first_trial = i0; tl.n = std::min(DSS_TRIAL_CHUNK, n_trials - i0);
+        memset(tl.len, 0, sizeof(tl.len));
+        for (int k = 0; k < tl.n; ++k) { tl.len[k] = len[i0 + k]; base += len[i0 + k]; }
+        int rc = launch(tl);
+        if (rc) return rc;
+    }
+    return DSS_OK;
+}
+
+static inline size_t dss_headroom(size_t need) { return need + need / 4 + 64; }
+
+// One owner for the device memory of a handle (and of the model, per device).  Every block allocated through it is remembered
+// and freed by free_all(), with the owner's device selected; the device descriptors that kernels take by value keep raw pointers.
+struct DSS_LOCAL DssDevBlocks {
+    std::vector<void *> blocks;
+
+    int alloc_bytes(size_t bytes, void **p);        // exactly `bytes`, as they come
+    void release(const void *p);        // frees one block early and forgets it (NULL: nothing)
+    void free_all();                    // copes with whatever a create path that failed halfway had allocated so far
+
+    // count elements, zeroed, and 16 spare bytes behind them: several kernels read a full vector at the tail
+    template <typename T>
+    int alloc(size_t count, T **p)
+    {
+        void *d = nullptr;
+        int rc = alloc_bytes(count * sizeof(T) + 16, &d);
+        if (rc) return rc;
+        DSS_HIP_CHECK(hipMemset(d, 0, count * sizeof(T)));
+        *p = (T *)d;
+        return DSS_OK;
+    }
+    // the same block filled from the host, with a blocking copy
+    template <typename T>
+    int upload(const T *host, size_t count, T **p)
+    {
+        void *d = nullptr;
+        int rc = alloc_bytes(count * sizeof(T) + 16, &d);
+        if (rc) return rc;
+        DSS_HIP_CHECK(hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice));
+        *p = (T *)d;
+        return DSS_OK;
+    }
+    // A device array that only grows: nothing when need <= *cap, else the old block is freed (hipFree waits for the device, so
+    // the buffer of a call still queued is not freed under it) and exactly `need` elements are allocated.  No spare bytes, not
+    // zeroed, contents not kept.
+    template <typename T>
+    int grow(T **p, size_t *cap, size_t need) { return need <= *cap ? DSS_OK : regrow(p, cap, need); }
+    // the same with dss_headroom(need) elements allocated, so that a slightly longer list next time does not allocate again
+    template <typename T>
+    int grow_headroom(T **p, size_t *cap, size_t need) { return need <= *cap ? DSS_OK : regrow(p, cap, dss_headroom(need)); }
+
+    template <typename T>
+    int regrow(T **p, size_t *cap, size_t count)
+    {
+        release(*p);
+        *p = nullptr; *cap = 0;
+        void *d = nullptr;
+        int rc = alloc_bytes(count * sizeof(T), &d);
+        if (rc) return rc;
+        *p = (T *)d;
+        *cap = count;
+        return DSS_OK;
+    }
+};
+
+// first and one-past-last row that a trial list covers: trial i spans first[i] .. first[i] + len[i] - lead[i] (lead may be NULL)
+DSS_LOCAL void trials_hull(int n_trials, const long long *first, const int *len, const int *lead, long long *lo, long long *hi);
 
 // The device view of `bytes` at p, which must lie inside one block from dss_host_alloc_fine and be `align`-byte aligned;
 // DSS_EINVAL with a message otherwise (pageable or cached page-locked memory, a short block, misalignment).

@@ -15,6 +15,7 @@ struct dss_spec {
     int device = 0;
     dss_spec_params p;
     DssSpecDev d;
+    DssDevBlocks blocks;
     double *d_win = nullptr, *d_tw = nullptr;
     // per call (one call per handle in flight)
     std::vector<DssSpecTrial> desc;
@@ -26,18 +27,6 @@ struct dss_spec {
     double *d_x = nullptr;           size_t x_cap = 0;
     double *d_out = nullptr;         size_t out_cap = 0;
 };
-
-template <typename T>
-static int spec_grow(T **p, size_t *cap, size_t need)
-{
-    if (need <= *cap) return DSS_OK;
-    if (*p) hipFree(*p);
-    *p = nullptr; *cap = 0;
-    const size_t n = need + need / 4 + 64;
-    DSS_HIP_CHECK(hipMalloc((void **)p, n * sizeof(T)));
-    *cap = n;
-    return DSS_OK;
-}
 
 static int spec_frame_shape(int nperseg, int hop)
 {
@@ -115,8 +104,7 @@ extern "C" void dss_spec_destroy(dss_spec *h)
     if (!h) return;
     hipSetDevice(h->device);
     hipDeviceSynchronize();
-    for (void *q : {(void *)h->d_win, (void *)h->d_tw, (void *)h->d_desc, (void *)h->d_tiles, (void *)h->d_partial, (void *)h->d_x, (void *)h->d_out})
-        if (q) hipFree(q);
+    h->blocks.free_all();
     delete h;
 }
 
@@ -162,8 +150,9 @@ static int spec_setup(dss_spec *h, const double *window)
         tw[2 * j] = cos(a);
         tw[2 * j + 1] = sin(a);
     }
-    DSS_HIP_CHECK(hipMalloc((void **)&h->d_win, win.size() * sizeof(double)));
-    DSS_HIP_CHECK(hipMalloc((void **)&h->d_tw, tw.size() * sizeof(double)));
+    int rc = h->blocks.alloc_bytes(win.size() * sizeof(double), (void **)&h->d_win);
+    if (!rc) rc = h->blocks.alloc_bytes(tw.size() * sizeof(double), (void **)&h->d_tw);
+    if (rc) return rc;
     DSS_HIP_CHECK(hipMemcpy(h->d_win, win.data(), win.size() * sizeof(double), hipMemcpyHostToDevice));
     DSS_HIP_CHECK(hipMemcpy(h->d_tw, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice));
     DssSpecDev &d = h->d;
@@ -195,7 +184,7 @@ static int spec_check_layout(const dss_spec *h, int ld, int C)
 
 static int spec_upload_desc(dss_spec *h, hipStream_t st)
 {
-    int rc = spec_grow(&h->d_desc, &h->desc_cap, h->desc.size());
+    int rc = h->blocks.grow_headroom(&h->d_desc, &h->desc_cap, h->desc.size());
     if (rc) return rc;
     DSS_HIP_CHECK(hipMemcpyAsync(h->d_desc, h->desc.data(), sizeof(DssSpecTrial) * h->desc.size(), hipMemcpyHostToDevice, st));
     return DSS_OK;
@@ -225,7 +214,7 @@ static long long spec_run_trials(dss_spec *h, const double *d_x, long long row_b
     }
     if (h->tiles.size() > 0x7fffffffULL) { dss_set_error("spectrogram: too many tiles for one launch"); return DSS_EINVAL; }
     int rc = spec_upload_desc(h, st);
-    if (!rc) rc = spec_grow(&h->d_tiles, &h->tiles_cap, h->tiles.size());
+    if (!rc) rc = h->blocks.grow_headroom(&h->d_tiles, &h->tiles_cap, h->tiles.size());
     if (rc) return rc;
     DSS_HIP_CHECK(hipMemcpyAsync(h->d_tiles, h->tiles.data(), sizeof(DssSpecTile) * h->tiles.size(), hipMemcpyHostToDevice, st));
     rc = dss_launch_spec_trials(h->d, g, d_x, ld, C, h->d_desc, h->d_tiles, (int)h->tiles.size(), d_out, st);
@@ -264,7 +253,7 @@ static int spec_run_mean(dss_spec *h, const double *d_x, long long row_base, int
         t.first = first[i] - row_base; t.n = length[i]; t.out = i; t.W = (int)((length[i] - h->p.nperseg) / h->p.hop + 1); t.frame0 = 0;
     }
     int rc = spec_upload_desc(h, st);
-    if (!rc) rc = spec_grow(&h->d_partial, &h->partial_cap, (size_t)n_trials * C * h->d.bins);
+    if (!rc) rc = h->blocks.grow_headroom(&h->d_partial, &h->partial_cap, (size_t)n_trials * C * h->d.bins);
     if (!rc) rc = dss_launch_spec_mean(h->d, g, d_x, ld, C, h->d_desc, n_trials, total, h->d_partial, d_out, st);
     return rc;
 }
@@ -278,7 +267,7 @@ static int spec_stage_rows(dss_spec *h, const double *x, int ld, int C, int n_tr
         lo = std::min(lo, first[i]);
         hi = std::max(hi, first[i] + length[i]);
     }
-    int rc = spec_grow(&h->d_x, &h->x_cap, (size_t)(hi - lo) * ld + 1);
+    int rc = h->blocks.grow_headroom(&h->d_x, &h->x_cap, (size_t)(hi - lo) * ld + 1);
     if (rc) return rc;
     // the last row ends behind its C channels: the caller's array may be a view that ends there
     if (hi > lo) DSS_HIP_CHECK(hipMemcpy(h->d_x, x + lo * ld, sizeof(double) * ((size_t)(hi - lo - 1) * ld + C), hipMemcpyHostToDevice));
@@ -315,7 +304,7 @@ extern "C" long long dss_spec_trials(dss_spec *h, const double *x, long long n_r
     long long base = 0;
     const size_t count = (size_t)total * C * h->d.bins;
     int rc = spec_stage_rows(h, x, ld, C, n_trials, first, length, &base);
-    if (!rc) rc = spec_grow(&h->d_out, &h->out_cap, count);
+    if (!rc) rc = h->blocks.grow_headroom(&h->d_out, &h->out_cap, count);
     if (rc) return rc;
     const long long got = spec_run_trials(h, h->d_x, base, ld, C, n_trials, first, length, h->d_out, nullptr);
     if (got < 0) return got;
@@ -347,7 +336,7 @@ extern "C" int dss_spec_locked(dss_spec *h, const double *x, long long n_rows, i
     long long base = 0;
     const size_t count = (size_t)C * h->d.bins * J;
     int rc = spec_stage_rows(h, x, ld, C, n_trials, first, length, &base);
-    if (!rc) rc = spec_grow(&h->d_out, &h->out_cap, count);
+    if (!rc) rc = h->blocks.grow_headroom(&h->d_out, &h->out_cap, count);
     if (!rc) rc = spec_run_locked(h, h->d_x, base, ld, C, n_trials, first, length, onset, pre, post, h->d_out, nullptr);
     if (rc < 0) return rc;
     rc = spec_fetch(h, out, count);
@@ -378,7 +367,7 @@ extern "C" int dss_spec_mean(dss_spec *h, const double *x, long long n_rows, int
     long long base = 0;
     const size_t count = (size_t)C * h->d.bins;
     int rc = spec_stage_rows(h, x, ld, C, n_trials, first, length, &base);
-    if (!rc) rc = spec_grow(&h->d_out, &h->out_cap, count);
+    if (!rc) rc = h->blocks.grow_headroom(&h->d_out, &h->out_cap, count);
     if (!rc) rc = spec_run_mean(h, h->d_x, base, ld, C, n_trials, first, length, total, h->d_out, nullptr);
     if (rc) return rc;
     return spec_fetch(h, out, count);

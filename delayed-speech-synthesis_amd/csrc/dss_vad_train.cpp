@@ -11,7 +11,7 @@ struct dss_vad_trainer {
     long np = 0;                       // elements of the flat parameter array
     size_t n_wT0 = 0, n_wT1 = 0;       // elements of the packed copies
     DssVadTrainDev d;
-    std::vector<void *> blocks;        // every device allocation of the handle
+    DssDevBlocks blocks;               // every device allocation of the handle
     bool loaded = false;
 };
 
@@ -48,23 +48,12 @@ extern "C" int dss_vad_trainer_check(int n_inputs, int hidden_units, int max_win
     return DSS_OK;
 }
 
-template <typename T>
-static int tr_alloc(dss_vad_trainer *tr, size_t count, T **out)
-{
-    void *p = nullptr;
-    DSS_HIP_CHECK(hipMalloc(&p, count * sizeof(T) + 16));
-    tr->blocks.push_back(p);
-    DSS_HIP_CHECK(hipMemset(p, 0, count * sizeof(T)));
-    *out = (T *)p;
-    return DSS_OK;
-}
-
 extern "C" void dss_vad_trainer_destroy(dss_vad_trainer *tr)
 {
     if (!tr) return;
     hipSetDevice(tr->device);
     hipDeviceSynchronize();
-    for (void *p : tr->blocks) hipFree(p);
+    tr->blocks.free_all();
     delete tr;
 }
 
@@ -83,13 +72,13 @@ extern "C" dss_vad_trainer *dss_vad_trainer_create(int n_inputs, int hidden_unit
     DssVadTrainDev &d = tr->d;
     memset(&d, 0, sizeof(d));
     d.v.S = 1; d.v.C = C; d.v.H = H; d.Tmax = max_window;
-    int rc = tr_alloc(tr, (size_t)tr->np, &d.p) | tr_alloc(tr, (size_t)tr->np, &d.g) | tr_alloc(tr, (size_t)tr->np, &d.sq);
-    rc |= tr_alloc(tr, tr->n_wT0, &d.wT0) | tr_alloc(tr, (size_t)H4, &d.b0) | tr_alloc(tr, tr->n_wT1, &d.wT1) | tr_alloc(tr, (size_t)H4, &d.b1);
-    rc |= tr_alloc(tr, (size_t)2 * H, &d.v.h) | tr_alloc(tr, (size_t)2 * H, &d.v.c);
-    rc |= tr_alloc(tr, Tm * C, &d.xs) | tr_alloc(tr, Tm * H4, &d.act0) | tr_alloc(tr, Tm * H4, &d.act1);
-    rc |= tr_alloc(tr, (Tm + 1) * H, &d.c0) | tr_alloc(tr, (Tm + 1) * H, &d.c1) | tr_alloc(tr, (Tm + 1) * H, &d.h0) | tr_alloc(tr, (Tm + 1) * H, &d.h1);
-    rc |= tr_alloc(tr, Tm * H, &d.h0m) | tr_alloc(tr, Tm * 2, &d.logit) | tr_alloc(tr, Tm * 2, &d.dl) | tr_alloc(tr, Tm, &d.lossf);
-    rc |= tr_alloc(tr, Tm * H4, &d.dg0) | tr_alloc(tr, Tm * H4, &d.dg1) | tr_alloc(tr, Tm * H, &d.dh0m);
+    int rc = tr->blocks.alloc((size_t)tr->np, &d.p) | tr->blocks.alloc((size_t)tr->np, &d.g) | tr->blocks.alloc((size_t)tr->np, &d.sq);
+    rc |= tr->blocks.alloc(tr->n_wT0, &d.wT0) | tr->blocks.alloc((size_t)H4, &d.b0) | tr->blocks.alloc(tr->n_wT1, &d.wT1) | tr->blocks.alloc((size_t)H4, &d.b1);
+    rc |= tr->blocks.alloc((size_t)2 * H, &d.v.h) | tr->blocks.alloc((size_t)2 * H, &d.v.c);
+    rc |= tr->blocks.alloc(Tm * C, &d.xs) | tr->blocks.alloc(Tm * H4, &d.act0) | tr->blocks.alloc(Tm * H4, &d.act1);
+    rc |= tr->blocks.alloc((Tm + 1) * H, &d.c0) | tr->blocks.alloc((Tm + 1) * H, &d.c1) | tr->blocks.alloc((Tm + 1) * H, &d.h0) | tr->blocks.alloc((Tm + 1) * H, &d.h1);
+    rc |= tr->blocks.alloc(Tm * H, &d.h0m) | tr->blocks.alloc(Tm * 2, &d.logit) | tr->blocks.alloc(Tm * 2, &d.dl) | tr->blocks.alloc(Tm, &d.lossf);
+    rc |= tr->blocks.alloc(Tm * H4, &d.dg0) | tr->blocks.alloc(Tm * H4, &d.dg1) | tr->blocks.alloc(Tm * H, &d.dh0m);
     if (rc) {
         dss_set_error("device allocation failed for the detector's trainer (%d inputs, %d hidden units, max_window %d)", C, H, max_window);
         dss_vad_trainer_destroy(tr);
