@@ -5,7 +5,8 @@
 // sums) and the staging of the host-buffer form; the arithmetic runs in csrc/contamination.hip only.  Every check of a value is a
 // handle-free host function (dss_contam_check_params, _check_window, _frames_for, _check_call, _result_size) that create and the
 // two calls run before they touch a device, so each is testable without one; only the NULL checks of a call's own pointers need
-// a handle to be told apart from a missing handle.
+// a handle to be told apart from a missing handle.  How a call's frames are cut into workgroups is decided in one place
+// (contam_cut), which dss_contam_plan reports without a device.
 #include <math.h>
 
 #include <algorithm>
@@ -113,6 +114,30 @@ extern "C" long long dss_contam_check_call(const dss_contam_params *p, long long
     return dss_contam_frames_for(n_rows, p->nperseg, p->hop, p->max_lag);
 }
 
+// Chunks of whole tiles: about 512 workgroups in all, every chunk at least one tile, the last one perhaps shorter.
+static void contam_cut(const DssContamDev &v, int W, int C, int *n_tiles, int *chunks, int *tiles_per_chunk)
+{
+    *n_tiles = (W + CONTAM_F - 1) / CONTAM_F;
+    const long long per_chunk = (long long)C * v.Z;
+    const int want = (int)std::max(1LL, std::min((long long)*n_tiles, (512 + per_chunk - 1) / per_chunk));
+    *tiles_per_chunk = (*n_tiles + want - 1) / want;
+    *chunks = (*n_tiles + *tiles_per_chunk - 1) / *tiles_per_chunk;
+}
+
+extern "C" int dss_contam_plan(const dss_contam_params *p, long long n_rows, int n_channels, int plan[6])
+{
+    const long long W = dss_contam_check_call(p, n_rows, n_channels, n_channels);
+    if (W < 0) return DSS_EINVAL;
+    if (!plan) { dss_set_error("contamination: nowhere to write the plan"); return DSS_EINVAL; }
+    DssContamDev v;
+    dss_contam_shape(p->nperseg, p->hop, p->bin_lo, p->n_bins, p->max_lag, &v);
+    plan[0] = (int)W;
+    contam_cut(v, (int)W, n_channels, &plan[1], &plan[2], &plan[3]);
+    plan[4] = v.Z;
+    plan[5] = v.lgn;
+    return DSS_OK;
+}
+
 extern "C" void dss_contam_destroy(dss_contam *h)
 {
     if (!h) return;
@@ -170,12 +195,8 @@ static int contam_run(dss_contam *h, const double *d_x, int ld, int C, const dou
     h->keep.assign((size_t)W, 1);
     if (keep_frames)
         for (int t = 0; t < W; ++t) h->keep[t] = keep_frames[t] ? 1 : 0;
-    // chunks of whole tiles: about 512 workgroups in all, every chunk at least one tile
-    const int n_tiles = (W + CONTAM_F - 1) / CONTAM_F;
-    const long long per_chunk = (long long)C * v.Z;
-    int chunks = (int)std::max(1LL, std::min((long long)n_tiles, (512 + per_chunk - 1) / per_chunk));
-    const int tiles_per_chunk = (n_tiles + chunks - 1) / chunks;
-    chunks = (n_tiles + tiles_per_chunk - 1) / tiles_per_chunk;
+    int n_tiles, chunks, tiles_per_chunk;
+    contam_cut(v, W, C, &n_tiles, &chunks, &tiles_per_chunk);
     int rc = h->blocks.grow_headroom(&h->d_keep, &h->keep_cap, (size_t)W);
     if (!rc) rc = h->blocks.grow_headroom(&h->d_aud, &h->aud_cap, (size_t)W * CONTAM_PAD);
     if (!rc) rc = h->blocks.grow_headroom(&h->d_partial, &h->partial_cap, (size_t)chunks * v.nlag * C * contam_record(v.B));

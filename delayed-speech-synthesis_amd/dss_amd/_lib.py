@@ -180,6 +180,7 @@ def _declare(L):
         "dss_contam_frames_for": (C.c_longlong, [C.c_longlong, i, i, i]),
         "dss_contam_check_call": (C.c_longlong, [vp, C.c_longlong, i, i]),
         "dss_contam_result_size": (C.c_longlong, [vp, i, vp]),
+        "dss_contam_plan": (i, [vp, C.c_longlong, i, vp]),
         "dss_contam_create": (vp, [vp, vp]),
         "dss_contam_destroy": (None, [vp]),
         "dss_contam_moments": (i, [vp, vp, C.c_longlong, i, i, vp, vp, vp]),

@@ -27,6 +27,7 @@ U = 2.0 ** -53
 
 Moments = collections.namedtuple("Moments", "n shift sa saa sb sbb sab")
 Analysis = collections.namedtuple("Analysis", "surrogate_measures dataset_measure criterion_value matrix correlations")
+Plan = collections.namedtuple("Plan", "frames tiles chunks tiles_per_chunk lag_groups lags_per_wave")
 
 
 class ContamParams(C.Structure):
@@ -58,6 +59,14 @@ def kept_bins(fs: float, nperseg: int, band) -> np.ndarray:
 def frames_for(n_rows: int, nperseg: int, hop: int, max_lag: int = 0) -> int:
     """(n_rows - nperseg) // hop + 1; DssError for a recording shorter than one window (needs no GPU)."""
     return _lib.check(_lib.load().dss_contam_frames_for(int(n_rows), int(nperseg), int(hop), int(max_lag)))
+
+
+def launch_plan(params: ContamParams, n_rows: int, n_channels: int) -> Plan:
+    """How the library cuts a call into workgroups (``dss_contam_plan``; needs no GPU): frames, tiles of 32 frames, chunks of
+    ``tiles_per_chunk`` tiles (the last may hold fewer), lag groups of the grid, lags per wave."""
+    plan = (C.c_int * 6)()
+    _lib.check(_lib.load().dss_contam_plan(C.addressof(params), int(n_rows), int(n_channels), C.addressof(plan)))
+    return Plan(*plan)
 
 
 def frame_mask(keep, nperseg: int, hop: int) -> np.ndarray:
@@ -210,6 +219,10 @@ class ContaminationGPU:
 
     def frames(self, n_rows: int) -> int:
         return frames_for(n_rows, self.nperseg, self.hop, self.max_lag)
+
+    def plan(self, n_rows: int, n_channels: int) -> Plan:
+        """The launch plan of a call on ``n_rows`` rows of ``n_channels`` channels (``launch_plan``)."""
+        return launch_plan(self.params, n_rows, n_channels)
 
     # ---- arguments ----------------------------------------------------------------------------------------------------
     def _layout(self, n_channels):

@@ -740,6 +740,11 @@ long long dss_contam_check_call(const dss_contam_params *p, long long n_rows, in
 /* Doubles of the result for n_channels channels, and (offsets != NULL) where n, shift, sa, saa, sb, sbb, sab start in it (no
  * device needed).  DSS_EINVAL for n_channels outside 1 .. 65535. */
 long long dss_contam_result_size(const dss_contam_params *p, int n_channels, long long offsets[7]);
+/* How a call on n_rows rows of n_channels channels is cut into workgroups, as the calls themselves decide it (no device needed):
+ * plan = {frames W, tiles of 32 frames, chunks (the grid's x), tiles per chunk (the last chunk may hold fewer), lag groups Z (the
+ * grid's z), lags per wave}.  Each workgroup (chunk, channel, lag group) walks its chunk's tiles with 4 x lags-per-wave lags in
+ * registers.  Returns 0, or DSS_EINVAL for what dss_contam_check_call(p, n_rows, n_channels, n_channels) refuses. */
+int dss_contam_plan(const dss_contam_params *p, long long n_rows, int n_channels, int plan[6]);
 /* window: nperseg doubles (dss_amd.contamination.hamming_symmetric).  NULL on failure. */
 dss_contam *dss_contam_create(const dss_contam_params *p, const double *window);
 void dss_contam_destroy(dss_contam *h);

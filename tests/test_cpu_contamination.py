@@ -8,11 +8,12 @@ import re
 import numpy as np
 import pytest
 
+import contamination_cases as cases
 import contamination_reference as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("dss_contam_check_params", "dss_contam_check_window", "dss_contam_frames_for", "dss_contam_check_call", "dss_contam_result_size",
-       "dss_contam_create", "dss_contam_destroy", "dss_contam_moments", "dss_contam_moments_dev")
+       "dss_contam_create", "dss_contam_destroy", "dss_contam_moments", "dss_contam_moments_dev", "dss_contam_plan")
 # the planted case (contamination_reference.planted_case, seed 11), artifact detection on: recorded from the reference
 PLANT_P, PLANT_MEASURE, CLEAN_P, CLEAN_MEASURE = 0.0, 0.5562, 0.7143, 0.0988
 
@@ -256,3 +257,105 @@ def test_planted_leak_is_found_and_its_absence_is_not(planted):
     assert p < 0.05 and p == PLANT_P and measure == pytest.approx(PLANT_MEASURE, abs=5e-5)
     _, _, (_, measure, p) = planted[False]
     assert p > 0.05 and p == pytest.approx(CLEAN_P, abs=5e-5) and measure == pytest.approx(CLEAN_MEASURE, abs=5e-5)
+
+
+def _plan(L, p, n_rows, n_channels):
+    plan = (C.c_int * 6)()
+    rc = L.dss_contam_plan(C.addressof(p), n_rows, n_channels, C.addressof(plan))
+    return rc, tuple(plan)
+
+
+@pytest.mark.parametrize("name", cases.NAMES)
+def test_every_case_reaches_the_plan_it_is_there_for_and_the_reference_agrees_with_itself(name):
+    """The case table of tests/contamination_cases.py without a GPU: the operator gives the shape the table states, the library
+    plans the launch the case is there to reach, and the reference alone -- its one-pass sums through correlations_from_moments
+    against its two-pass correlations -- meets every condition the GPU test holds the kernels to."""
+    from dss_amd import contamination
+    from dss_amd.contamination import Moments, correlations_from_moments
+    s = cases.spec(name)
+    op, brain, audio, keep = cases.build(name)
+    day = cases.day(name)
+    assert cases.shape_of(day) == s.shape
+    nperseg, hop, bin_lo, B, lag, W = s.shape
+    assert (int(round(op.get("window", 0.2) * op["fs"])), int(round(op["fs"] / op.get("spg_fs", 50)))) == (nperseg, hop)
+    inside = contamination.kept_bins(op["fs"], nperseg, op.get("band", (70, 170)))
+    assert (int(inside[0]), len(inside)) == (bin_lo, B) and contamination.frames_for(s.T, nperseg, hop, lag) == W
+    p = contamination.ContamParams(nperseg, hop, bin_lo, B, lag, 0)
+    assert contamination.launch_plan(p, s.T, s.C) == s.plan
+    frames, tiles, chunks, per, Z, lgn = s.plan
+    if name in ("many_tiles", "default_long", "planted", "one_chunk"):
+        assert per > 1 and (chunks == 1 or tiles % per)                               # several tiles per chunk, a shorter last chunk
+    else:
+        assert per == 1
+    if name == "odd_window":
+        assert nperseg % 2 == 1 and bin_lo + B - 1 == nperseg // 2
+    if name == "apart":
+        assert hop > ((nperseg + 3) & ~3) and np.isnan(brain).any() and np.isnan(audio).any()
+    if name == "abutting":
+        assert hop == nperseg < ((nperseg + 3) & ~3)
+    if name == "one_chunk":
+        assert brain.strides == (523 * 8, 8)
+    if name == "lds_edge":
+        assert 1800 < nperseg < 1900 and cases.params_accepted(nperseg, 1, bin_lo, B, 0)
+        assert not cases.params_accepted(nperseg + 1, 1, bin_lo, B, 0)
+        assert b"do not fit the kernel's 81920 bytes of LDS" in _lib_error()
+
+    want, bound = day.moments(cases.kept_mean(day))
+    r_want = day.correlations()
+    assert np.isfinite(r_want[~np.isnan(r_want)]).all() and all(np.isfinite(want[k]).all() for k in want)
+    r = correlations_from_moments(Moments(want["n"], None, want["sa"], want["saa"], want["sb"], want["sbb"], want["sab"]))
+    assert np.array_equal(np.isnan(r), np.isnan(r_want))
+    ok = ~np.isnan(r_want)
+    rb = ref.r_bound(want, bound)
+    assert ok.any() == (name not in cases.NO_CORRELATION)
+    if ok.any():
+        print(f"{name}: reference against itself, max |difference| / bound {np.max(np.abs(r - r_want)[ok] / rb[ok]):.3g}, "
+              f"median bound {np.median(rb[ok]):.3g}")
+        assert np.all(np.abs(r - r_want)[ok] <= rb[ok]) and np.median(rb[ok]) < 1e-9
+    cases.check_exact(name, want["n"], cases.kept_mean(day), want, r_want)
+    cases.check_exact(name, want["n"], cases.kept_mean(day), want, r)
+
+
+def _lib_error():
+    from dss_amd import _lib
+    return _lib.load().dss_last_error()
+
+
+def test_plan_refuses_what_the_calls_refuse_and_every_plan_covers_its_frames_and_lags():
+    from dss_amd import _lib, contamination
+    L = _lib.load()
+    P = contamination.ContamParams
+    good = dict(nperseg=200, hop=20, bin_lo=14, n_bins=21, max_lag=25, reserved=0)
+    p = P(**good)
+    assert _plan(L, p, 2600, 3) == (0, (121, 4, 4, 1, 2, 7))
+    assert contamination.launch_plan(p, 2600, 3)._fields == ("frames", "tiles", "chunks", "tiles_per_chunk", "lag_groups", "lags_per_wave")
+    for args in ((2600, 0), (2600, -1), (2600, 65536), (199, 3), (2**40, 3)):
+        assert L.dss_contam_check_call(C.addressof(p), args[0], args[1], args[1]) == -1
+        reason = L.dss_last_error()
+        assert L.dss_contam_plan(C.addressof(p), *args, C.addressof((C.c_int * 6)())) == -1 and L.dss_last_error() == reason, args
+        assert len(reason) > 10
+    for change in (dict(hop=0), dict(n_bins=32), dict(nperseg=2048, hop=2048), dict(max_lag=4097)):
+        bad = P(**{**good, **change})
+        assert L.dss_contam_check_call(C.addressof(bad), 2600, 3, 3) == -1
+        reason = L.dss_last_error()
+        assert _plan(L, bad, 2600, 3)[0] == -1 and L.dss_last_error() == reason, change
+    assert L.dss_contam_plan(None, 2600, 3, C.addressof((C.c_int * 6)())) == -1 and b"no parameters" in L.dss_last_error()
+    assert L.dss_contam_plan(C.addressof(p), 2600, 3, None) == -1 and b"nowhere to write the plan" in L.dss_last_error()
+    with pytest.raises(_lib.DssError, match="199 rows is shorter than one window"):
+        contamination.launch_plan(p, 199, 3)
+
+    # every chunk holds a tile, the chunks cover the tiles and the waves cover the lags, over a sweep of (W, C, L)
+    seen = set()
+    for lag in (0, 1, 3, 15, 16, 17, 25, 31, 32, 47, 48, 63, 64, 100, 1000, 4096):
+        q = P(nperseg=16, hop=4, bin_lo=2, n_bins=4, max_lag=lag, reserved=0)
+        for W in (1, 2, 31, 32, 33, 64, 65, 95, 96, 97, 991, 1014, 1925, 5000, 16385, 100001):
+            for Cn in (1, 2, 3, 9, 12, 40, 127, 128, 129, 255, 256, 257, 511, 512, 513, 520, 65535):
+                rc, (frames, tiles, chunks, per, Z, lgn) = _plan(L, q, 16 + 4 * (W - 1) + 3, Cn)
+                assert rc == 0 and frames == W and tiles == (W + 31) // 32, (lag, W, Cn)
+                assert chunks >= 1 and per >= 1 and chunks * per >= tiles > (chunks - 1) * per, (lag, W, Cn)
+                assert 1 <= lgn <= 8 and Z * 4 * lgn >= 2 * lag + 1 > (Z - 1) * 4 * 8, (lag, W, Cn)
+                assert chunks == 1 or (chunks - 1) * Cn * Z < 512 + Cn * Z, (lag, W, Cn)             # about 512 workgroups
+                seen.add((chunks == 1, per == 1, tiles % per == 0))
+    # (one chunk, one tile per chunk, a full last chunk): the sweep reaches every combination there is -- one chunk and chunks of
+    # one tile are always full
+    assert seen == {(True, True, True), (True, False, True), (False, True, True), (False, False, True), (False, False, False)}
