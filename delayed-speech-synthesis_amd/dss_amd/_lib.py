@@ -185,6 +185,10 @@ def _declare(L):
         "dss_contam_destroy": (None, [vp]),
         "dss_contam_moments": (i, [vp, vp, C.c_longlong, i, i, vp, vp, vp]),
         "dss_contam_moments_dev": (i, [vp, vp, C.c_longlong, i, i, vp, vp, vp, vp]),
+        "dss_dropout_check": (i, [i, vp]),
+        "dss_dropout_masks_dev": (i, [vp, i, vp]),
+        "dss_dropout_masks_host": (i, [vp, i]),
+        "dss_selftest_philox": (i, [vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

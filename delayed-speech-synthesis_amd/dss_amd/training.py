@@ -14,6 +14,12 @@ Dropout masks are drawn here, from a seeded ``torch.Generator`` on the host, and
 or 1 / (1 - p): a run is reproducible from its seed.  This is not torch's own random stream (``nn.LSTM``'s dropout draws inside
 MIOpen / ATen); the reference's training is not reproducible across devices either.
 
+``mask_source="device"`` (the epoch loops) or a ``DeviceMaskSource`` in place of the ``torch.Generator`` (the trainers) draws the
+masks on the device instead: a stateless counter-based generator (Philox4x32-10; csrc/dropout.hip, Part 14 of include/dss_hip.h),
+a mask being a pure function of (seed, draw number, shape, p).  Nothing is drawn on the host, staged or uploaded, and a model's
+masks depend neither on the group it trains in nor on its place there.  It is another random stream than the host generator's,
+so it is an opt-in: the default stays the host generator, bit for bit.
+
 The decoder's script trains ``BidirectionalSpeechSynthesisModel`` (2 bidirectional LSTM layers, ``dropout=0.5``) with batch size 1
 and no windows: a whole trial (250-1500 frames) is forward from the zero state, ``nn.MSELoss``, ``backward()`` through the trial,
 ``RMSprop.step()``.  ``DecoderTrainerGPU`` is that trial as seven hand-written launches on one stream
@@ -48,13 +54,142 @@ def _shapes(c: int, h: int):
     return [(h4, c), (h4, h), (h4,), (h4,), (h4, h), (h4, h), (h4,), (h4,), (2, h), (2,)]
 
 
-def dropout_mask(n_frames: int, hidden_units: int, p: float, generator):
-    """(n_frames, H) float32 multipliers of layer 0's output: 0 with probability p, else 1 / (1 - p); None for p == 0."""
-    import torch
+class _DropoutEntry(C.Structure):
+    """``dss_dropout_entry`` of include/dss_hip.h."""
+    _fields_ = [("d_mask", C.c_void_p), ("rows", C.c_int), ("width", C.c_int), ("seed", C.c_ulonglong), ("draw", C.c_ulonglong),
+                ("p", C.c_float), ("scale", C.c_float)]
+
+
+DROPOUT_MAX_ENTRIES = 64          # the entries of one launch (Part 14)
+
+
+def dropout_scale(p: float) -> np.float32:
+    """The multiplier of a kept element, float32 1 / (1 - p), in the bits ``dropout_mask`` has always produced (2.0 at p = 0.5)."""
+    return np.float32(1.0) / np.float32(1.0 - p)
+
+
+def _check_p(p):
     if not 0.0 <= p < 1.0:
         raise ValueError("dropout must be in [0, 1)")
+
+
+def device_dropout_masks(entries):
+    """Fill masks from the counter-based generator of Part 14, 64 per launch.  ``entries``: [(out, seed, draw, p)], ``out`` a
+    contiguous float32 torch tensor (rows, width) that the mask of (seed, draw, rows, width, p) is written into.  CUDA tensors are
+    filled by ``dss_dropout_masks_dev`` on torch's current stream, with no host synchronisation; CPU tensors by the library's
+    scalar restatement (``dss_dropout_masks_host``: the same bits, no GPU needed).  One call takes one kind.  Empty tensors are
+    skipped."""
+    import torch
+    L = _lib.load()
+    live, cuda = [], None
+    for out, seed, draw, p in entries:
+        if not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.dim() == 2 and out.is_contiguous()):
+            raise ValueError("a mask is written into a contiguous float32 tensor (rows, width)")
+        if not (0 <= int(seed) < 2 ** 64 and 0 <= int(draw) < 2 ** 64):
+            raise ValueError("seed and draw must be in 0 .. 2**64 - 1")
+        if not 0.0 < p < 1.0:
+            raise ValueError("a device mask needs 0 < dropout < 1 (dropout 0 is no mask)")
+        if cuda is not None and out.is_cuda != cuda:
+            raise ValueError("one call fills CUDA masks or CPU masks, not both")
+        cuda = out.is_cuda
+        if out.numel():
+            live.append(_DropoutEntry(out.data_ptr(), int(out.shape[0]), int(out.shape[1]), int(seed), int(draw), float(p), float(dropout_scale(p))))
+    if not live:
+        return
+    stream = None
+    if cuda:
+        _lib.require_gpu()
+        stream = torch.cuda.current_stream().cuda_stream
+    for a in range(0, len(live), DROPOUT_MAX_ENTRIES):
+        chunk = live[a:a + DROPOUT_MAX_ENTRIES]
+        table = (_DropoutEntry * len(chunk))(*chunk)
+        _lib.check(L.dss_dropout_masks_dev(table, len(chunk), stream) if cuda else L.dss_dropout_masks_host(table, len(chunk)))
+
+
+def _packed_masks(requests, device, buf=None):
+    """``requests``: [(rows, width, seed, draw, p) or None].  All masks in one buffer, each at a multiple of 4 floats (so that a
+    buffer aligned to 16 bytes is written in 16-byte stores), filled by one launch per 64; ``buf`` is reused when it is large
+    enough.  Returns ([(rows, width) view or None], the buffer)."""
+    import torch
+    offsets, total = [], 0
+    for r in requests:
+        offsets.append(total)
+        if r is not None:
+            total += -(-(int(r[0]) * int(r[1])) // 4) * 4
+    if buf is None or buf.numel() < total:
+        buf = torch.empty((total,), dtype=torch.float32, device=device)
+    views = [None if r is None else buf[o:o + int(r[0]) * int(r[1])].view(int(r[0]), int(r[1])) for r, o in zip(requests, offsets)]
+    device_dropout_masks([(v, r[2], r[3], r[4]) for v, r in zip(views, requests) if r is not None])
+    return views, buf
+
+
+class DeviceMaskSource:
+    """The dropout masks of one training run from the counter-based generator of Part 14: ``seed`` (0 <= seed < 2**64) and a
+    running ``draw`` number, which starts at 0, goes up by one with every mask and may be set (to resume a run, or to draw a mask
+    again).  The trainers take one wherever they take a ``torch.Generator``.  ``device="cpu"`` gives the same bits from the
+    library's CPU restatement."""
+
+    def __init__(self, seed: int = 0, device="cuda"):
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must be in 0 .. 2**64 - 1")
+        self.seed, self.device, self._draw = seed, device, 0
+
+    @property
+    def draw(self) -> int:
+        return self._draw
+
+    @draw.setter
+    def draw(self, value):
+        value = int(value)
+        if not 0 <= value < 2 ** 64:
+            raise ValueError("draw must be in 0 .. 2**64 - 1")
+        self._draw = value
+
+    def take(self, n: int = 1) -> int:
+        """Reserve the next n draw numbers; returns the first."""
+        first = self._draw
+        self.draw = first + int(n)
+        return first
+
+    def mask(self, rows: int, width: int, p: float, out=None):
+        """The next mask: a (rows, width) float32 tensor on the source's device (``out`` if given: contiguous float32 of that
+        shape) of 0 / 1 / (1 - p) multipliers; ``draw`` goes up by one.  None for p == 0, which draws nothing."""
+        import torch
+        _check_p(p)
+        if p == 0.0:
+            return None
+        rows, width = int(rows), int(width)
+        if rows < 0 or width < 0:
+            raise ValueError("a mask of negative size")
+        if out is None:
+            out = torch.empty((rows, width), dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != (rows, width):
+            raise ValueError(f"out must be ({rows}, {width})")
+        device_dropout_masks([(out, self.seed, self._draw, p)])
+        self.take()
+        return out
+
+    def masks(self, shapes, p: float):
+        """Several masks in one launch (per 64), one draw each in list order: ``shapes`` is [(rows, width) or None]; a None neither
+        draws nor advances and gives None.  The masks are slices of one buffer.  [None] * len(shapes) for p == 0."""
+        shapes = list(shapes)
+        _check_p(p)
+        if p == 0.0:
+            return [None] * len(shapes)
+        requests = [None if s is None else (int(s[0]), int(s[1]), self.seed, self.take(), p) for s in shapes]
+        return _packed_masks(requests, self.device)[0]
+
+
+def dropout_mask(n_frames: int, hidden_units: int, p: float, generator):
+    """(n_frames, H) float32 multipliers of layer 0's output: 0 with probability p, else 1 / (1 - p); None for p == 0.  From the
+    host generator (a ``torch.Generator`` or None: a CPU tensor), or on the device from a ``DeviceMaskSource``."""
+    import torch
+    _check_p(p)
     if p == 0.0:
         return None
+    if isinstance(generator, DeviceMaskSource):
+        return generator.mask(n_frames, hidden_units, p)
     keep = torch.rand((int(n_frames), int(hidden_units)), generator=generator, dtype=torch.float32) >= p
     return keep.to(torch.float32) / np.float32(1.0 - p)
 
@@ -131,8 +266,9 @@ class VadTrainerGPU:
                     alpha: float = ALPHA, eps: float = EPS):
         """One trial, as the script's lines 146-175: the state starts from zeros, then every window of ``window`` frames (the last
         one the remainder) is stepped, all enqueued in one call.  The dropout masks of the trial are ``masks`` ((len, H)
-        multipliers) if given, else drawn with ``dropout_mask(len, H, dropout, generator)``.  Returns the per-window losses
-        (float64 array)."""
+        multipliers) if given, else drawn with ``dropout_mask(len, H, dropout, generator)``: ``generator`` is a ``torch.Generator``
+        (or None) for the host's stream, or a ``DeviceMaskSource``, which draws the mask on the device.  Returns the per-window
+        losses (float64 array)."""
         import torch
         x = self._frames(x)
         n = int(x.shape[0])
@@ -201,8 +337,18 @@ def _corpus(corpus):
         return corpus.hga_activity, corpus.vad_labels, corpus.trial_ids
 
 
+def _mask_sources(mask_source, seeds):
+    """None for "host" (the masks come from the seeded ``torch.Generator`` that draws the permutations), else one
+    ``DeviceMaskSource`` per seed."""
+    if mask_source == "host":
+        return None
+    if mask_source != "device":
+        raise ValueError(f'mask_source must be "host" or "device", not {mask_source!r}')
+    return [DeviceMaskSource(s) for s in seeds]
+
+
 def train_vad(state_dict, train_corpus, valid_corpus, epochs: int = 8, window: int = 50, dropout: float = 0.5, lr: float = LR,
-              seed: int = 0, columns=None, shuffle: bool = True, alpha: float = ALPHA, eps: float = EPS):
+              seed: int = 0, columns=None, shuffle: bool = True, alpha: float = ALPHA, eps: float = EPS, mask_source: str = "host"):
     """The script's epoch loop.  ``state_dict`` (or a module) gives the initial weights; a corpus is a mapping (or an object) with
     ``hga_activity`` (N, C), ``vad_labels`` (N,) and ``trial_ids`` (N,), as ``session_corpus`` returns it; ``columns`` is the
     optional channel selection in front of the model (``SelectElectrodesOverSpeechAreas``).
@@ -211,9 +357,13 @@ def train_vad(state_dict, train_corpus, valid_corpus, epochs: int = 8, window: i
     order), ``train_trial`` on each with masks from the same generator, then ``publish`` into one kept ``VadLstmGPU`` and
     ``vad_validation`` on the validation corpus.  The best weights are kept when the validation accuracy is strictly greater than
     every one before (``StoreBestModel``).  Returns (best state_dict, history): history[e] has ``train_loss`` (the mean over
-    the epoch's windows), ``valid_loss``, ``accuracy``, ``update_steps`` (cumulative) and ``best`` (whether the epoch was kept)."""
+    the epoch's windows), ``valid_loss``, ``accuracy``, ``update_steps`` (cumulative) and ``best`` (whether the epoch was kept).
+
+    ``mask_source="device"``: the permutations still come from that generator, the masks from ``DeviceMaskSource(seed)``, one
+    draw per trial."""
     import torch
     from .validation import _corpus_frames
+    src = _mask_sources(mask_source, [seed])
     tr = VadTrainerGPU(state_dict, max_window=window)
     x, ranges = _corpus_frames(*(_corpus(train_corpus)[i] for i in (0, 2)), columns)
     ya = _corpus(train_corpus)[1]
@@ -229,7 +379,8 @@ def train_vad(state_dict, train_corpus, valid_corpus, epochs: int = 8, window: i
         losses = []
         for k in order:
             a, n = ranges[k]
-            losses.append(tr.train_trial(x[a:a + n], ya[a:a + n], window=window, dropout=dropout, generator=gen, lr=lr, alpha=alpha, eps=eps))
+            losses.append(tr.train_trial(x[a:a + n], ya[a:a + n], window=window, dropout=dropout, generator=src[0] if src else gen, lr=lr, alpha=alpha,
+                                         eps=eps))
         losses = np.concatenate(losses) if losses else np.zeros(0)
         steps += len(losses)
         tr.publish(detector)
@@ -329,7 +480,8 @@ class DecoderTrainerGPU:
     def train_trial(self, x, y, dropout: float = 0.5, generator=None, mask=None, lr: float = LR, alpha: float = ALPHA,
                     eps: float = EPS) -> float:
         """One update step, as the script's lines 134-152.  The dropout mask is ``mask`` ((T, 2H) multipliers) if given, else drawn
-        with ``decoder_dropout_mask(T, H, dropout, generator)``.  Returns the loss."""
+        with ``decoder_dropout_mask(T, H, dropout, generator)``: ``generator`` is a ``torch.Generator`` (or None) for the host's
+        stream, or a ``DeviceMaskSource``, which draws the mask on the device.  Returns the loss."""
         if mask is None:
             n = int(x.shape[0]) if hasattr(x, "shape") else len(x)
             mask = decoder_dropout_mask(n, self.H, dropout, generator)
@@ -383,7 +535,8 @@ def _dec_corpus(corpus):
 
 
 def train_decoder(state_dict, train_corpus, valid_corpus, epochs: int = 8, dropout: float = 0.5, lr: float = LR, seed: int = 0,
-                  columns=None, shuffle: bool = True, alpha: float = ALPHA, eps: float = EPS, max_streams: int = 256):
+                  columns=None, shuffle: bool = True, alpha: float = ALPHA, eps: float = EPS, max_streams: int = 256,
+                  mask_source: str = "host"):
     """The script's epoch loop.  ``state_dict`` (or a module) gives the initial weights; a corpus is a mapping (or an object) with
     ``hga_activity`` (N, C), ``lpc_coefficients`` (N, O) and ``trial_ids`` (N,): what ``session_corpus`` returns plus the targets;
     ``columns`` is the optional channel selection in front of the model.
@@ -393,9 +546,13 @@ def train_decoder(state_dict, train_corpus, valid_corpus, epochs: int = 8, dropo
     ``publish`` into one kept ``BiLstmDecoderGPU`` (``max_streams`` trials side by side) and ``decoder_validation`` on the
     validation corpus.  The best weights are kept when the validation loss is strictly less than every one before
     (``StoreBestModel``).  Returns (best state_dict, history): history[e] has ``train_loss`` (the mean over the epoch's trials),
-    ``valid_loss``, ``update_steps`` (cumulative) and ``best`` (whether the epoch was kept)."""
+    ``valid_loss``, ``update_steps`` (cumulative) and ``best`` (whether the epoch was kept).
+
+    ``mask_source="device"``: the permutations still come from that generator, the masks from ``DeviceMaskSource(seed)``, one
+    draw per trial."""
     import torch
     from .validation import _corpus_frames
+    src = _mask_sources(mask_source, [seed])
     hx, hy, hid = _dec_corpus(train_corpus)
     x, ranges = _corpus_frames(hx, hid, columns)
     vx, vy, vid = _dec_corpus(valid_corpus)
@@ -414,7 +571,7 @@ def train_decoder(state_dict, train_corpus, valid_corpus, epochs: int = 8, dropo
         losses = []
         for k in order:
             a, n = ranges[k]
-            m = decoder_dropout_mask(n, tr.H, dropout, gen)
+            m = decoder_dropout_mask(n, tr.H, dropout, src[0] if src else gen)
             losses.append(tr._trial(x[a:a + n], y[a:a + n], m, True, lr, alpha, eps))
         losses = torch.cat(losses).cpu().numpy() if losses else np.zeros(0)
         steps += len(losses)
@@ -634,22 +791,35 @@ def lockstep_schedule(orders):
     return [[o[k] if k < len(o) else None for o in orders] for k in range(max([len(o) for o in orders] + [0]))]
 
 
-def _group_epoch(step, gens, n_trials, lengths, hidden_units, dropout, shuffle):
+def _group_epoch(step, gens, n_trials, lengths, hidden_units, dropout, shuffle, sources=None):
     """One epoch of M runs in lock step.  Model m's generator ``gens[m]`` draws what ``train_decoder``'s generator draws in an
     epoch, in its order: the permutation of its ``n_trials[m]`` trials first, then the mask of each trial as its turn comes
     (``lengths[m][trial]`` frames).  ``step(trials, masks)`` gets, per step, every model's trial index (or None) and mask (or
-    None) and returns the step's losses.  Returns ([per step: trials], [per step: what step returned])."""
+    None) and returns the step's losses.  Returns ([per step: trials], [per step: what step returned]).
+
+    With ``sources`` (one ``DeviceMaskSource`` per model) the generators draw the permutations only: a step's masks are one entry
+    table and one launch into one device buffer, each mask at a multiple of 4 floats, model m's from ``sources[m]``'s next draw (a
+    model that sits the step out draws nothing), and ``step`` gets the slices -- nothing is staged or uploaded.  One buffer
+    serves every step: the launch that refills it is queued behind the step that read it, on the same stream."""
     import torch
+    _check_p(dropout)
     orders = [torch.randperm(n, generator=g).tolist() if shuffle else list(range(n)) for n, g in zip(n_trials, gens)]
-    steps, out = lockstep_schedule(orders), []
+    steps, out, buf = lockstep_schedule(orders), [], None
     for trials in steps:
-        masks = [None if k is None else decoder_dropout_mask(lengths[m][k], hidden_units, dropout, gens[m]) for m, k in enumerate(trials)]
+        if sources is None:
+            masks = [None if k is None else decoder_dropout_mask(lengths[m][k], hidden_units, dropout, gens[m]) for m, k in enumerate(trials)]
+        elif dropout == 0.0:
+            masks = [None] * len(trials)
+        else:
+            requests = [None if k is None else (lengths[m][k], 2 * int(hidden_units), sources[m].seed, sources[m].take(), dropout)
+                        for m, k in enumerate(trials)]
+            masks, buf = _packed_masks(requests, sources[0].device, buf)
         out.append(step(trials, masks))
     return steps, out
 
 
 def train_decoders(state_dicts, train_corpora, valid_corpora, epochs: int = 8, dropout: float = 0.5, lr=LR, seeds=None, columns=None,
-                   shuffle: bool = True, alpha: float = ALPHA, eps: float = EPS, max_streams: int = 256):
+                   shuffle: bool = True, alpha: float = ALPHA, eps: float = EPS, max_streams: int = 256, mask_source: str = "host"):
     """M ``train_decoder`` loops in lock step on one ``DecoderGroupTrainerGPU``: the folds of train_bidirectional_model.py:65-68,
     seeds or learning rates as one run.  ``state_dicts[m]``, ``train_corpora[m]``, ``valid_corpora[m]`` and ``seeds[m]`` (default
     0 .. M - 1) are model m's arguments of ``train_decoder``; ``lr`` is a scalar or one per model; ``columns`` is shared.
@@ -658,7 +828,11 @@ def train_decoders(state_dicts, train_corpora, valid_corpora, epochs: int = 8, d
     ``train_decoder`` does, and step k of an epoch runs every model's k-th trial, models with fewer trials sitting out the rest of
     the epoch: every model's history and best weights are those of ``train_decoder`` run alone with its seed and corpora, bit
     for bit.  After an epoch each model is published into one kept ``BiLstmDecoderGPU`` and validated on its own corpus.
-    Returns [(best state_dict, history)], one pair per model."""
+    Returns [(best state_dict, history)], one pair per model.
+
+    ``mask_source="device"``: the permutations still come from those generators; model m's masks come from
+    ``DeviceMaskSource(seeds[m])``, one draw per trial stepped, all masks of a step from one launch -- again what
+    ``train_decoder(..., mask_source="device", seed=seeds[m])`` computes alone, bit for bit."""
     import torch
     from .validation import _corpus_frames
     state_dicts, train_corpora, valid_corpora = list(state_dicts), list(train_corpora), list(valid_corpora)
@@ -668,6 +842,7 @@ def train_decoders(state_dicts, train_corpora, valid_corpora, epochs: int = 8, d
         if len(seq) != M:
             raise ValueError(f"{what}: {len(seq)} entries for {M} models")
     lrs = _per_model(lr, M, "lr")
+    sources = _mask_sources(mask_source, seeds)
     xs, ys, ranges, valid, longest = [], [], [], [], 1
     for m in range(M):
         hx, hy, hid = _dec_corpus(train_corpora[m])
@@ -696,7 +871,7 @@ def train_decoders(state_dicts, train_corpora, valid_corpora, epochs: int = 8, d
     best = [(None, np.inf)] * M
     n_steps, history = [0] * M, [[] for _ in range(M)]
     for _ in range(int(epochs)):
-        steps, losses = _group_epoch(step, gens, [len(r) for r in ranges], lengths, tr.H, dropout, shuffle)
+        steps, losses = _group_epoch(step, gens, [len(r) for r in ranges], lengths, tr.H, dropout, shuffle, sources)
         losses = torch.stack(losses).cpu().numpy() if losses else np.zeros((0, M))     # the losses stay on the device until here
         for m in range(M):
             mine = np.array([losses[k, m] for k, trials in enumerate(steps) if trials[m] is not None])
@@ -781,5 +956,5 @@ def join_corpora(corpora):
     return out
 
 
-__all__ = ["VadTrainerGPU", "train_vad", "dropout_mask", "DecoderTrainerGPU", "train_decoder", "decoder_dropout_mask", "trial_bounds",
+__all__ = ["VadTrainerGPU", "train_vad", "dropout_mask", "DeviceMaskSource", "device_dropout_masks", "dropout_scale", "DecoderTrainerGPU", "train_decoder", "decoder_dropout_mask", "trial_bounds",
            "DecoderGroupTrainerGPU", "train_decoders", "lockstep_schedule", "leave_one_day_out", "join_corpora", "LR", "ALPHA", "EPS"]

@@ -17,8 +17,8 @@
  * Parts 4-6 are the speech gate and the two recurrent models of the online path, Part 7 the acoustic labels of a
  * training corpus, Part 8 the two recurrent models over the trials of such a corpus (the validation passes of the
  * reference's training scripts), Part 9 the training of the neural detector, Part 10 that of the decoder, Part 11 the
- * spectrograms behind the reference's spectral analyses, Part 13 several decoders trained side by side, each described at its
- * declarations.
+ * spectrograms behind the reference's spectral analyses, Part 13 several decoders trained side by side, Part 14 the trainers'
+ * dropout masks drawn on the device, each described at its declarations.
  *
  * Error convention: functions returning int return 0 on success and a negative DSS_E* code on failure;
  * dss_last_error() gives a thread-local message.  Creators return NULL on failure (the reference's
@@ -797,6 +797,44 @@ int dss_dec_group_publish(dss_dec_group *g, int m, dss_dec *dec, void *hip_strea
  * a call in which every T is 0. */
 int dss_dec_group_step_dev(dss_dec_group *g, const dss_dec_group_trial *trials, int frames_are_f64, double *d_losses,
                            void *hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Part 14 -- the trainers' dropout masks drawn on the device (csrc/dropout.hip): the (T, H) / (T, 2H) multipliers that Parts 9, 10
+ * and 13 take as d_mask, from a stateless counter-based generator, so that no mask is drawn on the host and uploaded.  A mask is a
+ * pure function of (seed, draw, rows, width, p): it depends neither on the number of entries of a call, nor on an entry's place
+ * among them, nor on the order of calls, and a run is reproducible from its seed with no generator state to keep.
+ *
+ * The definition.  The block function is Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2,
+ * 3", SC'11): multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57; key increments 0x9E3779B9 (k0), 0xBB67AE85 (k1); ten rounds, each
+ *   (c0, c1, c2, c3) -> (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)),
+ * the key moved on by its increments after every round.  Known answers (counter / key -> block):
+ *   00000000 x 4 / 00000000 x 2                               -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *   ffffffff x 4 / ffffffff x 2                               -> 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *   243f6a88 85a308d3 13198a2e 03707344 / a4093822 299f31d0   -> d16cfe09 94fdcceb 5001e420 24126ea1
+ * A mask of rows x width float32, row-major: element e = t * width + j takes word e & 3 of the block with counter
+ * (lo32(e >> 2), hi32(e >> 2), lo32(draw), hi32(draw)) and key (lo32(seed), hi32(seed)); u = (float)(word >> 8) * 2^-24, exact in
+ * float32; the element is scale if u >= p, else 0.0f.  scale is the caller's float32 1 / (float32)(1.0 - p), an IEEE division
+ * done once on the host (2.0 at p = 0.5): the kernel only selects.  p == 0 is no mask at all (d_mask == NULL in Parts 9, 10, 13).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    float *d_mask;                  /* rows * width float32; 4-byte aligned (16-byte aligned masks are written in 16-byte stores) */
+    int rows, width;                /* rows == 0 (or width == 0): the entry is left alone and its pointer is not looked at */
+    unsigned long long seed, draw;
+    float p, scale;
+} dss_dropout_entry;
+/* The argument checks on their own (no device needed).  DSS_EINVAL with the reason in dss_last_error() for n_entries outside
+ * 1 .. 64, a NULL table, a negative size, and on an entry that is not empty: a null or not 4-byte aligned pointer, rows * width
+ * >= 2^31, p outside (0, 1) (NaN included), a scale that is not positive and finite; and for a table whose entries are all empty. */
+int dss_dropout_check(int n_entries, const dss_dropout_entry *e);
+/* Fills the masks of entries[0 .. n_entries), a HOST array read before the call returns, in ONE launch on hip_stream (the entry is
+ * blockIdx.y and travels with the kernel arguments); d_mask are device pointers.  No host synchronisation: calls may be enqueued
+ * back to back.  Nothing outside [d_mask, d_mask + rows * width) is written.  What dss_dropout_check refuses is refused before any
+ * launch. */
+int dss_dropout_masks_dev(const dss_dropout_entry *entries, int n_entries, void *hip_stream);
+/* The same masks, bit for bit, computed on the CPU (no device needed): d_mask are host pointers. */
+int dss_dropout_masks_host(const dss_dropout_entry *entries, int n_entries);
+/* Self-test of the block function on the CPU: out[4] = Philox4x32-10(counter[4], key[2]). */
+int dss_selftest_philox(const unsigned *counter, const unsigned *key, unsigned *out);
 
 #ifdef __cplusplus
 }
