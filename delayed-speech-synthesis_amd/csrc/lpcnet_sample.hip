@@ -24,6 +24,8 @@
 //               handed between the two waves through LDS as a tagged 8-byte word per row (no barrier).
 //   wave 7      GRU B, segments 2 and 4 + gates, and the scalar recurrences: mu-law / de-emphasis / PCM bookkeeping, kiss99
 //               thresholds, its own tree walk.
+// Issue priorities follow the phase (DSS_PHASE_PRIO): the relay waves run at 3 from barrier D to barrier C and at 0 from C to D, where
+// they only fetch the next sample's weights beside the dual-FC of waves 2, 3; waves 4, 5 run at 1 from D to B, ahead of waves 0, 1.
 // Summation order inside every row is exactly the C source's (one product at a time, ascending input),
 // and the library is built with -ffp-contract=off, so results are bit-identical to the scalar C path.
 #include <cstddef>
@@ -99,6 +101,16 @@
 #ifndef DSS_KNOCKOUT
 #define DSS_KNOCKOUT 0
 #endif
+#ifndef DSS_PHASE_PRIO
+#define DSS_PHASE_PRIO 1          // issue priorities that follow the phase (0: the relay waves at 3 throughout, everyone else at 0, as before):
+#endif                            //   D..B  waves 4, 5 at 1.  They carry the 10-block row groups, reach barrier B last (78 / 105 cycles of wait
+                                  //         against 320-360 on waves 0, 1) and share SIMDs 0, 1 with exactly those two waves.
+                                  //   C..D  the relay waves at 0.  Their 26 weight loads each for the next sample need only be there by barrier B;
+                                  //         at priority 3 they took issue slots from the dual-FC of waves 2, 3 on their SIMDs, which barrier D waits for.
+                                  //   Same-box A/B, sample kernel, 256 x 1 s, means of 4 alternations (profiles/phase_priority_experiment.md):
+                                  //   38.38 ms before, 38.14 with D..B alone, 37.77 with both; C..D alone 38.69 against 38.59 (barrier B then still
+                                  //   waits for waves 4, 5); waves 4, 5 at 1 throughout: no gain; wave 7 at 0 from D to B: 0.7 ms SLOWER (its
+                                  //   bookkeeping and the inputs of the speculation are on the path there).
 #ifndef GB4H
 #define GB4H 32
 #endif
@@ -328,7 +340,7 @@ __device__ __forceinline__ void dss_role_a(SampleLds &L, float *hblk_lds, const 
     const bool recur_first = m.h.gru_a_order == DSS_GRUA_RECUR_FIRST;     // wave-uniform (kernel argument)
     int cur = 0, seq = 0;
     float st = L.state_a[0][unit];
-    unsigned sa[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ta = 0;   // diagnostic build only
+    unsigned sa[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, ta = 0;   // diagnostic build only ([8]: barrier D .. the first embedding load is about to go out)
     f32x4 PR[2 * ZRC];                                           // z/r block products of the coming sample
     bool first_sample = true;
     DSS_H_CHAIN(L.state_a[0])                                    // first sample of this call
@@ -354,6 +366,7 @@ __device__ __forceinline__ void dss_role_a(SampleLds &L, float *hblk_lds, const 
             // code wave 7 runs for its bookkeeping) and looks the speculated indices up, so neither a barrier nor
             // wave 7 stands between the dual-FC and the embedding loads.
             int si, pi, ei;
+            const bool was_first = first_sample;
             if (first_sample) {
                 __syncthreads();                                                    // barrier A (first sample only)
                 si = L.idx[0]; pi = L.idx[1]; ei = L.idx[2];
@@ -367,7 +380,7 @@ __device__ __forceinline__ void dss_role_a(SampleLds &L, float *hblk_lds, const 
             // wave-uniform by construction: keep them scalar, so that the row offsets are SALU work and the loads take an
             // SGPR base (the first-sample path would otherwise drag them into VGPRs)
             si = __builtin_amdgcn_readfirstlane(si); pi = __builtin_amdgcn_readfirstlane(pi); ei = __builtin_amdgcn_readfirstlane(ei);
-            if (STAMP) ta = DSS_NOW();
+            if (STAMP) { const unsigned t = DSS_NOW(); if (!was_first) sa[8] += t - ta; ta = t; }
             {
                 // the nine embedding values of this lane: three 12-byte loads from the lane-ordered copies of the tables
                 // (m.embed_lane: [index][lane][gate]), 768 contiguous bytes per wave and table
@@ -430,6 +443,7 @@ __device__ __forceinline__ void dss_role_a(SampleLds &L, float *hblk_lds, const 
                 if (STAMP) { asm volatile("" :: "v"(st)); const unsigned t = DSS_NOW(); sa[3] += t - ta; ta = t; }
             }
             __syncthreads();                                                        // barrier B
+            if (DSS_PHASE_PRIO && !HAS_FC) __builtin_amdgcn_s_setprio(0);
             if (STAMP) { const unsigned t = DSS_NOW(); sa[4] += t - ta; ta = t; }
             else if (DSS_RELAY_STAMP) ta = DSS_NOW();
 #if DSS_KNOCKOUT      /* development builds only (results WRONG on purpose): what the relay's SIMD neighbours cost it, profiles/r5_latency_kernel_experiment.md */
@@ -496,13 +510,14 @@ __device__ __forceinline__ void dss_role_a(SampleLds &L, float *hblk_lds, const 
                 if (lane == 0) { L.bits[2 * wave] = (unsigned)mask; L.bits[2 * wave + 1] = (unsigned)(mask >> 32); }
             }
             __syncthreads();                                                        // barrier D
+            if (DSS_PHASE_PRIO && !HAS_FC) __builtin_amdgcn_s_setprio(1);      // waves 4, 5 ahead of waves 0, 1 until barrier B
             if (STAMP) { const unsigned t = DSS_NOW(); sa[7] += t - ta; ta = t; }
             cur ^= 1;
         }
     }
     __syncthreads();                                                                // final barrier
     if (STAMP && lane == 0 && b.trace_exc)
-        for (int k = 0; k < 8; ++k) b.trace_exc[((size_t)utt * 6 + wave) * 8 + k] = (float)sa[k];
+        for (int k = 0; k < 9; ++k) b.trace_exc[((size_t)utt * 6 + wave) * 9 + k] = (float)sa[k];
     if (DSS_RELAY_STAMP && !STAMP && lane == 0 && blockIdx.x == 0)
         reinterpret_cast<unsigned *>(pcm_out_dbg + (size_t)utt * n_frames * DSS_FRAME_SIZE)[16 + wave] = sa[5];
     b.gru_a_state[(size_t)slot * NA + unit] = st;
@@ -606,8 +621,10 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
                 DSS_SPECULATE(lane)                          // this wave is idle from here to barrier B: candidates 0..63
                 if (RS) r6[4] += DSS_NOW() - t6;
                 __syncthreads();                                                        // barrier C
+                if (DSS_PHASE_PRIO) __builtin_amdgcn_s_setprio(0);   // the loads below must not stand in front of wave 2's dual-FC
                 DSS_GBG_LOADS(GB3, (GB1 + GB2) / 4)          // the next sample's segment 3 weights (nothing else to do before barrier B)
                 __syncthreads();                                                        // barrier D
+                if (DSS_PHASE_PRIO) __builtin_amdgcn_s_setprio(3);
                 cur ^= 1;
             }
         }
@@ -761,10 +778,12 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
                 }
 #endif
                 __syncthreads();                                                        // barrier C
+                if (DSS_PHASE_PRIO) __builtin_amdgcn_s_setprio(0);   // the loads below must not stand in front of wave 3's dual-FC
                 if (RS) r7[6] += DSS_NOW() - t_prev;
                 if (STAMP) { const unsigned t = DSS_NOW(); stamp_acc[3] += t - t_prev; t_prev = t; }
                 DSS_GBG_LOADS(GB2, GB1 / 4)                  // the next sample's segment 2 weights, while the dual-FC waves work
                 __syncthreads();                                                        // barrier D
+                if (DSS_PHASE_PRIO) __builtin_amdgcn_s_setprio(3);
                 if (STAMP) { const unsigned t = DSS_NOW(); stamp_acc[4] += t - t_prev; t_prev = t; }
                 cur ^= 1;
                 int val;

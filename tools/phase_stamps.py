@@ -35,11 +35,15 @@ if MODE == 1 and B == 1:      # one workgroup: the relay waves' own way points i
           f"summed + published {w6[3]:.0f} | wave 7 segment 4 products ready {w7[3]:.0f}, has the sums {w7[4]:.0f}, summed {w7[5]:.0f}")
 rawA = np.empty((F * 160,), np.float32)
 chunks = []
-for k in range((B * 48 + rawA.size - 1) // rawA.size):
+NSA = 9                                                    # stamp slots per GRU A wave
+for k in range((B * 6 * NSA + rawA.size - 1) // rawA.size):
     _lib.check(gpu._L.dss_lpcnet_batch_tap(gpu._h, k, 3, rawA.ctypes.data, rawA.size))
     chunks.append(rawA.copy())
-sa = np.concatenate(chunks)[: B * 48].reshape(B, 6, 8) / n
-namesA = ["A->products", "emb wait+gz", "z/r sums", "activations", "wait B", "h chain", "wait C", "FC+wait D"]
+sa = np.concatenate(chunks)[: B * 6 * NSA].reshape(B, 6, NSA) / n
+# "D->1st load": barrier D .. the first embedding load is about to be issued (tree walk and whatever stands before that load);
+# "loads issued": from there until all three are out (the index extraction of the other two rows included)
+namesA = ["loads issued", "emb wait+gz", "z/r sums", "activations", "wait B", "h chain", "wait C", "FC+wait D", "D->1st load"]
 print("role A view (cycles per sample, mean over utterances), per wave:")
 for w in range(6):
-    print(f"  wave {w}: " + "  ".join(f"{namesA[k]}={sa[:, w, k].mean():7.1f}" for k in range(8)))
+    print(f"  wave {w}: " + "  ".join(f"{namesA[k]}={sa[:, w, k].mean():7.1f}" for k in range(NSA)))
+print(f"  D -> all embedding loads issued, mean over waves 0..5: {(sa[:, :, 8] + sa[:, :, 0]).mean():7.1f}")
