@@ -296,6 +296,21 @@ struct DssHgaDev {
     const double *zs_mean, *zs_std;   // optional z-score of the frames, [C] each (device-resident entry points)
     int force_path;    // tests / A-B timing only: 0 choose, 1 hga_fused_kernel, 2 the three-launch form
 };
+// The LDS ring of hga_fused_kernel / hga_trials_kernel: a frame, one shift and one tile of DSS_HGA_TT steps (+ 2) of rows,
+// rounded up to a multiple of 8; 16 columns of float64 per row.  The one-launch forms serve a window shape iff the ring fits
+// DSS_HGA_RING_LIMIT bytes beside the kernels' static tiles.  dss_launch_hga, dss_launch_hga_trials and dss_hga_plan (which
+// reports the decision without a device) all take it from here.
+#define DSS_HGA_TT 64
+#define DSS_HGA_RING_LIMIT (40 * 1024)
+struct DssHgaRing { int rows; size_t bytes; bool fused; };
+static inline DssHgaRing dss_hga_ring(int frame_length, int overlap)
+{
+    DssHgaRing r;
+    r.rows = (frame_length + (frame_length - overlap) + DSS_HGA_TT + 2 + 7) & ~7;
+    r.bytes = (size_t)r.rows * 16 * sizeof(double);
+    r.fused = r.bytes <= DSS_HGA_RING_LIMIT;
+    return r;
+}
 // the front end of a call (local/common.py:16-58,308-345): raw amplifier rows (S, n, c_raw) instead of (S, n, C)
 struct DssHgaFrontDev {
     const double *raw;

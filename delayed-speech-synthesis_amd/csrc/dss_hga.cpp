@@ -42,6 +42,28 @@ extern "C" int dss_hga_log_power(const double *data, int T, int C, int sr, float
     return DSS_OK;
 }
 
+// hga_optimized.pyx:72-74 (float32 products truncated to int): rows of a frame and rows between two frames
+static void hga_window_rows(int fs, float window_length, float window_shift, int *frame_length, int *shift)
+{
+    *shift = (int)(window_shift * fs);
+    *frame_length = (int)(window_length * fs);
+}
+
+/* What serves a window shape, without a device: out = {frame_length, shift, overlap, ring_rows, ring_bytes, fused}.  The ring is
+ * dss_hga_ring's (csrc/dss_common.h), the one dss_launch_hga and dss_launch_hga_trials size their launches by: fused = 1 means
+ * one launch per call (hga_fused_kernel) and a serviceable trial list, 0 the three-launch form and no trial list. */
+extern "C" int dss_hga_plan(int fs, float window_length, float window_shift, int out[6])
+{
+    if (!out) { dss_set_error("nowhere to write the plan"); return DSS_EINVAL; }
+    int fl, shift;
+    hga_window_rows(fs, window_length, window_shift, &fl, &shift);
+    if (fs <= 0 || fl <= 0 || shift <= 0 || shift > fl) { dss_set_error("bad window shape"); return DSS_EINVAL; }
+    if (fl > (1 << 24)) { dss_set_error("a frame of %d rows is too long", fl); return DSS_EINVAL; }
+    const DssHgaRing ring = dss_hga_ring(fl, fl - shift);
+    out[0] = fl; out[1] = shift; out[2] = fl - shift; out[3] = ring.rows; out[4] = (int)ring.bytes; out[5] = ring.fused ? 1 : 0;
+    return DSS_OK;
+}
+
 struct DssHgaTrialDesc { long long in_row, out_row; int n, W, zero_rows, pad; };       // HgaTrialDesc of csrc/hga_kernels.hip
 
 struct dss_hga {
@@ -103,9 +125,8 @@ extern "C" dss_hga *dss_hga_create(int n_streams, int n_channels, int fs, float 
     DssHgaDev &d = h->d;
     memset(&d, 0, sizeof(d));
     d.S = n_streams; d.C = n_channels; d.fs = fs; d.nsec = n_sections; d.wl = window_length; d.ws = window_shift;
-    // hga_optimized.pyx:72-74 (float32 products truncated to int)
-    const int shift = (int)(window_shift * fs);
-    d.frame_length = (int)(window_length * fs);
+    int shift;
+    hga_window_rows(fs, window_length, window_shift, &d.frame_length, &shift);
     d.overlap = d.frame_length - shift;
     for (int q = 0; q < n_sections; ++q)
         for (int k = 0; k < 6; ++k) { d.sos[0][q][k] = sos_hg[q * 6 + k]; d.sos[1][q][k] = sos_fh[q * 6 + k]; }
@@ -340,7 +361,8 @@ extern "C" int dss_hga_extract_raw(dss_hga *h, const double *raw, int n, double 
 // zero-padded frame; a chunk no longer than the frame shift is what the reference's frame buffer must not be given (pyx:57).
 extern "C" int dss_hga_trial_frames_for(int fs, float wl, float ws, int len)
 {
-    const int shift = (int)(ws * fs), fl = (int)(wl * fs);
+    int shift, fl;
+    hga_window_rows(fs, wl, ws, &fl, &shift);
     if (fs <= 0 || fl <= 0 || shift <= 0 || shift > fl) { dss_set_error("bad window shape"); return DSS_EINVAL; }
     if (len <= shift) { dss_set_error("a trial of %d rows is not longer than the frame shift (%d rows)", len, shift); return DSS_EINVAL; }
     const int W = dss_hga_num_windows(len >= fl ? len : fl, fs, wl, ws);
@@ -426,12 +448,45 @@ extern "C" int dss_hga_apply_patches(double *frames, long long N, int C, int n_p
     return DSS_OK;
 }
 
+// numpy's pairwise_sum over a contiguous run of n elements (element i: a[i], or with sq (a[i] - m) * (a[i] - m)): sequential
+// below 8 elements; up to 128 eight running sums over blocks of eight, ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the remainder
+// in order; longer runs are halved (the left half a multiple of 8) and the halves' sums added
+static double hga_pairwise_sum(const double *a, long long n, double m, bool sq)
+{
+    auto at = [&](long long i) { const double d = a[i] - m; return sq ? d * d : a[i]; };
+    if (n < 8) {
+        double r = at(0);
+        for (long long i = 1; i < n; ++i) r += at(i);
+        return r;
+    }
+    if (n <= 128) {
+        double r[8];
+        for (int u = 0; u < 8; ++u) r[u] = at(u);
+        long long i = 8;
+        for (; i < n - (n % 8); i += 8)
+            for (int u = 0; u < 8; ++u) r[u] += at(i + u);
+        double sum = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (; i < n; ++i) sum += at(i);
+        return sum;
+    }
+    long long n2 = n / 2;
+    n2 -= n2 % 8;
+    const double left = hga_pairwise_sum(a, n2, m, sq);
+    return left + hga_pairwise_sum(a + n2, n - n2, m, sq);
+}
+
 // np.vstack([np.mean(x, axis=0), np.std(x, axis=0)]) of a C-contiguous (N, C) array, in numpy's order: rows are added one
-// after the other (row 0, += row 1, ...), / N; std from d = x - mean, d * d summed the same way, / N, sqrt
+// after the other (row 0, += row 1, ...), / N; std from d = x - mean, d * d summed the same way, / N, sqrt.  ONE column is one
+// contiguous run, which numpy sums with its pairwise kernel instead (hga_pairwise_sum), the squares too.
 extern "C" int dss_hga_column_stats(const double *frames, long long N, int C, double *out)
 {
     if (!frames || !out || N <= 0 || C <= 0) { dss_set_error("column statistics need at least one frame"); return DSS_EINVAL; }
     double *mean = out, *sd = out + C;
+    if (C == 1) {
+        mean[0] = hga_pairwise_sum(frames, N, 0.0, false) / (double)N;
+        sd[0] = sqrt(hga_pairwise_sum(frames, N, mean[0], true) / (double)N);
+        return DSS_OK;
+    }
     for (int c = 0; c < C; ++c) mean[c] = frames[c];
     for (long long i = 1; i < N; ++i)
         for (int c = 0; c < C; ++c) mean[c] += frames[(size_t)i * C + c];

@@ -42,6 +42,7 @@ __device__ __forceinline__ int hga_win_stop(int start, float wl, int sr)
 // 128-byte row segments; lane 2*nsec-1 writes the filtered sample to the column's row buffer at row0 + t.
 #define HGA_TT 64
 #define HGA_WTAB 256          // windows whose row ranges the fused kernel tabulates in LDS (2 KB)
+static_assert(HGA_TT == DSS_HGA_TT, "the ring of dss_hga_ring (dss_common.h) is sized for this tile");
 
 // lanes 1..15 of every row receive their left neighbour's `y`; lane 0 (no neighbour) keeps `x`: the column's input
 __device__ __forceinline__ double hga_shift_in(double x, double y)
@@ -536,11 +537,10 @@ int dss_launch_hga_trials(const DssHgaDev &h, const double *d_data, const void *
     if (n_trials <= 0) return DSS_OK;
     HgaSos sos;
     memcpy(&sos, h.sos, sizeof(sos));
-    const int shift = h.frame_length - h.overlap;
-    int ring_rows = h.frame_length + shift + HGA_TT + 2;
-    ring_rows = (ring_rows + 7) & ~7;
-    const size_t ring_bytes = (size_t)ring_rows * 16 * sizeof(double);
-    if (ring_bytes > 40 * 1024) {
+    const DssHgaRing ring = dss_hga_ring(h.frame_length, h.overlap);
+    const int ring_rows = ring.rows;
+    const size_t ring_bytes = ring.bytes;
+    if (!ring.fused) {
         dss_set_error("HGA trials: a frame of %d rows does not fit the kernel's ring", h.frame_length);
         return DSS_EINVAL;
     }
@@ -665,8 +665,79 @@ hga_colstats_kernel(const double *__restrict__ frames, long N, int C, double *__
     out[C + c] = sqrt(sq / (double)N);
 }
 
+// ONE column (C == 1) is one contiguous run, and numpy sums a contiguous run with its pairwise kernel, not row by row: below 8
+// elements in order; up to 128 eight running sums over blocks of eight, ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the remainder
+// in order; a longer run is halved (the left half a multiple of 8) and the halves' sums are added.  Element i is a[i], or with
+// sq (a[i] - m) * (a[i] - m).  The halving is walked with an explicit stack of (offset, length, stage, left sum): a run of n
+// elements nests ceil(log2(n / 128)) deep, 64 levels hold any long.
+__device__ double hga_pairwise_run(const double *__restrict__ a, long n, double m, bool sq)
+{
+#define HGA_PW_AT(I) (sq ? (a[I] - m) * (a[I] - m) : a[I])
+    if (n < 8) {
+        double r = HGA_PW_AT(0);
+        for (long i = 1; i < n; ++i) r += HGA_PW_AT(i);
+        return r;
+    }
+    double r[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) r[u] = HGA_PW_AT(u);
+    long i = 8;
+    for (; i < n - (n % 8); i += 8) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) r[u] += HGA_PW_AT(i + u);
+    }
+    double sum = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; ++i) sum += HGA_PW_AT(i);
+    return sum;
+#undef HGA_PW_AT
+}
+
+__device__ double hga_pairwise_sum(const double *__restrict__ a, long n, double m, bool sq)
+{
+    long off[64], len[64];
+    double left[64];
+    int stage[64];
+    int sp = 0;
+    off[0] = 0; len[0] = n; stage[0] = 0;
+    double ret = 0.0;
+    while (sp >= 0) {
+        if (len[sp] <= 128) { ret = hga_pairwise_run(a + off[sp], len[sp], m, sq); --sp; continue; }
+        long n2 = len[sp] / 2;
+        n2 -= n2 % 8;
+        if (stage[sp] == 0) {                              // the left half first
+            stage[sp] = 1;
+            if (sp + 1 >= 64) return ret;                  // unreachable for a long n; never past the stack
+            off[sp + 1] = off[sp]; len[sp + 1] = n2; stage[sp + 1] = 0;
+            ++sp;
+        } else if (stage[sp] == 1) {                       // then the right half
+            left[sp] = ret;
+            stage[sp] = 2;
+            off[sp + 1] = off[sp] + n2; len[sp + 1] = len[sp] - n2; stage[sp + 1] = 0;
+            ++sp;
+        } else {
+            ret = left[sp] + ret;
+            --sp;
+        }
+    }
+    return ret;
+}
+
+__global__ void __launch_bounds__(64)
+hga_colstats_one_kernel(const double *__restrict__ frames, long N, double *__restrict__ out)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const double m = hga_pairwise_sum(frames, N, 0.0, false) / (double)N;
+    out[0] = m;
+    out[1] = sqrt(hga_pairwise_sum(frames, N, m, true) / (double)N);
+}
+
 int dss_launch_hga_colstats(const double *d_frames, long N, int C, double *d_out, hipStream_t st)
 {
+    if (C == 1) {
+        hipLaunchKernelGGL(hga_colstats_one_kernel, dim3(1), dim3(64), 0, st, d_frames, N, d_out);
+        DSS_HIP_CHECK(hipGetLastError());
+        return DSS_OK;
+    }
     hipLaunchKernelGGL(hga_colstats_kernel, dim3((C + 63) / 64), dim3(64), 0, st, d_frames, N, C, d_out);
     DSS_HIP_CHECK(hipGetLastError());
     return DSS_OK;
@@ -745,14 +816,13 @@ int dss_launch_hga(const DssHgaDev &h, const double *d_data, const DssHgaFrontDe
     HgaSos sos;
     memcpy(&sos, h.sos, sizeof(sos));
     const long pairs = (long)h.S * h.C;
-    const int shift = h.frame_length - h.overlap;
     if (fe) { dss_set_error("HGA: raw amplifier rows go through dss_launch_hga_frontend first"); return DSS_EINVAL; }
     if (h.force_path != 2) {   // fused form when the ring (frame + shift + one tile of rows) fits beside the tiles
         const int TT = HGA_TT;
-        int ring_rows = h.frame_length + shift + TT + 2;
-        ring_rows = (ring_rows + 7) & ~7;
-        const size_t ring_bytes = (size_t)ring_rows * 16 * sizeof(double);
-        if (ring_bytes <= 40 * 1024 && rows - h.overlap + TT <= (1 << 30) && h.overlap <= ring_rows && row0 <= ring_rows) {
+        const DssHgaRing ring = dss_hga_ring(h.frame_length, h.overlap);
+        const int ring_rows = ring.rows;
+        const size_t ring_bytes = ring.bytes;
+        if (ring.fused && rows - h.overlap + TT <= (1 << 30) && h.overlap <= ring_rows && row0 <= ring_rows) {
             hipLaunchKernelGGL(hga_fused_kernel, dim3((unsigned)((pairs + 15) / 16)), dim3(256), ring_bytes, st, d_data, h.zi,
                                    h.rows, d_out, sos, h.S, h.C, n, h.nsec, row0, h.cap_rows, zero_rows, rows, W, h.overlap, h.fs, h.wl,
                                    h.ws, apply_log, ring_rows, h.zs_mean, h.zs_std);

@@ -111,6 +111,7 @@ def _declare(L):
         "dss_hga_extract_wire_dev": (i, [vp, vp, i, vp, i, vp]),
         "dss_hga_set_zscore": (i, [vp, vp, vp]),
         "dss_selftest_hga_force_path": (i, [vp, i]),
+        "dss_hga_plan": (i, [i, f, f, vp]),
         "dss_hga_trial_frames": (i, [vp, i]),
         "dss_hga_trial_frames_for": (i, [i, f, f, i]),
         "dss_hga_check_trials": (i, [i, f, f, C.c_longlong, i, vp, vp]),

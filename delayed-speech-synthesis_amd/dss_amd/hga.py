@@ -1,6 +1,8 @@
 """High-gamma feature extraction on MI355X: Python host side of Part 3 of include/dss_hip.h."""
 from __future__ import annotations
 
+import collections
+import ctypes
 from typing import Optional
 
 import numpy as np
@@ -66,6 +68,18 @@ def log_power(data: np.ndarray, sr: int, wl: float, ws: float) -> np.ndarray:
     if W:
         _lib.check(L.dss_hga_log_power(d.ctypes.data, d.shape[0], d.shape[1], int(sr), wl, ws, out.ctypes.data))
     return out
+
+
+Plan = collections.namedtuple("Plan", "frame_length shift overlap ring_rows ring_bytes fused")
+
+
+def plan(fs: int = 1000, window_length: float = 0.05, window_shift: float = 0.01) -> Plan:
+    """What serves a window shape (``dss_hga_plan``; needs no GPU): rows per frame and between frames, the rows and bytes of the
+    one-launch kernels' LDS ring, and ``fused`` -- 1: one launch per call and a serviceable trial list, 0: the three-launch
+    form and no trial list.  The launch code takes its ring from the same helper."""
+    out = (ctypes.c_int * 6)()
+    _lib.check(_lib.load().dss_hga_plan(int(fs), window_length, window_shift, ctypes.addressof(out)))
+    return Plan(*out)
 
 
 def trial_frames(length: int, fs: int = 1000, window_length: float = 0.05, window_shift: float = 0.01) -> int:
@@ -161,6 +175,10 @@ class HgaExtractorGPU:
 
     def reset(self):
         _lib.check(self._L.dss_hga_reset(self._h))
+
+    def plan(self) -> Plan:
+        """The form that serves this extractor's window shape (module-level ``plan``)."""
+        return plan(self.fs, self.wl, self.ws)
 
     def frames_for(self, n: int) -> int:
         return int(self._L.dss_hga_frames_for(self._h, int(n)))

@@ -324,9 +324,18 @@ int dss_hga_apply_patches(double *frames, long long N, int C, int n_patches, con
                           const int *nb_off);
 /* out (2, C) = vstack([np.mean(frames, axis=0), np.std(frames, axis=0)]) in numpy's summation order for a C-contiguous
  * (N, C) array: rows added one after the other, / N; std from d = x - mean, d * d, summed the same way, / N, sqrt.  Bit-identical
- * to numpy on the same frames, on the host and on the device (one lane per column walks the rows: the order is the contract). */
+ * to numpy on the same frames, on the host and on the device (one lane per column walks the rows: the order is the contract).
+ * C == 1 is one contiguous run, which numpy sums with its pairwise kernel instead (eight running sums up to 128 elements,
+ * halves beyond); both forms follow it there, for the sum and for the sum of squares. */
 int dss_hga_column_stats(const double *frames, long long N, int C, double *out);
 int dss_hga_column_stats_dev(const double *d_frames, long long N, int C, double *d_out, void *hip_stream);
+/* Which form serves a window shape, without a handle or a device: out = {frame_length, shift, overlap, ring_rows, ring_bytes,
+ * fused}.  frame_length and shift are the float32 products of hga_optimized.pyx:72-74; ring_rows = (frame_length + shift + 66
+ * + 7) & ~7 rows of 16 float64 columns is the LDS ring of the one-launch kernels, ring_bytes = 128 ring_rows; fused = 1 iff
+ * ring_bytes <= 40960: dss_hga_extract* then run hga_fused_kernel and the trial entry points are serviceable; with 0 the
+ * extractor runs its three-launch form and a trial list is refused.  The launch code takes the same values from the same
+ * helper.  Returns 0, or DSS_EINVAL for a shape without a positive shift no longer than the frame. */
+int dss_hga_plan(int fs, float window_length, float window_shift, int out[6]);
 /* Tests and A/B timing only: which kernel form serves this extractor.  0 = choose (default: hga_fused_kernel; three
  * launches when its ring does not fit LDS), 1 = hga_fused_kernel, 2 = the three-launch form. */
 int dss_selftest_hga_force_path(dss_hga *h, int path);
