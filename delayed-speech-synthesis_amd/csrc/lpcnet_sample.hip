@@ -21,11 +21,13 @@
 //               new state) and the speculation over the 256 possible excitations -- hidden under GRU B.
 //               C..D (waves 0..3): dual-FC logits of all 255 tree nodes -> decision bits.
 //   wave 6      GRU B, segments 1 and 3 of the chain (see GB1..GB4 below): lane = output row, one sequential chain per row,
-//               handed between the two waves through LDS as a tagged 8-byte word per row (no barrier).
-//   wave 7      GRU B, segments 2 and 4 + gates, and the scalar recurrences: mu-law / de-emphasis / PCM bookkeeping, kiss99
-//               thresholds, its own tree walk.
-// Issue priorities follow the phase (DSS_PHASE_PRIO): the relay waves run at 3 from barrier D to barrier C and at 0 from C to D, where
-// they only fetch the next sample's weights beside the dual-FC of waves 2, 3; waves 4, 5 run at 1 from D to B, ahead of waves 0, 1.
+//               handed between the two waves through LDS as a tagged 8-byte word per row (no barrier).  Once it has handed
+//               segment 3 over: a quarter of the speculation, and the kiss99 generator with the sample's eight thresholds.
+//   wave 7      GRU B, segments 2 and 4 + gates, and the scalar recurrences: mu-law / de-emphasis / PCM bookkeeping, its own
+//               tree walk.
+// Issue priorities follow the phase (DSS_PHASE_PRIO): the relay waves run at 3 from barrier D to barrier C (wave 6 only until it has
+// handed segment 3 over) and at 0 from C to D, where they only fetch the next sample's weights beside the dual-FC of waves 2, 3;
+// from D to B waves 4, 5 run at 1, ahead of waves 0, 1, and wave 3 at 3 beside wave 7.
 // Summation order inside every row is exactly the C source's (one product at a time, ascending input),
 // and the library is built with -ffp-contract=off, so results are bit-identical to the scalar C path.
 #include <cstddef>
@@ -111,6 +113,9 @@
                                   //   38.38 ms before, 38.14 with D..B alone, 37.77 with both; C..D alone 38.69 against 38.59 (barrier B then still
                                   //   waits for waves 4, 5); waves 4, 5 at 1 throughout: no gain; wave 7 at 0 from D to B: 0.7 ms SLOWER (its
                                   //   bookkeeping and the inputs of the speculation are on the path there).
+                                  //   Later (profiles/wave7_dtob_experiment.md), once wave 7 no longer waits for the threshold table between D and B:
+                                  //   D..B  wave 3 at 3, level with wave 7 on its SIMD;  B..C  wave 6 at 0 from its last hand-over on (speculation
+                                  //         and thresholds are needed at barrier C only; its SIMD neighbour, wave 2, ends its h chain 150 cycles before C).
 #ifndef GB4H
 #define GB4H 32
 #endif
@@ -444,6 +449,7 @@ __device__ __forceinline__ void dss_role_a(SampleLds &L, float *hblk_lds, const 
             }
             __syncthreads();                                                        // barrier B
             if (DSS_PHASE_PRIO && !HAS_FC) __builtin_amdgcn_s_setprio(0);
+            if (DSS_PHASE_PRIO && HAS_FC && wave == 3) __builtin_amdgcn_s_setprio(0);
             if (STAMP) { const unsigned t = DSS_NOW(); sa[4] += t - ta; ta = t; }
             else if (DSS_RELAY_STAMP) ta = DSS_NOW();
 #if DSS_KNOCKOUT      /* development builds only (results WRONG on purpose): what the relay's SIMD neighbours cost it, profiles/r5_latency_kernel_experiment.md */
@@ -511,6 +517,7 @@ __device__ __forceinline__ void dss_role_a(SampleLds &L, float *hblk_lds, const 
             }
             __syncthreads();                                                        // barrier D
             if (DSS_PHASE_PRIO && !HAS_FC) __builtin_amdgcn_s_setprio(1);      // waves 4, 5 ahead of waves 0, 1 until barrier B
+            if (DSS_PHASE_PRIO && HAS_FC && wave == 3) __builtin_amdgcn_s_setprio(3);      // wave 3 level with wave 7, which shares its SIMD
             if (STAMP) { const unsigned t = DSS_NOW(); sa[7] += t - ta; ta = t; }
             cur ^= 1;
         }
@@ -585,6 +592,7 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
         const int row = lane < NB3 ? lane : 0;
         __builtin_amdgcn_s_setprio(3);               // everything this wave does is on the sample's critical path
         const float gbb0 = m.gru_b_bias[row];
+        DssKiss99 rng = {b.rng[slot * 4 + 0], b.rng[slot * 4 + 1], b.rng[slot * 4 + 2], b.rng[slot * 4 + 3]};
         int cur = 0, seq = 0;
         unsigned r6[5] = {0, 0, 0, 0, 0};     // diagnostic build: cycles from barrier B to the relay's way points on this wave
         __syncthreads();                                             // matches role A's prologue barrier
@@ -618,8 +626,21 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
 #if DSS_RELAY_MASK
                 }
 #endif
+                if (DSS_PHASE_PRIO) __builtin_amdgcn_s_setprio(0);   // nothing below is needed before barrier C: wave 2's h chain first
                 DSS_SPECULATE(lane)                          // this wave is idle from here to barrier B: candidates 0..63
                 if (RS) r6[4] += DSS_NOW() - t6;
+                {   // The 8 thresholds the dual-FC lanes read behind barrier C of THIS sample (their last readers finished before
+                    // barrier D of the sample before: one buffer).  Drawn here, in ~800 idle cycles that cover the table's L2 latency:
+                    // on wave 7, between D and B, that latency decided when the wave reached barrier B, and no other stretch of wave 7
+                    // is idle (profiles/wave7_dtob_experiment.md).  One pair of draws per synthesised sample, as in lpcnet.c.
+                    const uint32_t r0 = dss_kiss99_rand(rng);
+                    const uint32_t r1 = dss_kiss99_rand(rng);
+                    rng.z = dss_uniform(rng.z); rng.w = dss_uniform(rng.w); rng.jsr = dss_uniform(rng.jsr); rng.jcong = dss_uniform(rng.jcong);
+                    if (lane < 8) {
+                        const uint32_t r = lane < 4 ? r0 : r1;
+                        L.thr[lane] = m.logit_table[(r >> (8 * (lane & 3))) & 0xFF];     // 1 KB table, L2/L1 resident
+                    }
+                }
                 __syncthreads();                                                        // barrier C
                 if (DSS_PHASE_PRIO) __builtin_amdgcn_s_setprio(0);   // the loads below must not stand in front of wave 2's dual-FC
                 DSS_GBG_LOADS(GB3, (GB1 + GB2) / 4)          // the next sample's segment 3 weights (nothing else to do before barrier B)
@@ -633,6 +654,9 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
             for (int k = 0; k < 4; ++k) b.trace_pcm[72 + k] = (float)r6[k];
         if (DSS_RELAY_STAMP && !STAMP && lane == 0 && blockIdx.x == 0)      // development builds only: into the (silent) first frame's PCM
             for (int k = 0; k < 5; ++k) reinterpret_cast<unsigned *>(pcm_out + (size_t)utt * n_frames * DSS_FRAME_SIZE)[8 + k] = r6[k];
+        if (lane == 0) {
+            b.rng[slot * 4 + 0] = rng.z; b.rng[slot * 4 + 1] = rng.w; b.rng[slot * 4 + 2] = rng.jsr; b.rng[slot * 4 + 3] = rng.jcong;
+        }
     } else {
         // =====================================================================================================
         // role B2 + S (wave 7): GRU B, segments 2 and 4, and gates; scalar recurrences replicated across lanes
@@ -661,8 +685,7 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
         float ls_lane = b.last_sig[(size_t)slot * DSS_LPC_ORDER + (lane & (DSS_LPC_ORDER - 1))], lpc_lane = 0.f;
         float deemph = b.deemph[slot];
         int last_exc = b.last_exc[slot];
-        DssKiss99 rng = {b.rng[slot * 4 + 0], b.rng[slot * 4 + 1], b.rng[slot * 4 + 2], b.rng[slot * 4 + 3]};
-        unsigned stamp_acc[6] = {0, 0, 0, 0, 0, 0};
+        unsigned stamp_acc[7] = {0, 0, 0, 0, 0, 0, 0}, t_d = 0;     // [6]: barrier D .. this wave's arrival at barrier B
         unsigned t_prev = 0, r7[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // r7: cycles from barrier B to the relay's way points on this wave
         int cur = 0, seq = 0;
         float pred = 0.f, upd_pred = 0.f;
@@ -707,15 +730,6 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
                 }
                 if (STAMP) { const unsigned t = DSS_NOW(); stamp_acc[1] += t - t_prev; t_prev = t; }
                 if (upd_pending) { DSS_S_UPDATE() }                                     // previous sample's bookkeeping
-                {   // off the critical path: this sample's 8 thresholds and GRU B's recurrent half
-                    const uint32_t r0 = dss_kiss99_rand(rng);
-                    const uint32_t r1 = dss_kiss99_rand(rng);
-                    rng.z = dss_uniform(rng.z); rng.w = dss_uniform(rng.w); rng.jsr = dss_uniform(rng.jsr); rng.jcong = dss_uniform(rng.jcong);
-                    if (lane < 8) {
-                        const uint32_t r = lane < 4 ? r0 : r1;
-                        L.thr[lane] = m.logit_table[(r >> (8 * (lane & 3))) & 0xFF];     // 1 KB table, L2/L1 resident
-                    }
-                }
                 {   // inputs of the speculation the GRU A waves run between barriers B and C
                     const bool last_of_frame = (i == DSS_FRAME_SIZE - 1);
                     next_exists = !(last_of_frame && f == nf - 1);
@@ -729,10 +743,15 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
                     if (lane < DSS_LPC_ORDER) L.spec_prod[lane] = lane ? prod : lp;
                     if (lane == 0) L.spec_pred = pred;
                 }
+                // GRU B's recurrent half, off the critical path -- and pinned here: left alone, the compiler keeps the 32 values read
+                // from LDS in registers through the whole relay and forms the 16 products and sums among the last sums of segment 4,
+                // ~130 cycles at the very end of the sample's longest chain
                 float rec = gbb1;
 #pragma unroll
                 for (int j = 0; j < NB; ++j) rec += L.gb_wrec[j * NB3 + row] * L.state_b[j];
-                const float sb_old = L.state_b[lane & (NB - 1)];     // the h lanes' own unit: read here, not after the chain
+                float sb_old = L.state_b[lane & (NB - 1)];           // the h lanes' own unit: read here, not after the chain
+                asm volatile("" : "+v"(rec), "+v"(sb_old));
+                if (STAMP && seq > 1) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); stamp_acc[6] += DSS_NOW() - t_d; }
                 __syncthreads();                                                        // barrier B
                 if (STAMP) { const unsigned t = DSS_NOW(); stamp_acc[2] += t - t_prev; t_prev = t; }
                 else if (RS) t_prev = DSS_NOW();
@@ -784,7 +803,7 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
                 DSS_GBG_LOADS(GB2, GB1 / 4)                  // the next sample's segment 2 weights, while the dual-FC waves work
                 __syncthreads();                                                        // barrier D
                 if (DSS_PHASE_PRIO) __builtin_amdgcn_s_setprio(3);
-                if (STAMP) { const unsigned t = DSS_NOW(); stamp_acc[4] += t - t_prev; t_prev = t; }
+                if (STAMP) { const unsigned t = DSS_NOW(); stamp_acc[4] += t - t_prev; t_prev = t; t_d = t; }
                 cur ^= 1;
                 int val;
                 DSS_TREE_WALK(val)
@@ -808,6 +827,7 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
         __syncthreads();                                                                // final barrier
         if (STAMP && lane == 0 && b.trace_pcm) {        // diagnostic build only
             for (int k = 0; k < 6; ++k) b.trace_pcm[(size_t)utt * 6 + k] = (float)stamp_acc[k];
+            b.trace_pcm[(size_t)gridDim.x * 6 + utt] = (float)stamp_acc[6];      // behind the six-slot records of all rows
             if (gridDim.x == 1) for (int k = 0; k < 6; ++k) b.trace_pcm[64 + k] = (float)r7[k];
         }
         if (DSS_RELAY_STAMP && !STAMP && lane == 0 && blockIdx.x == 0)
@@ -816,8 +836,7 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
         if (lane < DSS_LPC_ORDER) b.last_sig[(size_t)slot * DSS_LPC_ORDER + lane] = ls_lane;
         if (lane == 0) {
             b.deemph[slot] = deemph;
-            b.last_exc[slot] = last_exc;
-            b.rng[slot * 4 + 0] = rng.z; b.rng[slot * 4 + 1] = rng.w; b.rng[slot * 4 + 2] = rng.jsr; b.rng[slot * 4 + 3] = rng.jcong;
+            b.last_exc[slot] = last_exc;                     // (the generator's state: wave 6)
         }
     }
 }

@@ -24,6 +24,7 @@ st = raw[: B * 6].reshape(B, 6) / n
 print("wave 7 (scalar role) view, cycles per sample, mean over utterances:")
 print("  " + "  ".join(f"{names[k]}={st[:, k].mean():8.1f}" for k in range(6)), " total", st.sum(axis=1).mean())
 print("  min/max total over utterances:", st.sum(axis=1).min(), st.sum(axis=1).max())
+w7_dtob = raw[B * 6: B * 7] / n if MODE == 1 else None    # one-utterance kernel: barrier D .. wave 7's arrival at barrier B, one value per row
 if MODE == 2 and B == 1:                                   # one workgroup: the relay waves' own stamps inside B..C
     print(f"  GRU B relay, from barrier B: wave 6 hands over for the last time at {raw[65] / n:.1f} and reaches C at {raw[66] / n:.1f}, "
           f"wave 7 ends the chain at {raw[64] / n:.1f} and reaches C at {raw[67] / n:.1f}")
@@ -47,3 +48,6 @@ print("role A view (cycles per sample, mean over utterances), per wave:")
 for w in range(6):
     print(f"  wave {w}: " + "  ".join(f"{namesA[k]}={sa[:, w, k].mean():7.1f}" for k in range(NSA)))
 print(f"  D -> all embedding loads issued, mean over waves 0..5: {(sa[:, :, 8] + sa[:, :, 0]).mean():7.1f}")
+if w7_dtob is not None:      # who is last at barrier B: the six role-A waits beside wave 7's own way from barrier D to barrier B
+    print("  wait at barrier B, waves 0..5: " + " ".join(f"{sa[:, w, 4].mean():.0f}" for w in range(6)) +
+          f" | wave 7, barrier D -> its arrival at barrier B: {w7_dtob.mean():.0f}")
