@@ -27,6 +27,7 @@
 // several trainers in one launch (blockIdx.y is the model; DESIGN.md, "Training several decoders at once").  The arithmetic is
 // stated once, so a model's bits do not depend on which of the two ran it.
 #include "dec_lstm_dot.h"
+#include "dss_global_ptr.h"
 
 // offsets of the eighteen tensors in the flat parameter array (state_dict order; also of the gradients and the square averages)
 __host__ __device__ static inline DssDecTrainOff dec_train_off(int C, int H, int O)
@@ -49,15 +50,8 @@ __host__ __device__ static inline DssDecTrainOff dec_train_off(int C, int H, int
 
 long dss_dec_train_param_count(int C, int H, int O) { return dec_train_off(C, H, O).total; }
 
-// A pointer read from the descriptor or from a trial table, as a pointer to global memory.  The compiler knows that of a kernel
-// argument's members, not of a pointer it loaded from a table (the group kernels at the end of this file), which it would address
-// through the flat aperture: those loads also count as LDS traffic in the waits of the serial chains.  Changes no value.
-template <typename P>
-__device__ __forceinline__ P *dec_gp(P *p)
-{
-    typedef __attribute__((address_space(1))) P *G;
-    return (P *)(G)(unsigned long long)p;
-}
+// Every pointer read from the descriptor or from a trial table goes through dss_gp (dss_global_ptr.h): the group kernels at the end
+// of this file load them from a table, and must still address global memory, not the flat aperture.
 
 // ---- forward, one layer: bilstm_layer_kernel<., 1> for one stream, with the stash ---------------------------------------------
 // blockIdx.x is the direction; step s is frame s (forward) or T - 1 - s (backward).  The dot products, the bias add and the cell
@@ -73,14 +67,14 @@ __device__ __forceinline__ void dec_train_layer_body(const DssDecTrainDev &d, co
     const int tid = threadIdx.x, H = d.H, H4 = 4 * H;
     const int Cin = LAYER ? 2 * H : d.C;
     const int Cp = (Cin + 3) & ~3, Hp = (H + 3) & ~3;
-    const float *wT = dec_gp(d.wT[LAYER][dir]);
+    const float *wT = dss_gp(d.wT[LAYER][dir]);
     const bool own = tid < H, rowt = tid < H4;
-    float *act = dec_gp(d.act[LAYER][dir]), *cst = dec_gp(d.c[LAYER][dir]), *hst = dec_gp(d.h[LAYER][dir]);
+    float *act = dss_gp(d.act[LAYER][dir]), *cst = dss_gp(d.c[LAYER][dir]), *hst = dss_gp(d.h[LAYER][dir]);
     float c = 0.f;
     for (int k = tid; k < DEC_MAXH; k += DEC_THREADS) hs[k].v = 0.f;
     for (int k = tid; k < DEC_TP * DEC_MAXC; k += DEC_THREADS) reinterpret_cast<float *>(xin)[k] = 0.f;
     if (own) { cst[tid] = 0.f; hst[tid] = 0.f; }           // row 0 of the stashes: the zero state
-    const float bias = rowt ? dec_gp(d.b[LAYER][dir])[tid] : 0.f;
+    const float bias = rowt ? dss_gp(d.b[LAYER][dir])[tid] : 0.f;
     df4 whh[DEC_MAXH / 4];                                 // this thread's row of W_hh, in registers for all steps
     {
         const df4 *wr = reinterpret_cast<const df4 *>(wT + (size_t)Cp * H4) + (rowt ? tid : 0);
@@ -95,7 +89,7 @@ __device__ __forceinline__ void dec_train_layer_body(const DssDecTrainDev &d, co
             const int step = step0 + tt, t = dir ? T - 1 - step : step;
             const float x = (float)in[(size_t)t * Cin + k];
             xin[tt][k].v = x;
-            if (LAYER == 0 && dir == 0) dec_gp(d.xs)[(size_t)t * Cin + k] = x;
+            if (LAYER == 0 && dir == 0) dss_gp(d.xs)[(size_t)t * Cin + k] = x;
         }
         __syncthreads();
         V pre[DEC_TP];
@@ -132,8 +126,8 @@ __device__ __forceinline__ void dec_train_layer_body(const DssDecTrainDev &d, co
                 cst[(size_t)(step + 1) * H + tid] = c;
                 hst[(size_t)(step + 1) * H + tid] = h;
                 const size_t oi = (size_t)t * (2 * H) + dir * H + tid;
-                if (LAYER == 0) dec_gp(d.midm)[oi] = mask ? h * mask[oi] : h;
-                else dec_gp(d.top)[oi] = h;
+                if (LAYER == 0) dss_gp(d.midm)[oi] = mask ? h * mask[oi] : h;
+                else dss_gp(d.top)[oi] = h;
             }
             __syncthreads();
         }
@@ -158,11 +152,11 @@ __device__ __forceinline__ void dec_train_head_body(const DssDecTrainDev &d, con
     __shared__ double es[DTH_ROWS][DSS_DEC_MAXO];
     const int tid = threadIdx.x, K = 2 * d.H, O = d.O;
     const DssDecTrainOff o = dec_train_off(d.C, d.H, O);
-    const float *w = dec_gp(d.p) + o.wr, *b = dec_gp(d.p) + o.br;
+    const float *w = dss_gp(d.p) + o.wr, *b = dss_gp(d.p) + o.br;
     float *ws = rs, *xs = rs + (size_t)O * (K + 1), *dfs = xs + (size_t)DTH_ROWS * K;
     const int t0 = blk * DTH_ROWS, nst = min(DTH_ROWS, T - t0);
     for (int k = tid; k < O * K; k += 256) { const int oo = k / K, j = k - oo * K; ws[oo * (K + 1) + j] = w[k]; }
-    for (int k = tid; k < DTH_ROWS * K; k += 256) xs[k] = k / K < nst ? dec_gp(d.top)[(size_t)t0 * K + k] : 0.f;
+    for (int k = tid; k < DTH_ROWS * K; k += 256) xs[k] = k / K < nst ? dss_gp(d.top)[(size_t)t0 * K + k] : 0.f;
     __syncthreads();
     for (int idx = tid; idx < nst * O; idx += 256) {
         const int rr = idx / O, oo = idx - rr * O;
@@ -173,8 +167,8 @@ __device__ __forceinline__ void dec_train_head_body(const DssDecTrainDev &d, con
         const size_t fi = (size_t)(t0 + rr) * O + oo;
         const double e = (double)f - (double)targets[fi];
         const float df = (float)(2.0 * e / ((double)T * (double)O));
-        dec_gp(d.feat)[fi] = f;
-        dec_gp(d.dfeat)[fi] = df;
+        dss_gp(d.feat)[fi] = f;
+        dss_gp(d.dfeat)[fi] = df;
         dfs[idx] = df;
         es[rr][oo] = e;
     }
@@ -182,13 +176,13 @@ __device__ __forceinline__ void dec_train_head_body(const DssDecTrainDev &d, con
     if (tid < nst) {
         double acc = 0.0;
         for (int oo = 0; oo < O; ++oo) acc += es[tid][oo] * es[tid][oo];
-        dec_gp(d.lossf)[t0 + tid] = acc;
+        dss_gp(d.lossf)[t0 + tid] = acc;
     }
     for (int idx = tid; idx < nst * K; idx += 256) {
         const int rr = idx / K, k = idx - rr * K;
         float a = 0.f;
         for (int oo = 0; oo < O; ++oo) a = __builtin_fmaf(ws[oo * (K + 1) + k], dfs[rr * O + oo], a);
-        dec_gp(d.dtop)[(size_t)(t0 + rr) * K + k] = a;
+        dss_gp(d.dtop)[(size_t)(t0 + rr) * K + k] = a;
     }
 }
 
@@ -211,7 +205,7 @@ __device__ __forceinline__ void dec_train_loss_body(const DssDecTrainDev &d, con
 {
     __shared__ double ls[DSS_DEC_TRAIN_MAXT];
     const int tid = threadIdx.x;
-    for (int t = tid; t < T; t += DEC_THREADS) ls[t] = dec_gp(d.lossf)[t];
+    for (int t = tid; t < T; t += DEC_THREADS) ls[t] = dss_gp(d.lossf)[t];
     __syncthreads();
     if (tid == 0) {
         double acc = 0.0;
@@ -227,16 +221,16 @@ __device__ __forceinline__ void dec_train_bptt_body(const DssDecTrainDev &d, con
     __shared__ float part[4][DEC_MAXH];                                   // W_hh^T dG per gate, before the owner adds them
     const int tid = threadIdx.x, H = d.H, H4 = 4 * H;
     const DssDecTrainOff o = dec_train_off(d.C, H, d.O);
-    const float *Whh = dec_gp(d.p) + (dir ? o.whh[LAYER][1] : o.whh[LAYER][0]);
+    const float *Whh = dss_gp(d.p) + (dir ? o.whh[LAYER][1] : o.whh[LAYER][0]);
     const int q = tid / DEC_MAXH, j = tid - q * DEC_MAXH;
     const bool own = tid < H, colt = j < H;
     float wt[DEC_MAXH];
 #pragma unroll
     for (int r = 0; r < DEC_MAXH; ++r) wt[r] = (colt && r < H) ? Whh[((size_t)q * H + r) * H + j] : 0.f;
     reinterpret_cast<float *>(dgs)[tid] = 0.f;             // (DEC_THREADS == 4 * DEC_MAXH)
-    const float *act = dec_gp(dir ? d.act[LAYER][1] : d.act[LAYER][0]), *cst = dec_gp(dir ? d.c[LAYER][1] : d.c[LAYER][0]);
-    const float *up = dec_gp(LAYER ? d.dtop : d.dmid) + dir * H + tid;
-    float *dG = dec_gp(dir ? d.dg[LAYER][1] : d.dg[LAYER][0]);
+    const float *act = dss_gp(dir ? d.act[LAYER][1] : d.act[LAYER][0]), *cst = dss_gp(dir ? d.c[LAYER][1] : d.c[LAYER][0]);
+    const float *up = dss_gp(LAYER ? d.dtop : d.dmid) + dir * H + tid;
+    float *dG = dss_gp(dir ? d.dg[LAYER][1] : d.dg[LAYER][0]);
     // the owner's stash values of step s, into seven registers
 #define DEC_LOAD_STEP(s)                                                                                                           \
     do {                                                                                                                           \
@@ -311,7 +305,7 @@ __device__ __forceinline__ void dec_train_dmid_body(const DssDecTrainDev &d, con
     for (int idx = tid; idx < 2 * DTM_FR * H4; idx += 256) {
         const int dd = idx / (DTM_FR * H4), rem = idx - dd * (DTM_FR * H4);
         const int tt = rem / H4, r = rem - tt * H4;
-        dgl[dd][r][tt] = tt < nst ? dec_gp(d.dg[1][dd])[(size_t)(t0 + tt) * H4 + r] : 0.f;
+        dgl[dd][r][tt] = tt < nst ? dss_gp(d.dg[1][dd])[(size_t)(t0 + tt) * H4 + r] : 0.f;
     }
     __syncthreads();
     if (tid >= K) return;
@@ -320,7 +314,7 @@ __device__ __forceinline__ void dec_train_dmid_body(const DssDecTrainDev &d, con
     for (int dd = 0; dd < 2; ++dd) {
 #pragma unroll
         for (int tt = 0; tt < DTM_FR; ++tt) acc[dd][tt] = 0.f;
-        const float *W = dec_gp(d.p) + o.wih[1][dd] + tid;
+        const float *W = dss_gp(d.p) + o.wih[1][dd] + tid;
         int r = 0;
         for (; r + 4 <= H4; r += 4) {
             float w[4];
@@ -342,7 +336,7 @@ __device__ __forceinline__ void dec_train_dmid_body(const DssDecTrainDev &d, con
         const size_t oi = (size_t)(t0 + tt) * K + tid;
         float s = acc[0][tt] + acc[1][tt];
         if (mask) s *= mask[oi];
-        dec_gp(d.dmid)[oi] = s;
+        dss_gp(d.dmid)[oi] = s;
     }
 }
 
@@ -366,8 +360,8 @@ dec_train_dmid_kernel(DssDecTrainDev d, int T, const float *__restrict__ mask)
 
 __device__ __forceinline__ float dec_rmsprop(const DssDecTrainDev &d, int k, float g, int apply, double lr, double alpha, double eps)
 {
-    float *dp = dec_gp(d.p), *dsq = dec_gp(d.sq);
-    dec_gp(d.g)[k] = g;
+    float *dp = dss_gp(d.p), *dsq = dss_gp(d.sq);
+    dss_gp(d.g)[k] = g;
     if (!apply) return dp[k];
     const float sq = (float)(alpha * (double)dsq[k] + (1.0 - alpha) * ((double)g * (double)g));
     dsq[k] = sq;
@@ -383,9 +377,9 @@ __device__ __forceinline__ void dec_train_step_body(const DssDecTrainDev &d, con
     const int tid = threadIdx.x, C = d.C, H = d.H, H4 = 4 * H, O = d.O;
     const bool head = b >= 4 * H4;
     const int LD = head ? 0 : b / H4, L = LD >> 1, dir = LD & 1, r = head ? b - 4 * H4 : b - LD * H4;
-    const float *dg = dec_gp(head ? d.dfeat : d.dg[L][dir]) + r;
+    const float *dg = dss_gp(head ? d.dfeat : d.dg[L][dir]) + r;
     const int dgs = head ? O : H4;
-    const float *inA = dec_gp(head ? d.top : (L ? d.midm : d.xs)), *inB = dec_gp(d.h[L][dir]);
+    const float *inA = dss_gp(head ? d.top : (L ? d.midm : d.xs)), *inB = dss_gp(d.h[L][dir]);
     const int nA = head || L ? 2 * H : C, nB = head ? 0 : H, ncol = nA + nB + 1;
     const int Cp = (nA + 3) & ~3;
     // the flat offsets of this (layer, direction)'s four tensors, and of the head (dec_train_off, without an indexed table)
@@ -415,7 +409,7 @@ __device__ __forceinline__ void dec_train_step_body(const DssDecTrainDev &d, con
             const float g = dgt[tt];
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                const float x = bias[u] ? 1.f : dec_gp(src[u])[(long)(t0 + tt) * stride[u]];
+                const float x = bias[u] ? 1.f : dss_gp(src[u])[(long)(t0 + tt) * stride[u]];
                 acc[u] = __builtin_fmaf(g, x, acc[u]);
             }
         }
@@ -430,14 +424,14 @@ __device__ __forceinline__ void dec_train_step_body(const DssDecTrainDev &d, con
         } else if (bias[u]) {
             const float bi = dec_rmsprop(d, o_bih + r, acc[u], apply, lr, alpha, eps);
             const float bh = dec_rmsprop(d, o_bhh + r, acc[u], apply, lr, alpha, eps);
-            if (apply) dec_gp(d.b[L][dir])[r] = bi + bh;
+            if (apply) dss_gp(d.b[L][dir])[r] = bi + bh;
         } else {
             const bool a = k < nA;
             const int pk = a ? o_wih + r * nA + k : o_whh + r * H + (k - nA);
             const float p = dec_rmsprop(d, pk, acc[u], apply, lr, alpha, eps);
             // the packed copy: [inputs / 4][4H rows][4 consecutive inputs], W_hh behind W_ih's padded inputs
             const int ki = a ? k : Cp + (k - nA);
-            if (apply) dec_gp(d.wT[L][dir])[((size_t)(ki >> 2) * H4 + r) * 4 + (ki & 3)] = p;
+            if (apply) dss_gp(d.wT[L][dir])[((size_t)(ki >> 2) * H4 + r) * 4 + (ki & 3)] = p;
         }
     }
 }
@@ -490,8 +484,8 @@ dec_group_layer_kernel(const DssDecTrainDev *__restrict__ models, const DssDecGr
     const DssDecGroupTrial tr = trials[blockIdx.y];
     if (tr.T <= 0) return;
     const DssDecTrainDev &d = models[blockIdx.y];
-    if (LAYER) dec_train_layer_body<InT, LAYER>(d, blockIdx.x, dec_gp((const InT *)d.midm), tr.T, (const float *)nullptr);
-    else dec_train_layer_body<InT, LAYER>(d, blockIdx.x, dec_gp((const InT *)tr.frames), tr.T, dec_gp(tr.mask));
+    if (LAYER) dec_train_layer_body<InT, LAYER>(d, blockIdx.x, dss_gp((const InT *)d.midm), tr.T, (const float *)nullptr);
+    else dec_train_layer_body<InT, LAYER>(d, blockIdx.x, dss_gp((const InT *)tr.frames), tr.T, dss_gp(tr.mask));
 }
 
 __global__ void __launch_bounds__(256)
@@ -500,7 +494,7 @@ dec_group_head_kernel(const DssDecTrainDev *__restrict__ models, const DssDecGro
     const DssDecGroupTrial tr = trials[blockIdx.y];
     if ((int)blockIdx.x * DTH_ROWS >= tr.T) return;
     const DssDecTrainDev &d = models[blockIdx.y];
-    dec_train_head_body(d, blockIdx.x, tr.T, dec_gp(tr.targets));
+    dec_train_head_body(d, blockIdx.x, tr.T, dss_gp(tr.targets));
 }
 
 template <int LAYER>
@@ -513,7 +507,7 @@ dec_group_bptt_kernel(const DssDecTrainDev *__restrict__ models, const DssDecGro
         const DssDecGroupTrial tr = trials[m];
         if (tr.T <= 0) return;
         const DssDecTrainDev &d = models[m];
-        dec_train_loss_body(d, tr.T, dec_gp(tr.loss));
+        dec_train_loss_body(d, tr.T, dss_gp(tr.loss));
         return;
     }
     const DssDecGroupTrial tr = trials[blockIdx.y];
@@ -528,7 +522,7 @@ dec_group_dmid_kernel(const DssDecTrainDev *__restrict__ models, const DssDecGro
     const DssDecGroupTrial tr = trials[blockIdx.y];
     if ((int)blockIdx.x * DTM_FR >= tr.T) return;
     const DssDecTrainDev &d = models[blockIdx.y];
-    dec_train_dmid_body(d, blockIdx.x, tr.T, dec_gp(tr.mask));
+    dec_train_dmid_body(d, blockIdx.x, tr.T, dss_gp(tr.mask));
 }
 
 __global__ void __launch_bounds__(DTS_THREADS)

@@ -228,6 +228,23 @@ long dss_vad_train_param_count(int C, int H);
 int dss_launch_vad_train_window(const DssVadTrainDev &d, const void *d_frames, int frames_f64, int T, const unsigned char *d_targets,
                                 const float *d_mask, int apply_step, double lr, double alpha, double eps, double *d_loss, hipStream_t s);
 
+// ---- several detector trainers of equal sizes stepped by one pair of launches per window (vad_train.hip; Part 15) ----------
+#define DSS_VAD_GROUP_MAXM 64     // M serial workgroups of 640 threads in the window launch: a quarter of the 256 CUs
+struct DssVadGroupTrial {         // one model's entry of a step's trial table (64 bytes); len == 0: the model sits the step out
+    const void *frames;           // (len, C) float32 or float64 (one dtype per step)
+    const unsigned char *targets; // [len] 0 / 1
+    const float *mask;            // (len, H) or NULL
+    double *losses;               // window w's loss goes to losses[w]
+    double lr, alpha, eps;
+    int len, apply;
+};
+// A trial step of M trainers on one stream: d_models[M] and d_trials[M] are device tables.  Windows w = 0 .. n_windows - 1 of
+// `window` frames each: model m's window w is frames w * window .. of its trial, min(window, len_m - w * window) of them, and a
+// model whose trial has run out (or with len == 0) is left alone.  reset != 0: the carried (h, c) of every model with len > 0 is
+// zeroed first, by one launch.
+int dss_launch_vad_train_group(const DssVadTrainDev *d_models, const DssVadGroupTrial *d_trials, int M, int C, int H, int n_windows,
+                               int window, int reset, int frames_f64, hipStream_t s);
+
 // ---- bidirectional recurrent decoder (bilstm_decoder.hip) ----------------------------------------------------
 struct DssDecDev {
     int S_max, T_max, C, H, O;    // capacity (streams x frames per call), inputs per frame, hidden units per direction, outputs (20)

@@ -120,6 +120,10 @@ int dss_dec_device_weights(dss_dec *v, int *device, int *n_inputs, int *hidden_u
 struct dss_dec_trainer;
 int dss_dec_trainer_view(dss_dec_trainer *tr, DssDecTrainDev *d, int *device, int *loaded);
 
+// The same for a detector's trainer (Part 9), for the group of Part 15.
+struct dss_vad_trainer;
+int dss_vad_trainer_view(dss_vad_trainer *tr, DssVadTrainDev *d, int *device, int *loaded);
+
 // Small host -> device uploads that must not stall, and must not be overwritten, while earlier calls are still queued.
 //
 // hipMemcpyAsync from pageable memory may wait for the stream's earlier work (the runtime stages it), which would hold the

@@ -1,0 +1,174 @@
+// csrc/dss_vad_group.cpp -- host side of Part 15 of include/dss_hip.h: several detectors of equal sizes trained side by side, one
+// pair of launches per window (the group kernels of csrc/vad_train.hip).  A group owns M trainers of Part 9 -- so loading,
+// reading, state access and publishing a member are Part 9's own functions on that member -- a device table of their M
+// descriptors, written once, and a ring of trial tables: a step fills the next page-locked slot, copies it to the slot's device
+// table in stream order and launches on that table, so a step enqueued while earlier ones still run never rewrites a table they
+// read.  A slot is reused only after the event behind its step's last launch (DssPinnedRing: the ninth step in flight waits for
+// the first).
+#include <vector>
+
+#include "dss_host.h"
+
+struct dss_vad_group {
+    int device = 0;
+    int M = 0, C = 0, H = 0, Tmax = 0;
+    std::vector<dss_vad_trainer *> tr;
+    DssVadTrainDev *d_models = nullptr;                   // [M]
+    DssVadGroupTrial *d_trials[DssPinnedRing::K] = {};    // [K][M]
+    DssDevBlocks blocks;                                  // the two kinds of table; a member's memory is the member's
+    DssPinnedRing ring;
+    bool ring_ok = false;
+};
+
+extern "C" int dss_vad_group_check(int n_models, int n_inputs, int hidden_units, int max_window)
+{
+    int rc = dss_vad_trainer_check(n_inputs, hidden_units, max_window, 1, 1, 1);
+    if (rc) return rc;
+    if (n_models < 1 || n_models > DSS_VAD_GROUP_MAXM) {
+        dss_set_error("a group of %d models: must be 1 .. %d (more models: more groups)", n_models, DSS_VAD_GROUP_MAXM);
+        return DSS_EINVAL;
+    }
+    return DSS_OK;
+}
+
+extern "C" void dss_vad_group_destroy(dss_vad_group *g)
+{
+    if (!g) return;
+    hipSetDevice(g->device);
+    hipDeviceSynchronize();
+    g->blocks.free_all();
+    if (g->ring_ok) g->ring.destroy();
+    for (dss_vad_trainer *t : g->tr) dss_vad_trainer_destroy(t);
+    delete g;
+}
+
+extern "C" dss_vad_group *dss_vad_group_create(int n_models, int n_inputs, int hidden_units, int max_window)
+{
+    if (dss_vad_group_check(n_models, n_inputs, hidden_units, max_window)) return nullptr;
+    if (dss_ensure_device()) return nullptr;
+    dss_vad_group *g = new dss_vad_group;
+    hipGetDevice(&g->device);
+    g->M = n_models; g->C = n_inputs; g->H = hidden_units; g->Tmax = max_window;
+    std::vector<DssVadTrainDev> table((size_t)n_models);
+    for (int m = 0; m < n_models; ++m) {
+        dss_vad_trainer *t = dss_vad_trainer_create(n_inputs, hidden_units, max_window);
+        if (!t) { dss_vad_group_destroy(g); return nullptr; }
+        g->tr.push_back(t);
+        int device = 0, loaded = 0;
+        dss_vad_trainer_view(t, &table[m], &device, &loaded);
+    }
+    const size_t tb = (size_t)n_models * sizeof(DssVadGroupTrial);
+    bool ok = g->blocks.alloc_bytes(table.size() * sizeof(DssVadTrainDev), (void **)&g->d_models) == DSS_OK &&
+              hipMemcpy(g->d_models, table.data(), table.size() * sizeof(DssVadTrainDev), hipMemcpyHostToDevice) == hipSuccess;
+    for (int k = 0; ok && k < DssPinnedRing::K; ++k)
+        ok = g->blocks.alloc_bytes(tb, (void **)&g->d_trials[k]) == DSS_OK && hipMemset(g->d_trials[k], 0, tb) == hipSuccess;
+    g->ring_ok = true;
+    if (ok) ok = g->ring.init((tb + sizeof(int) - 1) / sizeof(int)) == DSS_OK;
+    if (!ok) {
+        dss_set_error("device allocation failed for the tables of a group of %d detector trainers", n_models);
+        dss_vad_group_destroy(g);
+        return nullptr;
+    }
+    return g;
+}
+
+static dss_vad_trainer *member(dss_vad_group *g, int m, const char *who)
+{
+    if (!g || m < 0 || m >= g->M) {
+        dss_set_error("%s: model %d of a group of %d (or a NULL group)", who, m, g ? g->M : 0);
+        return nullptr;
+    }
+    return g->tr[(size_t)m];
+}
+
+extern "C" int dss_vad_group_load(dss_vad_group *g, int m, const float *w_ih0, const float *w_hh0, const float *b_ih0, const float *b_hh0,
+                                  const float *w_ih1, const float *w_hh1, const float *b_ih1, const float *b_hh1, const float *cls_w,
+                                  const float *cls_b)
+{
+    dss_vad_trainer *t = member(g, m, "dss_vad_group_load");
+    return t ? dss_vad_trainer_load(t, w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1, b_ih1, b_hh1, cls_w, cls_b) : DSS_EINVAL;
+}
+
+extern "C" int dss_vad_group_read(dss_vad_group *g, int m, int what, float *out)
+{
+    dss_vad_trainer *t = member(g, m, "dss_vad_group_read");
+    return t ? dss_vad_trainer_read(t, what, out) : DSS_EINVAL;
+}
+
+extern "C" int dss_vad_group_state(dss_vad_group *g, int m, float *h, float *c, int set)
+{
+    dss_vad_trainer *t = member(g, m, "dss_vad_group_state");
+    return t ? dss_vad_trainer_state(t, h, c, set) : DSS_EINVAL;
+}
+
+extern "C" int dss_vad_group_publish(dss_vad_group *g, int m, dss_vad *v, void *hip_stream)
+{
+    dss_vad_trainer *t = member(g, m, "dss_vad_group_publish");
+    return t ? dss_vad_trainer_publish(t, v, hip_stream) : DSS_EINVAL;
+}
+
+// One step: the checks, the table through the ring, the launches.  window == 0: dss_vad_group_window_dev (one window of len
+// frames each, no reset, apply_step honoured); else dss_vad_group_trial_dev.  Returns the number of window pairs launched.
+static int group_step(dss_vad_group *g, const dss_vad_group_trial *trials, int window, int frames_are_f64, void *hip_stream, const char *who)
+{
+    if (!g || !trials) { dss_set_error("%s: null argument", who); return DSS_EINVAL; }
+    const bool whole_trials = window != 0;
+    if (whole_trials && (window < 1 || window > g->Tmax)) {
+        dss_set_error("%s: windows of %d frames: must be 1 .. max_window = %d", who, window, g->Tmax);
+        return DSS_EINVAL;
+    }
+    const int win = whole_trials ? window : g->Tmax;
+    int n_windows = 0;
+    for (int m = 0; m < g->M; ++m) {
+        const dss_vad_group_trial &t = trials[m];
+        if (t.len == 0) continue;
+        if (t.len < 0) { dss_set_error("%s: model %d: %d frames: must be 0 (sits out) or more", who, m, t.len); return DSS_EINVAL; }
+        if (!whole_trials && t.len > g->Tmax) {
+            dss_set_error("%s: model %d: a window of %d frames: must be 0 (sits out) .. max_window = %d", who, m, t.len, g->Tmax);
+            return DSS_EINVAL;
+        }
+        if (!t.d_frames || !t.d_targets || !t.d_losses) {
+            dss_set_error("%s: model %d: null frames, targets or losses for %d frames", who, m, t.len);
+            return DSS_EINVAL;
+        }
+        DssVadTrainDev d;
+        int device = 0, loaded = 0;
+        dss_vad_trainer_view(g->tr[(size_t)m], &d, &device, &loaded);
+        if (!loaded) { dss_set_error("%s: model %d has no parameters loaded (dss_vad_group_load)", who, m); return DSS_EINVAL; }
+        const int nw = (int)(((long long)t.len + win - 1) / win);
+        if (nw > n_windows) n_windows = nw;
+    }
+    if (!n_windows) { dss_set_error("%s: every model sits out (all len are 0): nothing to launch", who); return DSS_EINVAL; }
+    DSS_HIP_CHECK(hipSetDevice(g->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    DssVadGroupTrial *slot = (DssVadGroupTrial *)g->ring.acquire();
+    if (!slot) { dss_set_error("%s: waiting for a free trial table failed", who); return DSS_ENODEV; }
+    for (int m = 0; m < g->M; ++m) {
+        const dss_vad_group_trial &t = trials[m];
+        DssVadGroupTrial &e = slot[m];
+        e.frames = t.d_frames; e.targets = t.d_targets; e.mask = t.d_mask; e.losses = t.d_losses;
+        e.lr = t.lr; e.alpha = t.alpha; e.eps = t.eps;
+        e.len = t.len; e.apply = whole_trials ? 1 : t.apply_step;
+    }
+    DssVadGroupTrial *d_slot = g->d_trials[g->ring.cur];
+    DSS_HIP_CHECK(hipMemcpyAsync(d_slot, slot, (size_t)g->M * sizeof(DssVadGroupTrial), hipMemcpyHostToDevice, st));
+    int rc = dss_launch_vad_train_group(g->d_models, d_slot, g->M, g->C, g->H, n_windows, win, whole_trials ? 1 : 0, frames_are_f64, st);
+    // behind the last launch, not only the copy: the device table of the slot is read until the step's last window has run
+    int rc2 = g->ring.commit(st);
+    return rc ? rc : rc2 ? rc2 : n_windows;
+}
+
+extern "C" int dss_vad_group_window_dev(dss_vad_group *g, const dss_vad_group_trial *trials, int frames_are_f64, void *hip_stream)
+{
+    int rc = group_step(g, trials, 0, frames_are_f64, hip_stream, "dss_vad_group_window_dev");
+    return rc < 0 ? rc : DSS_OK;
+}
+
+extern "C" int dss_vad_group_trial_dev(dss_vad_group *g, const dss_vad_group_trial *trials, int window, int frames_are_f64, void *hip_stream)
+{
+    if (g && window == 0) {
+        dss_set_error("dss_vad_group_trial_dev: windows of 0 frames: must be 1 .. max_window = %d", g->Tmax);
+        return DSS_EINVAL;
+    }
+    return group_step(g, trials, window, frames_are_f64, hip_stream, "dss_vad_group_trial_dev");
+}

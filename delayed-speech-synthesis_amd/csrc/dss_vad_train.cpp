@@ -204,6 +204,15 @@ extern "C" int dss_vad_trainer_trial_dev(dss_vad_trainer *tr, const void *d_fram
     return w;
 }
 
+int dss_vad_trainer_view(dss_vad_trainer *tr, DssVadTrainDev *d, int *device, int *loaded)
+{
+    if (!tr || !d || !device || !loaded) { dss_set_error("dss_vad_trainer_view: null argument"); return DSS_EINVAL; }
+    *d = tr->d;
+    *device = tr->device;
+    *loaded = tr->loaded ? 1 : 0;
+    return DSS_OK;
+}
+
 extern "C" int dss_vad_trainer_publish(dss_vad_trainer *tr, dss_vad *v, void *hip_stream)
 {
     if (!tr || !tr->loaded) { dss_set_error("dss_vad_trainer_publish: the trainer is NULL or has no parameters loaded"); return DSS_EINVAL; }

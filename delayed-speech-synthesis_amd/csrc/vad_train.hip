@@ -17,7 +17,14 @@
 //                            (torch layout) and of the packed copies the forward pass reads
 // Every sum has a fixed order and there are no atomics: the same call from the same state gives the same bits.  Fused
 // multiply-adds are written out (__builtin_fmaf), as in vad_lstm.hip; the library is built with -ffp-contract=off.
+// Each kernel's body is a __device__ __forceinline__ function that takes the descriptor by reference and what was a kernel
+// argument or blockIdx.x as an argument, because two kernels run it: the single trainer's, and the group form at the end of this
+// file, which steps several trainers in one launch (blockIdx.y is the model; DESIGN.md, "Training several detectors at once").
+// The arithmetic is stated once, so a model's bits do not depend on which of the two ran it.  Every pointer read from the
+// descriptor goes through dss_gp (dss_global_ptr.h): the group kernels load them from a table, and must still address global
+// memory, not the flat aperture.
 #include "vad_lstm_dot.h"
+#include "dss_global_ptr.h"
 
 // offsets of the ten tensors in the flat parameter array (state_dict order; also of the gradients and the square averages)
 struct VadTrainOff { int wih0, whh0, bih0, bhh0, wih1, whh1, bih1, bhh1, wc, bc, total; };
@@ -68,18 +75,19 @@ __device__ __forceinline__ void vad_bptt_layer(const DssVadTrainDev &d, const Va
                                                float (*part)[VAD_MAXH])
 {
     const int H = d.v.H, H4 = 4 * H;
-    const float *act = LAYER ? d.act1 : d.act0, *call = LAYER ? d.c1 : d.c0;
-    float *dG = LAYER ? d.dg1 : d.dg0;
-    const float *Whh = d.p + (LAYER ? o.whh1 : o.whh0);
+    const float *act = dss_gp(LAYER ? d.act1 : d.act0), *call = dss_gp(LAYER ? d.c1 : d.c0);
+    float *dG = dss_gp(LAYER ? d.dg1 : d.dg0);
+    const float *p = dss_gp(d.p), *Whh = p + (LAYER ? o.whh1 : o.whh0);
+    const float *dl = dss_gp(d.dl), *dh0m = dss_gp(d.dh0m);
     const int q = tid / VAD_MAXH, j = tid - q * VAD_MAXH;
     const bool own = tid < H;
     float dcn = 0.f, wc0 = 0.f, wc1 = 0.f;
-    if (LAYER == 1 && own) { wc0 = d.p[o.wc + tid]; wc1 = d.p[o.wc + H + tid]; }
+    if (LAYER == 1 && own) { wc0 = p[o.wc + tid]; wc1 = p[o.wc + H + tid]; }
     for (int t = T - 1; t >= 0; --t) {
         if (own) {
             float dh = t == T - 1 ? 0.f : (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
-            if (LAYER == 1) dh += __builtin_fmaf(wc1, d.dl[2 * t + 1], wc0 * d.dl[2 * t]);
-            else dh += d.dh0m[(size_t)t * H + tid];
+            if (LAYER == 1) dh += __builtin_fmaf(wc1, dl[2 * t + 1], wc0 * dl[2 * t]);
+            else dh += dh0m[(size_t)t * H + tid];
             const float *a = act + (size_t)t * H4;
             const float gi = a[tid], gf = a[H + tid], gg = a[2 * H + tid], go = a[3 * H + tid];
             const float c = call[(size_t)(t + 1) * H + tid], cp = call[(size_t)t * H + tid];
@@ -101,9 +109,9 @@ __device__ __forceinline__ void vad_bptt_layer(const DssVadTrainDev &d, const Va
 }
 
 template <typename FrameT>
-__global__ void __launch_bounds__(VAD_THREADS)
-vad_train_window_kernel(DssVadTrainDev d, const FrameT *__restrict__ frames, int T, const unsigned char *__restrict__ targets,
-                        const float *__restrict__ mask, double *__restrict__ loss)
+__device__ __forceinline__ void vad_train_window_body(const DssVadTrainDev &d, const FrameT *__restrict__ frames, const int T,
+                                                      const unsigned char *__restrict__ targets, const float *__restrict__ mask,
+                                                      double *__restrict__ loss)
 {
     typedef typename VadVec<1>::type V;
     __shared__ __attribute__((aligned(16))) V xin[VAD_TP][VAD_MAXC];
@@ -119,6 +127,12 @@ vad_train_window_kernel(DssVadTrainDev d, const FrameT *__restrict__ frames, int
     const int Cp = (C + 3) & ~3, Hp = (H + 3) & ~3;
     const VadTrainOff o = vad_train_off(C, H);
     const bool own = tid < H, rowt = tid < H4;
+    const float *wT0 = dss_gp(v.wT0), *wT1 = dss_gp(v.wT1), *wc = dss_gp(v.wc), *bc = dss_gp(v.bc);
+    float *vh = dss_gp(v.h), *vc = dss_gp(v.c);
+    float *sh0 = dss_gp(d.h0), *sh1 = dss_gp(d.h1), *sc0 = dss_gp(d.c0), *sc1 = dss_gp(d.c1), *act0 = dss_gp(d.act0), *act1 = dss_gp(d.act1);
+    float *xs = dss_gp(d.xs), *h0m = dss_gp(d.h0m), *logit = dss_gp(d.logit), *dl = dss_gp(d.dl), *dh0m = dss_gp(d.dh0m);
+    double *lossf = dss_gp(d.lossf);
+    const float *dg1 = dss_gp(d.dg1);
 
     // ---- forward: vad_trials_kernel's chains from the carried state, with the stash ------------------------------------------
     float c0 = 0.f, c1 = 0.f;
@@ -127,19 +141,19 @@ vad_train_window_kernel(DssVadTrainDev d, const FrameT *__restrict__ frames, int
     for (int k = tid; k < VAD_TP * VAD_MAXC; k += VAD_THREADS) reinterpret_cast<float *>(xin)[k] = 0.f;
     __syncthreads();
     if (own) {
-        const float ha = v.h[tid], hb = v.h[H + tid];
-        c0 = v.c[tid]; c1 = v.c[H + tid];
+        const float ha = vh[tid], hb = vh[H + tid];
+        c0 = vc[tid]; c1 = vc[H + tid];
         hs[0][tid].v = ha; hs[1][tid].v = hb;
-        d.h0[tid] = ha; d.h1[tid] = hb; d.c0[tid] = c0; d.c1[tid] = c1;     // row 0 of the stashes: the window's initial state
+        sh0[tid] = ha; sh1[tid] = hb; sc0[tid] = c0; sc1[tid] = c1;         // row 0 of the stashes: the window's initial state
     }
-    const float bias0 = rowt ? v.b0[tid] : 0.f, bias1 = rowt ? v.b1[tid] : 0.f;
+    const float bias0 = rowt ? dss_gp(v.b0)[tid] : 0.f, bias1 = rowt ? dss_gp(v.b1)[tid] : 0.f;
     for (int w0 = 0; w0 < T; w0 += VAD_TP) {
         const int nst = min(VAD_TP, T - w0);
         for (int idx = tid; idx < nst * C; idx += VAD_THREADS) {
             const int tt = idx / C, k = idx - tt * C;
             const float x = (float)frames[(size_t)(w0 + tt) * C + k];
             xin[tt][k].v = x;
-            d.xs[(size_t)(w0 + tt) * C + k] = x;
+            xs[(size_t)(w0 + tt) * C + k] = x;
         }
         __syncthreads();
 #pragma unroll
@@ -148,8 +162,8 @@ vad_train_window_kernel(DssVadTrainDev d, const FrameT *__restrict__ frames, int
 #pragma unroll
             for (int tt = 0; tt < VAD_TP; ++tt) pre[tt].v = 0.f;
             if (rowt) {
-                if (layer == 0) vad_dot_steps<1, V, VAD_MAXC>(pre, v.wT0, H4, tid, xin, Cp);
-                else vad_dot_steps<1, V, VAD_MAXH>(pre, v.wT1, H4, tid, h0s, Hp);
+                if (layer == 0) vad_dot_steps<1, V, VAD_MAXC>(pre, wT0, H4, tid, xin, Cp);
+                else vad_dot_steps<1, V, VAD_MAXH>(pre, wT1, H4, tid, h0s, Hp);
             }
 #pragma unroll
             for (int tt = 0; tt < VAD_TP; ++tt) {
@@ -157,8 +171,8 @@ vad_train_window_kernel(DssVadTrainDev d, const FrameT *__restrict__ frames, int
                 const int t = w0 + tt;
                 if (rowt) {
                     V acc = pre[tt];
-                    if (layer == 0) vad_dot<1, V>(acc, v.wT0 + (size_t)Cp * H4, H4, tid, hs[0], Hp);
-                    else vad_dot<1, V>(acc, v.wT1 + (size_t)Hp * H4, H4, tid, hs[1], Hp);
+                    if (layer == 0) vad_dot<1, V>(acc, wT0 + (size_t)Cp * H4, H4, tid, hs[0], Hp);
+                    else vad_dot<1, V>(acc, wT1 + (size_t)Hp * H4, H4, tid, hs[1], Hp);
                     acc.v += layer == 0 ? bias0 : bias1;
                     gates[tid] = acc;
                 }
@@ -170,58 +184,58 @@ vad_train_window_kernel(DssVadTrainDev d, const FrameT *__restrict__ frames, int
                     c = gf * c + gi * gg;
                     const float h = go * tanhf(c);
                     hs[layer][tid].v = h;
-                    float *a = (layer == 0 ? d.act0 : d.act1) + (size_t)t * H4;
+                    float *a = dss_uniform((layer == 0 ? act0 : act1) + (size_t)t * H4);
                     a[tid] = gi; a[H + tid] = gf; a[2 * H + tid] = gg; a[3 * H + tid] = go;
-                    (layer == 0 ? d.c0 : d.c1)[(size_t)(t + 1) * H + tid] = c;
-                    (layer == 0 ? d.h0 : d.h1)[(size_t)(t + 1) * H + tid] = h;
+                    dss_uniform((layer == 0 ? sc0 : sc1) + (size_t)(t + 1) * H)[tid] = c;
+                    dss_uniform((layer == 0 ? sh0 : sh1) + (size_t)(t + 1) * H)[tid] = h;
                     if (layer == 0) {
-                        const float hm = mask ? h * mask[(size_t)t * H + tid] : h;
+                        const float hm = mask ? h * dss_uniform(mask + (size_t)t * H)[tid] : h;
                         h0s[tt][tid].v = hm;
-                        d.h0m[(size_t)t * H + tid] = hm;
+                        dss_uniform(h0m + (size_t)t * H)[tid] = hm;
                     }
                 }
                 __syncthreads();
                 if (layer == 1) {
                     if (tid < 2) {
                         float a = 0.f;
-                        for (int k = 0; k < H; ++k) a = __builtin_fmaf(v.wc[tid * H + k], hs[1][k].v, a);
-                        d.logit[2 * t + tid] = a + v.bc[tid];
+                        for (int k = 0; k < H; ++k) a = __builtin_fmaf(wc[tid * H + k], hs[1][k].v, a);
+                        logit[2 * t + tid] = a + bc[tid];
                     }
                     // (the next step writes hs[1] only behind its own first barrier)
                 }
             }
         }
     }
-    if (own) { v.h[tid] = hs[0][tid].v; v.h[H + tid] = hs[1][tid].v; v.c[tid] = c0; v.c[H + tid] = c1; }
+    if (own) { vh[tid] = hs[0][tid].v; vh[H + tid] = hs[1][tid].v; vc[tid] = c0; vc[H + tid] = c1; }
     __syncthreads();
 
     // ---- loss and dlogits: per frame in float64 from the float32 logits, the mean summed in frame order ---------------------
     for (int t = tid; t < T; t += VAD_THREADS) {
-        const double z0 = d.logit[2 * t], z1 = d.logit[2 * t + 1];
+        const double z0 = logit[2 * t], z1 = logit[2 * t + 1];
         const int tg = targets[t] ? 1 : 0;
         const double m = fmax(z0, z1);
         const double lse = m + log(exp(z0 - m) + exp(z1 - m));
-        d.lossf[t] = lse - (tg ? z1 : z0);
-        d.dl[2 * t] = (float)((exp(z0 - lse) - (tg ? 0.0 : 1.0)) / (double)T);
-        d.dl[2 * t + 1] = (float)((exp(z1 - lse) - (tg ? 1.0 : 0.0)) / (double)T);
+        lossf[t] = lse - (tg ? z1 : z0);
+        dl[2 * t] = (float)((exp(z0 - lse) - (tg ? 0.0 : 1.0)) / (double)T);
+        dl[2 * t + 1] = (float)((exp(z1 - lse) - (tg ? 1.0 : 0.0)) / (double)T);
     }
     __syncthreads();
     if (tid == 0) {
         double acc = 0.0;
-        for (int t = 0; t < T; ++t) acc += d.lossf[t];
+        for (int t = 0; t < T; ++t) acc += lossf[t];
         *loss = acc / (double)T;
     }
 
     // ---- backward: layer 1 through time, then what it sends down through W_ih_l1 and the mask, then layer 0 -----------------
     vad_bptt_layer<1>(d, o, T, tid, dgs, part);
     {
-        const float *Wih1 = d.p + o.wih1;
+        const float *Wih1 = dss_gp(d.p) + o.wih1;
         const int q = tid / VAD_MAXH, j = tid - q * VAD_MAXH;
         for (int t0 = 0; t0 < T; t0 += VAD_TP) {
             const int nst = min(VAD_TP, T - t0);
             if (rowt) {
 #pragma unroll
-                for (int tt = 0; tt < VAD_TP; ++tt) dg4[tid][tt] = tt < nst ? d.dg1[(size_t)(t0 + tt) * H4 + tid] : 0.f;
+                for (int tt = 0; tt < VAD_TP; ++tt) dg4[tid][tt] = tt < nst ? dg1[(size_t)(t0 + tt) * H4 + tid] : 0.f;
             }
             __syncthreads();
             if (j < H) {
@@ -252,13 +266,21 @@ vad_train_window_kernel(DssVadTrainDev d, const FrameT *__restrict__ frames, int
                 for (int tt = 0; tt < nst; ++tt) {
                     float s = (part4[0][tid][tt] + part4[1][tid][tt]) + (part4[2][tid][tt] + part4[3][tid][tt]);
                     if (mask) s *= mask[(size_t)(t0 + tt) * H + tid];
-                    d.dh0m[(size_t)(t0 + tt) * H + tid] = s;
+                    dh0m[(size_t)(t0 + tt) * H + tid] = s;
                 }
             }
         }
     }
     __syncthreads();
     vad_bptt_layer<0>(d, o, T, tid, dgs, part);
+}
+
+template <typename FrameT>
+__global__ void __launch_bounds__(VAD_THREADS)
+vad_train_window_kernel(DssVadTrainDev d, const FrameT *__restrict__ frames, int T, const unsigned char *__restrict__ targets,
+                        const float *__restrict__ mask, double *__restrict__ loss)
+{
+    vad_train_window_body<FrameT>(d, frames, T, targets, mask, loss);
 }
 
 // ---- the parallel part: weight gradients and the RMSprop update --------------------------------------------------------------
@@ -274,27 +296,28 @@ vad_train_window_kernel(DssVadTrainDev d, const FrameT *__restrict__ frames, int
 
 __device__ __forceinline__ float vad_rmsprop(const DssVadTrainDev &d, int k, float g, int apply, double lr, double alpha, double eps)
 {
-    d.g[k] = g;
-    if (!apply) return d.p[k];
-    const float sq = (float)(alpha * (double)d.sq[k] + (1.0 - alpha) * ((double)g * (double)g));
-    d.sq[k] = sq;
-    const float p = (float)((double)d.p[k] - lr * (double)g / (sqrt((double)sq) + eps));
-    d.p[k] = p;
+    float *dp = dss_gp(d.p), *dsq = dss_gp(d.sq);
+    dss_gp(d.g)[k] = g;
+    if (!apply) return dp[k];
+    const float sq = (float)(alpha * (double)dsq[k] + (1.0 - alpha) * ((double)g * (double)g));
+    dsq[k] = sq;
+    const float p = (float)((double)dp[k] - lr * (double)g / (sqrt((double)sq) + eps));
+    dp[k] = p;
     return p;
 }
 
-__global__ void __launch_bounds__(VTS_THREADS)
-vad_train_step_kernel(DssVadTrainDev d, int T, int apply, double lr, double alpha, double eps)
+__device__ __forceinline__ void vad_train_step_body(const DssVadTrainDev &d, const int b, const int T, const int apply, const double lr,
+                                                    const double alpha, const double eps)
 {
     __shared__ float dgt[VTS_THREADS];
-    const int tid = threadIdx.x, b = blockIdx.x, C = d.v.C, H = d.v.H, H4 = 4 * H;
+    const int tid = threadIdx.x, C = d.v.C, H = d.v.H, H4 = 4 * H;
     const int Cp = (C + 3) & ~3, Hp = (H + 3) & ~3;
     const VadTrainOff o = vad_train_off(C, H);
     const bool head = b >= 2 * H4;
     const int L = head ? 2 : b / H4, r = head ? b - 2 * H4 : b - L * H4;
-    const float *dg = head ? d.dl + r : (L ? d.dg1 : d.dg0) + r;
+    const float *dg = dss_gp(head ? d.dl : (L ? d.dg1 : d.dg0)) + r;
     const int dgs = head ? 2 : H4;
-    const float *inA = head ? d.h1 + H : (L ? d.h0m : d.xs), *inB = L ? d.h1 : d.h0;
+    const float *inA = dss_gp(head ? d.h1 + H : (L ? d.h0m : d.xs)), *inB = dss_gp(L ? d.h1 : d.h0);
     const int nA = head || L ? H : C, nB = head ? 0 : H, ncol = nA + nB + 1;
     // two columns per thread: ncol <= 128 + 160 + 1
     const float *src[2];
@@ -319,7 +342,7 @@ vad_train_step_kernel(DssVadTrainDev d, int T, int apply, double lr, double alph
             const float g = dgt[tt];
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                const float x = bias[u] ? 1.f : src[u][(size_t)(t0 + tt) * stride[u]];
+                const float x = bias[u] ? 1.f : dss_gp(src[u])[(size_t)(t0 + tt) * stride[u]];
                 acc[u] = __builtin_fmaf(g, x, acc[u]);
             }
         }
@@ -334,16 +357,22 @@ vad_train_step_kernel(DssVadTrainDev d, int T, int apply, double lr, double alph
         } else if (bias[u]) {
             const float bi = vad_rmsprop(d, (L ? o.bih1 : o.bih0) + r, acc[u], apply, lr, alpha, eps);
             const float bh = vad_rmsprop(d, (L ? o.bhh1 : o.bhh0) + r, acc[u], apply, lr, alpha, eps);
-            if (apply) (L ? d.b1 : d.b0)[r] = bi + bh;
+            if (apply) dss_gp(L ? d.b1 : d.b0)[r] = bi + bh;
         } else {
             const bool a = k < nA;
             const int pk = a ? (L ? o.wih1 : o.wih0) + r * nA + k : (L ? o.whh1 : o.whh0) + r * H + (k - nA);
             const float p = vad_rmsprop(d, pk, acc[u], apply, lr, alpha, eps);
             // the packed copy: [inputs / 4][4H rows][4 consecutive inputs], W_hh behind W_ih's padded inputs
             const int ki = a ? k : (L ? Hp : Cp) + (k - nA);
-            if (apply) (L ? d.wT1 : d.wT0)[((size_t)(ki >> 2) * H4 + r) * 4 + (ki & 3)] = p;
+            if (apply) dss_gp(L ? d.wT1 : d.wT0)[((size_t)(ki >> 2) * H4 + r) * 4 + (ki & 3)] = p;
         }
     }
+}
+
+__global__ void __launch_bounds__(VTS_THREADS)
+vad_train_step_kernel(DssVadTrainDev d, int T, int apply, double lr, double alpha, double eps)
+{
+    vad_train_step_body(d, blockIdx.x, T, apply, lr, alpha, eps);
 }
 
 int dss_launch_vad_train_window(const DssVadTrainDev &d, const void *d_frames, int frames_f64, int T, const unsigned char *d_targets,
@@ -360,5 +389,76 @@ int dss_launch_vad_train_window(const DssVadTrainDev &d, const void *d_frames, i
     DSS_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(vad_train_step_kernel, dim3(8 * H + 2), dim3(VTS_THREADS), 0, st, d, T, apply_step, lr, alpha, eps);
     DSS_HIP_CHECK(hipGetLastError());
+    return DSS_OK;
+}
+
+// ---- several trainers in one launch (Part 15) ---------------------------------------------------------------------------------
+// The same two launches with a model axis: blockIdx.y is the model, blockIdx.x keeps its meaning.  A workgroup reads its model's
+// descriptor from a device table of M and its model's entry of the step's trial table (uniform addresses: scalar loads), then runs
+// the body the single-trainer kernel runs, so a model's numbers do not depend on M, on its place in the group or on what the others
+// do.  The entry describes a whole trial; the launch says which window of it: window w of `window` frames is frames t0 = w * window
+// .. t0 + T of the trial, T = min(window, len - t0), its masks and targets from row t0 on, its loss in losses[w].  T <= 0 is a model
+// that sits the step out (len == 0) or whose trial has run out: the test is uniform over the workgroup and comes before the first
+// store and the first barrier, so nothing of that model is written.  Both tables are constant while a launch runs (dss_cp).
+// The window kernel is held to the single trainer's six waves per SIMD (amdgpu_waves_per_eu): with the descriptor coming from a
+// table the scheduler otherwise settles for four and spends the registers (118 VGPRs for the same instructions).
+__device__ __forceinline__ int vad_group_window_frames(const DssVadGroupTrial &tr, int w, int window)
+{
+    return (int)min((long long)window, (long long)tr.len - (long long)w * window);
+}
+
+template <typename FrameT>
+__global__ void __launch_bounds__(VAD_THREADS) __attribute__((amdgpu_waves_per_eu(6)))
+vad_group_window_kernel(const DssVadTrainDev *__restrict__ models, const DssVadGroupTrial *__restrict__ trials, int w, int window)
+{
+    const DssVadGroupTrial &tr = *dss_cp(trials + blockIdx.y);
+    const int T = vad_group_window_frames(tr, w, window);
+    if (T <= 0) return;
+    const DssVadTrainDev &d = *dss_cp(models + blockIdx.y);
+    const size_t t0 = (size_t)w * window;
+    vad_train_window_body<FrameT>(d, dss_gp((const FrameT *)tr.frames) + t0 * d.v.C, T, dss_gp(tr.targets) + t0,
+                                  tr.mask ? dss_gp(tr.mask) + t0 * d.v.H : (const float *)nullptr, dss_gp(tr.losses) + w);
+}
+
+__global__ void __launch_bounds__(VTS_THREADS)
+vad_group_step_kernel(const DssVadTrainDev *__restrict__ models, const DssVadGroupTrial *__restrict__ trials, int w, int window)
+{
+    const DssVadGroupTrial &tr = *dss_cp(trials + blockIdx.y);
+    const int T = vad_group_window_frames(tr, w, window);
+    if (T <= 0) return;
+    const DssVadTrainDev &d = *dss_cp(models + blockIdx.y);
+    vad_train_step_body(d, blockIdx.x, T, tr.apply, tr.lr, tr.alpha, tr.eps);
+}
+
+// a new trial: zeros in the carried (h, c), [2 layers][H] each, of every model that takes part in the step
+__global__ void __launch_bounds__(VTS_THREADS)
+vad_group_reset_kernel(const DssVadTrainDev *__restrict__ models, const DssVadGroupTrial *__restrict__ trials)
+{
+    if (dss_cp(trials + blockIdx.x)->len <= 0) return;
+    const DssVadTrainDev &d = *dss_cp(models + blockIdx.x);
+    float *h = dss_gp(d.v.h), *c = dss_gp(d.v.c);
+    for (int k = threadIdx.x; k < 2 * d.v.H; k += VTS_THREADS) { h[k] = 0.f; c[k] = 0.f; }
+}
+
+int dss_launch_vad_train_group(const DssVadTrainDev *d_models, const DssVadGroupTrial *d_trials, int M, int C, int H, int n_windows,
+                               int window, int reset, int frames_f64, hipStream_t st)
+{
+    if (M < 1 || M > DSS_VAD_GROUP_MAXM || H < 1 || H > VAD_MAXH || 4 * H > VAD_THREADS || C < 1 || C > VAD_MAXC || n_windows < 1 ||
+        window < 1 || window > DSS_VAD_TRAIN_MAXT) {
+        dss_set_error("VAD group kernels: %d models / %d hidden units / %d inputs / %d windows of %d frames out of range (<= %d / <= %d / <= %d / >= 1 / <= %d)",
+                      M, H, C, n_windows, window, DSS_VAD_GROUP_MAXM, VAD_MAXH, VAD_MAXC, DSS_VAD_TRAIN_MAXT);
+        return DSS_EINVAL;
+    }
+    if (reset) {
+        hipLaunchKernelGGL(vad_group_reset_kernel, dim3(M), dim3(VTS_THREADS), 0, st, d_models, d_trials);
+        DSS_HIP_CHECK(hipGetLastError());
+    }
+    for (int w = 0; w < n_windows; ++w) {
+        if (frames_f64) hipLaunchKernelGGL((vad_group_window_kernel<double>), dim3(1, M), dim3(VAD_THREADS), 0, st, d_models, d_trials, w, window);
+        else hipLaunchKernelGGL((vad_group_window_kernel<float>), dim3(1, M), dim3(VAD_THREADS), 0, st, d_models, d_trials, w, window);
+        DSS_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(vad_group_step_kernel, dim3(8 * H + 2, M), dim3(VTS_THREADS), 0, st, d_models, d_trials, w, window);
+        DSS_HIP_CHECK(hipGetLastError());
+    }
     return DSS_OK;
 }

@@ -190,6 +190,15 @@ def _declare(L):
         "dss_dropout_masks_dev": (i, [vp, i, vp]),
         "dss_dropout_masks_host": (i, [vp, i]),
         "dss_selftest_philox": (i, [vp, vp, vp]),
+        "dss_vad_group_check": (i, [i, i, i, i]),
+        "dss_vad_group_create": (vp, [i, i, i, i]),
+        "dss_vad_group_destroy": (None, [vp]),
+        "dss_vad_group_load": (i, [vp, i] + [vp] * 10),
+        "dss_vad_group_read": (i, [vp, i, i, vp]),
+        "dss_vad_group_state": (i, [vp, i, vp, vp, i]),
+        "dss_vad_group_publish": (i, [vp, i, vp, vp]),
+        "dss_vad_group_window_dev": (i, [vp, vp, i, vp]),
+        "dss_vad_group_trial_dev": (i, [vp, vp, i, i, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

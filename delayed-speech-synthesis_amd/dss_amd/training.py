@@ -30,7 +30,8 @@ and no windows: a whole trial (250-1500 frames) is forward from the zero state, 
 ``DecoderGroupTrainerGPU`` steps up to 64 decoders of equal sizes in the same seven launches (the model is ``blockIdx.y``; the kernels'
 bodies are the single trainer's, so every model's numbers are its bits), and ``train_decoders`` is that many ``train_decoder`` loops
 in lock step: the fold loop of train_bidirectional_model.py:65-78 (``leave_one_day_out``, ``join_corpora``), seeds and learning
-rates as one run.
+rates as one run.  ``VadGroupTrainerGPU`` and ``train_vads`` are the same for the detector: up to 64 detectors in one pair of launches
+per window, M ``train_vad`` loops in lock step (the day split of train_unidirectional_vad.py:81-93, seeds, learning rates).
 
 No HDF files, tensorboard, plots, ``torchinfo`` summary or per-epoch ``.npy`` dumps are produced, and the decoder script's
 vocoding of validation samples (``AsynchronousSynthesisQueue``) is not part of the loop: ``dss_amd.lpcnet.LPCNetBatch`` vocodes
@@ -605,6 +606,37 @@ def _per_model(v, n, what):
     return [float(e) for e in v]
 
 
+class _MaskStage:
+    """A group step's host masks on their way to the device: one page-locked buffer and one copy per step.  Two buffers take
+    turns, each guarded by an event behind its copy, so filling the next step's masks does not wait for the step in flight."""
+
+    def __init__(self):
+        self._stage, self._stage_ev, self._stage_k, self._dev_masks = [None, None], [None, None], 0, None
+
+    def upload(self, host, device):
+        """``host``: [(m, float32 CPU tensor)]; returns {m: flat device tensor}."""
+        import torch
+        total = sum(t.numel() for _, t in host)
+        k = self._stage_k
+        self._stage_k = 1 - k
+        if self._stage_ev[k] is not None:
+            self._stage_ev[k].synchronize()
+        if self._stage[k] is None or self._stage[k].numel() < total:
+            self._stage[k] = torch.empty((total,), dtype=torch.float32).pin_memory()
+        if self._dev_masks is None or self._dev_masks.numel() < total:
+            self._dev_masks = torch.empty((total,), dtype=torch.float32, device=device)
+        out, o = {}, 0
+        for m, t in host:
+            n = t.numel()
+            self._stage[k][o:o + n].copy_(t.reshape(-1))
+            out[m] = self._dev_masks[o:o + n]
+            o += n
+        self._dev_masks[:total].copy_(self._stage[k][:total], non_blocking=True)
+        ev = self._stage_ev[k] = self._stage_ev[k] or torch.cuda.Event()
+        ev.record()
+        return out
+
+
 class DecoderGroupTrainerGPU:
     """The trainers of M decoders of equal sizes, stepped together: one trial for each model in ONE set of ``DecoderTrainerGPU``'s
     seven launches, with the model as ``blockIdx.y`` (``dss_dec_group_step_dev``, csrc/dec_train.hip), so the serial chains of all
@@ -635,7 +667,7 @@ class DecoderGroupTrainerGPU:
         if not self._h:
             raise MemoryError(L.dss_last_error().decode())
         self._last = [0] * self.M
-        self._stage, self._stage_ev, self._stage_k, self._dev_masks = [None, None], [None, None], 0, None
+        self._mask_stage = _MaskStage()
         for m, w in enumerate(ws):
             _lib.check(L.dss_dec_group_load(self._h, m, (C.c_void_p * 18)(*[a.ctypes.data for a in w])))
 
@@ -652,31 +684,6 @@ class DecoderGroupTrainerGPU:
         if not 0 <= m < self.M:
             raise IndexError(f"model {m} of a group of {self.M}")
         return m
-
-    def _upload_masks(self, host, device):
-        """The step's host masks ([(m, (T, 2H) float32 CPU tensor)]) through one page-locked buffer and one copy; returns
-        {m: device tensor}.  Two buffers take turns, each guarded by an event behind its copy, so filling the next step's masks does
-        not wait for the step in flight."""
-        import torch
-        total = sum(t.numel() for _, t in host)
-        k = self._stage_k
-        self._stage_k = 1 - k
-        if self._stage_ev[k] is not None:
-            self._stage_ev[k].synchronize()
-        if self._stage[k] is None or self._stage[k].numel() < total:
-            self._stage[k] = torch.empty((total,), dtype=torch.float32).pin_memory()
-        if self._dev_masks is None or self._dev_masks.numel() < total:
-            self._dev_masks = torch.empty((total,), dtype=torch.float32, device=device)
-        out, o = {}, 0
-        for m, t in host:
-            n = t.numel()
-            self._stage[k][o:o + n].copy_(t.reshape(-1))
-            out[m] = self._dev_masks[o:o + n]
-            o += n
-        self._dev_masks[:total].copy_(self._stage[k][:total], non_blocking=True)
-        ev = self._stage_ev[k] = self._stage_ev[k] or torch.cuda.Event()
-        ev.record()
-        return out
 
     def step(self, xs, ys, masks=None, apply: bool = True, lr=LR, alpha=ALPHA, eps=EPS, losses=None):
         """One step: model m runs the trial ``xs[m]`` (T_m, C) frames / ``ys[m]`` (T_m, O) targets / ``masks[m]`` (T_m, 2H)
@@ -729,7 +736,7 @@ class DecoderGroupTrainerGPU:
         if dtype is None:
             raise ValueError("every model sits out: a step needs at least one trial")
         if host_masks:
-            for m, k in self._upload_masks(host_masks, device).items():
+            for m, k in self._mask_stage.upload(host_masks, device).items():
                 table[m].d_mask = k.data_ptr()
         if losses is None:
             losses = torch.full((M,), float("nan"), dtype=torch.float64, device=device)
@@ -791,7 +798,7 @@ def lockstep_schedule(orders):
     return [[o[k] if k < len(o) else None for o in orders] for k in range(max([len(o) for o in orders] + [0]))]
 
 
-def _group_epoch(step, gens, n_trials, lengths, hidden_units, dropout, shuffle, sources=None):
+def _group_epoch(step, gens, n_trials, lengths, hidden_units, dropout, shuffle, sources=None, mask_fn=None, mask_width=None):
     """One epoch of M runs in lock step.  Model m's generator ``gens[m]`` draws what ``train_decoder``'s generator draws in an
     epoch, in its order: the permutation of its ``n_trials[m]`` trials first, then the mask of each trial as its turn comes
     (``lengths[m][trial]`` frames).  ``step(trials, masks)`` gets, per step, every model's trial index (or None) and mask (or
@@ -800,18 +807,23 @@ def _group_epoch(step, gens, n_trials, lengths, hidden_units, dropout, shuffle, 
     With ``sources`` (one ``DeviceMaskSource`` per model) the generators draw the permutations only: a step's masks are one entry
     table and one launch into one device buffer, each mask at a multiple of 4 floats, model m's from ``sources[m]``'s next draw (a
     model that sits the step out draws nothing), and ``step`` gets the slices -- nothing is staged or uploaded.  One buffer
-    serves every step: the launch that refills it is queued behind the step that read it, on the same stream."""
+    serves every step: the launch that refills it is queued behind the step that read it, on the same stream.
+
+    ``mask_fn(frames, hidden_units, dropout, generator)`` draws a host mask and ``mask_width`` is a device mask's width: the
+    decoder's by default (``decoder_dropout_mask``, 2H); the detector's loop passes ``dropout_mask`` and H."""
     import torch
     _check_p(dropout)
+    mask_fn = decoder_dropout_mask if mask_fn is None else mask_fn
+    mask_width = 2 * int(hidden_units) if mask_width is None else int(mask_width)
     orders = [torch.randperm(n, generator=g).tolist() if shuffle else list(range(n)) for n, g in zip(n_trials, gens)]
     steps, out, buf = lockstep_schedule(orders), [], None
     for trials in steps:
         if sources is None:
-            masks = [None if k is None else decoder_dropout_mask(lengths[m][k], hidden_units, dropout, gens[m]) for m, k in enumerate(trials)]
+            masks = [None if k is None else mask_fn(lengths[m][k], hidden_units, dropout, gens[m]) for m, k in enumerate(trials)]
         elif dropout == 0.0:
             masks = [None] * len(trials)
         else:
-            requests = [None if k is None else (lengths[m][k], 2 * int(hidden_units), sources[m].seed, sources[m].take(), dropout)
+            requests = [None if k is None else (lengths[m][k], mask_width, sources[m].seed, sources[m].take(), dropout)
                         for m, k in enumerate(trials)]
             masks, buf = _packed_masks(requests, sources[0].device, buf)
         out.append(step(trials, masks))
@@ -887,6 +899,276 @@ def train_decoders(state_dicts, train_corpora, valid_corpora, epochs: int = 8, d
     return [(best[m][0] if best[m][0] is not None else tr.state_dict(m), history[m]) for m in range(M)]
 
 
+# ---- several detectors at once -----------------------------------------------------------------------------------------------------
+
+class _VadGroupTrial(C.Structure):
+    """``dss_vad_group_trial`` of include/dss_hip.h."""
+    _fields_ = [("d_frames", C.c_void_p), ("d_targets", C.c_void_p), ("d_mask", C.c_void_p), ("d_losses", C.c_void_p),
+                ("lr", C.c_double), ("alpha", C.c_double), ("eps", C.c_double), ("len", C.c_int), ("apply_step", C.c_int)]
+
+
+class VadGroupTrainerGPU:
+    """The trainers of M detectors of equal sizes, stepped together: one window for each model in ONE pair of ``VadTrainerGPU``'s
+    launches, with the model as ``blockIdx.y`` (``dss_vad_group_window_dev`` / ``_trial_dev``, csrc/vad_train.hip), so the serial
+    workgroups of all models run side by side on different compute units.  Every model's numbers are bit for bit those of a
+    ``VadTrainerGPU`` with the same weights given the same windows in the same order.  1 <= M <= 64; more models are more groups."""
+
+    def __init__(self, state_dicts, max_window: int = 50):
+        state_dicts = list(state_dicts)
+        ws = []
+        for sd in state_dicts:
+            sd = _state_dict(sd, _vad.fits, "VadGroupTrainerGPU")
+            ws.append([np.ascontiguousarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], dtype=np.float32)
+                       for k in _vad._KEYS])
+        self._L = L = _lib.load()
+        self.M, self.max_window = len(ws), int(max_window)
+        if not ws:
+            _lib.check(L.dss_vad_group_check(0, 1, 1, self.max_window))
+        h4, c = ws[0][0].shape
+        self.C, self.H = int(c), int(h4 // 4)
+        shapes = [tuple(a.shape) for a in ws[0]]
+        for m, w in enumerate(ws):
+            if [tuple(a.shape) for a in w] != shapes:
+                raise ValueError(f"VadGroupTrainerGPU: model {m} has other sizes than model 0 (one group, one size)")
+        _lib.check(L.dss_vad_group_check(self.M, self.C, self.H, self.max_window))
+        _lib.require_gpu()
+        self._n = int(L.dss_vad_trainer_param_count(self.C, self.H))
+        self._h = L.dss_vad_group_create(self.M, self.C, self.H, self.max_window)
+        if not self._h:
+            raise MemoryError(L.dss_last_error().decode())
+        self._mask_stage = _MaskStage()
+        for m, w in enumerate(ws):
+            _lib.check(L.dss_vad_group_load(self._h, m, *[a.ctypes.data for a in w]))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._L.dss_vad_group_destroy(self._h)
+            self._h = None
+
+    def __len__(self):
+        return self.M
+
+    def _member(self, m):
+        m = int(m)
+        if not 0 <= m < self.M:
+            raise IndexError(f"model {m} of a group of {self.M}")
+        return m
+
+    # ---- steps ----
+    def _table(self, xs, ys, masks, lr, alpha, eps, longest):
+        """The step's entry table from per-model sequences (everything but where the losses go), what must stay alive until the
+        call has been enqueued, the frames' dtype and their device."""
+        import torch
+        M = self.M
+        xs, ys = list(xs), list(ys)
+        masks = [None] * M if masks is None else list(masks)
+        for what, seq in (("xs", xs), ("ys", ys), ("masks", masks)):
+            if len(seq) != M:
+                raise ValueError(f"{what}: {len(seq)} entries for {M} models")
+        lrs, alphas, epss = (_per_model(v, M, w) for v, w in ((lr, "lr"), (alpha, "alpha"), (eps, "eps")))
+        table = (_VadGroupTrial * M)()
+        keep, host_masks, dtype, device = [], [], None, None
+        for m in range(M):
+            if xs[m] is None:
+                continue
+            x = xs[m] if isinstance(xs[m], torch.Tensor) else torch.from_numpy(np.ascontiguousarray(xs[m]))
+            if x.dtype not in (torch.float64, torch.float32):
+                raise TypeError("frames must be float64 or float32")
+            if x.dim() != 2 or x.shape[1] != self.C:
+                raise ValueError(f"model {m}: frames must be (T, {self.C})")
+            if dtype is not None and x.dtype != dtype:
+                raise TypeError("the frames of one step must have one dtype")
+            dtype = x.dtype
+            n = int(x.shape[0])
+            if n < 1 or (longest is not None and n > longest):
+                raise ValueError(f"model {m}: {n} frames: must be 1 .. {'any' if longest is None else longest}")
+            x = x.cuda().contiguous()
+            device = x.device
+            y = ys[m]
+            if isinstance(y, torch.Tensor) and y.is_cuda and y.dtype == torch.uint8:       # resident labels are taken as they are
+                if tuple(y.shape) != (n,):
+                    raise ValueError(f"model {m}: {n} frames but targets of shape {tuple(y.shape)}")
+                y = y.contiguous()
+            else:
+                y = VadTrainerGPU._targets(y, n)
+            k = masks[m]
+            if k is not None:
+                k = k if isinstance(k, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(k))
+                if tuple(k.shape) != (n, self.H):
+                    raise ValueError(f"model {m}: the mask must be ({n}, {self.H})")
+                k = k.to(dtype=torch.float32).contiguous()
+                if not k.is_cuda:
+                    host_masks.append((m, k))
+            keep += [x, y, k]
+            table[m] = _VadGroupTrial(x.data_ptr(), y.data_ptr(), k.data_ptr() if k is not None and k.is_cuda else None, None,
+                                      lrs[m], alphas[m], epss[m], n, 1)
+        if dtype is None:
+            raise ValueError("every model sits out: a step needs at least one model with frames")
+        if host_masks:
+            for m, k in self._mask_stage.upload(host_masks, device).items():
+                table[m].d_mask = k.data_ptr()
+        return table, keep, dtype, device
+
+    def _losses(self, losses, table, columns, device):
+        """The (M, columns) float64 device tensor the step writes, new and NaN-filled unless given (``columns`` None: (M,)); every
+        taking-part model's entry gets its row."""
+        import torch
+        shape = (self.M,) if columns is None else (self.M, columns)
+        if losses is None:
+            losses = torch.full(shape, float("nan"), dtype=torch.float64, device=device)
+        elif not (isinstance(losses, torch.Tensor) and losses.is_cuda and losses.dtype == torch.float64 and losses.is_contiguous()
+                  and losses.dim() == len(shape) and losses.shape[0] == self.M and (columns is None or losses.shape[1] >= columns)):
+            raise ValueError(f"losses must be a contiguous CUDA float64 tensor of {' x '.join(str(s) for s in shape)} entries"
+                             + ("" if columns is None else " (or more columns)"))
+        row = 8 * (1 if columns is None else int(losses.shape[1]))
+        for m in range(self.M):
+            if table[m].len:
+                table[m].d_losses = losses.data_ptr() + row * m
+        return losses
+
+    def window(self, xs, ys, masks=None, step: bool = True, lr=LR, alpha=ALPHA, eps=EPS, losses=None):
+        """One window for each model from its carried state, as ``VadTrainerGPU.window``: model m runs ``xs[m]`` (T_m, C) frames
+        (T_m <= max_window) / ``ys[m]`` (T_m,) 0 / 1 targets / ``masks[m]`` (T_m, H) multipliers or None; ``xs[m] is None``: the
+        model sits out and nothing of it changes.  All frames of a step have one dtype.  ``lr``, ``alpha``, ``eps``: a scalar or one
+        per model.  Returns the device tensor of M float64 losses: ``losses`` if given (a CUDA float64 tensor of M entries), else a
+        new one filled with NaN; the entries of models that sat out are not written.  Nothing synchronises with the host."""
+        import torch
+        table, keep, dtype, device = self._table(xs, ys, masks, lr, alpha, eps, self.max_window)
+        losses = self._losses(losses, table, None, device)
+        for m in range(self.M):
+            table[m].apply_step = int(bool(step))
+        _lib.check(self._L.dss_vad_group_window_dev(self._h, table, int(dtype == torch.float64), torch.cuda.current_stream().cuda_stream))
+        return losses
+
+    def train_trials(self, xs, ys, window: int = 50, masks=None, lr=LR, alpha=ALPHA, eps=EPS, losses=None):
+        """One trial for each model, as ``VadTrainerGPU.train_trial`` with given masks: the carried state of every model that takes
+        part starts from zeros, then window after window of ``window`` frames (a model's last one the remainder) is stepped for all
+        models at once until the longest trial has run out; ``xs[m] is None`` sits out.  ``masks[m]``: (len_m, H) multipliers or
+        None.  Returns (losses, counts): the (M, max(counts)) float64 device tensor of per-window losses -- ``losses`` if given (M
+        rows, at least that many columns), else new and NaN-filled; row m holds model m's ``counts[m]`` = ceil(len_m / window)
+        losses, the rest of it is not written -- and the counts (0 for a model that sat out).  Nothing synchronises with the host:
+        trials may be enqueued back to back."""
+        import torch
+        window = int(window)
+        _lib.check(self._L.dss_vad_trainer_check(self.C, self.H, self.max_window, 1, 1, window))
+        table, keep, dtype, device = self._table(xs, ys, masks, lr, alpha, eps, None)
+        counts = [-(-int(table[m].len) // window) for m in range(self.M)]
+        losses = self._losses(losses, table, max(counts), device)
+        _lib.check(self._L.dss_vad_group_trial_dev(self._h, table, window, int(dtype == torch.float64),
+                                                   torch.cuda.current_stream().cuda_stream))
+        return losses, counts
+
+    # ---- what the group holds, per model ----
+    def _read(self, m: int, what: int) -> dict:
+        flat = np.empty(self._n, np.float32)
+        _lib.check(self._L.dss_vad_group_read(self._h, self._member(m), what, flat.ctypes.data))
+        out, o = {}, 0
+        for k, shp in zip(_vad._KEYS, _shapes(self.C, self.H)):
+            cnt = int(np.prod(shp))
+            out[k] = flat[o:o + cnt].reshape(shp).copy()
+            o += cnt
+        return out
+
+    def gradients(self, m: int) -> dict:
+        """The gradients of model m's last window, float32 arrays keyed by the torch names."""
+        return self._read(m, 1)
+
+    def square_avg(self, m: int) -> dict:
+        """Model m's RMSprop square averages."""
+        return self._read(m, 2)
+
+    def state_dict(self, m: int) -> dict:
+        """Model m's current parameters as float32 torch tensors."""
+        import torch
+        return {k: torch.from_numpy(v) for k, v in self._read(m, 0).items()}
+
+    def state(self, m: int):
+        """Model m's carried (h, c), host float32 arrays [2][H]."""
+        h = np.empty((2, self.H), np.float32)
+        c = np.empty((2, self.H), np.float32)
+        _lib.check(self._L.dss_vad_group_state(self._h, self._member(m), h.ctypes.data, c.ctypes.data, 0))
+        return h, c
+
+    def set_state(self, m: int, h, c):
+        h = np.ascontiguousarray(h, dtype=np.float32).reshape(2, self.H)
+        c = np.ascontiguousarray(c, dtype=np.float32).reshape(2, self.H)
+        _lib.check(self._L.dss_vad_group_state(self._h, self._member(m), h.ctypes.data, c.ctypes.data, 1))
+
+    def publish(self, m: int, detector: "_vad.VadLstmGPU"):
+        """Copy model m's current weights device to device into an inference handle of the same sizes (``VadLstmGPU``)."""
+        import torch
+        if not isinstance(detector, _vad.VadLstmGPU):
+            raise TypeError("publish takes a VadLstmGPU")
+        _lib.check(self._L.dss_vad_group_publish(self._h, self._member(m), detector._h, torch.cuda.current_stream().cuda_stream))
+
+
+def train_vads(state_dicts, train_corpora, valid_corpora, epochs: int = 8, window: int = 50, dropout: float = 0.5, lr=LR, seeds=None,
+               columns=None, shuffle: bool = True, alpha: float = ALPHA, eps: float = EPS, mask_source: str = "host"):
+    """M ``train_vad`` loops in lock step on one ``VadGroupTrainerGPU``: the day split of train_unidirectional_vad.py:81-93, seeds
+    or learning rates as one run.  ``state_dicts[m]``, ``train_corpora[m]``, ``valid_corpora[m]`` and ``seeds[m]`` (default
+    0 .. M - 1) are model m's arguments of ``train_vad``; ``lr`` is a scalar or one per model; ``columns`` is shared.
+
+    Model m owns a generator seeded with ``seeds[m]`` that draws its epoch's permutation and then its masks exactly as
+    ``train_vad`` does, and step k of an epoch runs every model's k-th trial (``train_trials``), models with fewer trials sitting
+    out the rest of the epoch: every model's history and best weights are those of ``train_vad`` run alone with its seed and
+    corpora, bit for bit.  After an epoch each model is published into one kept ``VadLstmGPU`` and validated on its own corpus;
+    its weights are kept when its accuracy is strictly greater than every earlier one.  Returns [(best state_dict, history)], one
+    pair per model.
+
+    ``mask_source="device"``: the permutations still come from those generators; model m's masks come from
+    ``DeviceMaskSource(seeds[m])``, one draw per trial stepped, all masks of a step from one launch -- again what
+    ``train_vad(..., mask_source="device", seed=seeds[m])`` computes alone, bit for bit."""
+    import torch
+    from .validation import _corpus_frames
+    state_dicts, train_corpora, valid_corpora = list(state_dicts), list(train_corpora), list(valid_corpora)
+    M = len(state_dicts)
+    seeds = list(range(M)) if seeds is None else list(seeds)
+    for what, seq in (("train_corpora", train_corpora), ("valid_corpora", valid_corpora), ("seeds", seeds)):
+        if len(seq) != M:
+            raise ValueError(f"{what}: {len(seq)} entries for {M} models")
+    lrs = _per_model(lr, M, "lr")
+    sources = _mask_sources(mask_source, seeds)
+    xs, ys, ranges = [], [], []
+    for m in range(M):
+        hx, hy, hid = _corpus(train_corpora[m])
+        x, r = _corpus_frames(hx, hid, columns)
+        ya = (hy.detach().cpu().numpy() if isinstance(hy, torch.Tensor) else np.asarray(hy)).ravel()
+        if len(ya) != x.shape[0]:
+            raise ValueError(f"model {m}: {x.shape[0]} frames but {len(ya)} labels")
+        xs.append(x); ranges.append(r)
+        ys.append(VadTrainerGPU._targets(ya, len(ya)))       # checked to be 0 / 1 and resident from here on
+    if len({x.dtype for x in xs}) > 1:
+        xs = [x.double() for x in xs]
+    tr = VadGroupTrainerGPU(state_dicts, max_window=window)
+    gens = [torch.Generator().manual_seed(int(s)) for s in seeds]
+    detector = _vad.VadLstmGPU(1, state_dict=tr.state_dict(0))
+    lengths = [[n for _, n in r] for r in ranges]
+
+    def step(trials, masks):
+        sl = [None if k is None else slice(ranges[m][k][0], ranges[m][k][0] + ranges[m][k][1]) for m, k in enumerate(trials)]
+        return tr.train_trials([None if s is None else xs[m][s] for m, s in enumerate(sl)], [None if s is None else ys[m][s] for m, s in enumerate(sl)],
+                               window, masks, lrs, alpha, eps)
+
+    best = [(None, -np.inf)] * M
+    n_steps, history = [0] * M, [[] for _ in range(M)]
+    for _ in range(int(epochs)):
+        steps, out = _group_epoch(step, gens, [len(r) for r in ranges], lengths, tr.H, dropout, shuffle, sources, dropout_mask, tr.H)
+        out = [(losses.cpu().numpy(), counts) for losses, counts in out]       # the losses stay on the device until here
+        for m in range(M):
+            mine = [losses[m, :counts[m]] for (losses, counts), trials in zip(out, steps) if trials[m] is not None]
+            mine = np.concatenate(mine) if mine else np.zeros(0)
+            n_steps[m] += len(mine)
+            tr.publish(m, detector)
+            vx, vy, vid = _corpus(valid_corpora[m])
+            v = vad_validation(detector, vx, vy, vid, columns=columns)
+            keep = v["accuracy"] > best[m][1]               # StoreBestModel.update: strictly greater
+            if keep:
+                best[m] = (tr.state_dict(m), v["accuracy"])
+            history[m].append(dict(train_loss=float(mine.mean()) if len(mine) else float("nan"), valid_loss=v["loss"],
+                                   accuracy=v["accuracy"], update_steps=n_steps[m], best=bool(keep)))
+    return [(best[m][0] if best[m][0] is not None else tr.state_dict(m), history[m]) for m in range(M)]
+
+
 def leave_one_day_out(days, start_with_day=None):
     """The folds of the reference's ``LeaveOneDayOut().split`` (local/common.py:73-101): the days sorted, rotated so that
     ``start_with_day`` (if given) comes first, then every day in turn as the test day against all the others, in that order.
@@ -957,4 +1239,4 @@ def join_corpora(corpora):
 
 
 __all__ = ["VadTrainerGPU", "train_vad", "dropout_mask", "DeviceMaskSource", "device_dropout_masks", "dropout_scale", "DecoderTrainerGPU", "train_decoder", "decoder_dropout_mask", "trial_bounds",
-           "DecoderGroupTrainerGPU", "train_decoders", "lockstep_schedule", "leave_one_day_out", "join_corpora", "LR", "ALPHA", "EPS"]
+           "DecoderGroupTrainerGPU", "train_decoders", "VadGroupTrainerGPU", "train_vads", "lockstep_schedule", "leave_one_day_out", "join_corpora", "LR", "ALPHA", "EPS"]

@@ -18,7 +18,7 @@
  * training corpus, Part 8 the two recurrent models over the trials of such a corpus (the validation passes of the
  * reference's training scripts), Part 9 the training of the neural detector, Part 10 that of the decoder, Part 11 the
  * spectrograms behind the reference's spectral analyses, Part 13 several decoders trained side by side, Part 14 the trainers'
- * dropout masks drawn on the device, each described at its declarations.
+ * dropout masks drawn on the device, Part 15 several detectors trained side by side, each described at its declarations.
  *
  * Error convention: functions returning int return 0 on success and a negative DSS_E* code on failure;
  * dss_last_error() gives a thread-local message.  Creators return NULL on failure (the reference's
@@ -844,6 +844,58 @@ int dss_dropout_masks_dev(const dss_dropout_entry *entries, int n_entries, void 
 int dss_dropout_masks_host(const dss_dropout_entry *entries, int n_entries);
 /* Self-test of the block function on the CPU: out[4] = Philox4x32-10(counter[4], key[2]). */
 int dss_selftest_philox(const unsigned *counter, const unsigned *key, unsigned *out);
+
+/* ------------------------------------------------------------------------------------------------
+ * Part 15 -- several detectors of Part 9 trained side by side: the day split of train_unidirectional_vad.py:81-93, seeds,
+ * learning rates.  Batch size 1 is a property of one training run; the runs are independent.  A group is n_models trainers of
+ * equal sizes, and a window is one window for each of them in ONE pair of Part 9's launches with a model axis on the grid
+ * (csrc/vad_train.hip), so the serial workgroups of all models run at the same time on different compute units.  The arithmetic
+ * is Part 9's, shared term for term: after any sequence of steps, every model's losses, gradients, square averages, parameters,
+ * packed copies and carried state are bit for bit those of a dss_vad_trainer given the same weights and the same windows in the
+ * same order, whatever n_models is, wherever the model sits in the group and whatever the others do.
+ * 1 <= n_models <= 64; more models are more groups.  Calls on one group are issued on one stream, or one after the other has
+ * finished.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct dss_vad_group dss_vad_group;
+/* One model's part of a step.  len == 0: the model sits the step out -- its parameters, square averages, gradients, packed
+ * copies, workspace, carried state and loss slots all stay as they were, and its pointers are not looked at.  Else device
+ * pointers as in Part 9: d_frames (len, n_inputs), d_targets uint8[len], d_mask float32 (len, H) or NULL, d_losses float64, one
+ * slot per window of the model (dss_vad_group_window_dev: one; dss_vad_group_trial_dev: ceil(len / window)). */
+typedef struct {
+    const void *d_frames;
+    const unsigned char *d_targets;
+    const float *d_mask;
+    double *d_losses;
+    double lr, alpha, eps;
+    int len, apply_step;
+} dss_vad_group_trial;
+/* The argument checks on their own (no device needed): Part 9's limits on the sizes, and 1 <= n_models <= 64. */
+int dss_vad_group_check(int n_models, int n_inputs, int hidden_units, int max_window);
+/* n_models times Part 9's device memory, plus the tables. */
+dss_vad_group *dss_vad_group_create(int n_models, int n_inputs, int hidden_units, int max_window);
+void dss_vad_group_destroy(dss_vad_group *g);
+/* dss_vad_trainer_load / _read / _state / _publish for model m (0 <= m < n_models). */
+int dss_vad_group_load(dss_vad_group *g, int m, const float *w_ih0, const float *w_hh0, const float *b_ih0, const float *b_hh0,
+                       const float *w_ih1, const float *w_hh1, const float *b_ih1, const float *b_hh1,
+                       const float *cls_w, const float *cls_b);
+int dss_vad_group_read(dss_vad_group *g, int m, int what, float *out);
+int dss_vad_group_state(dss_vad_group *g, int m, float *h, float *c, int set);
+int dss_vad_group_publish(dss_vad_group *g, int m, dss_vad *v, void *hip_stream);
+/* Both step functions: trials is a HOST array of n_models entries, read before the call returns; the frames of all models have
+ * one dtype (frames_are_f64).  Launches on hip_stream with no host synchronisation: the entries travel in a ring of eight
+ * page-locked tables, copied in stream order, so steps may be enqueued back to back (the ninth step in flight waits for the
+ * first to finish).  DSS_EINVAL before any launch, with a message that names the model, for a model with len > 0 that has no
+ * parameters loaded, len < 0, null frames, targets or losses on a model with len > 0, and for a call in which every len is 0.
+ *
+ * dss_vad_group_window_dev: one window for each model, len <= max_window frames, from the model's carried state (no reset), as
+ * dss_vad_trainer_window_dev; apply_step is honoured; the loss goes to d_losses[0].  Also refuses len > max_window. */
+int dss_vad_group_window_dev(dss_vad_group *g, const dss_vad_group_trial *trials, int frames_are_f64, void *hip_stream);
+/* dss_vad_group_trial_dev: one trial for each model, as dss_vad_trainer_trial_dev: the carried state of every model with
+ * len > 0 is zeroed (one launch), then window w = 0, 1, ... of every model is stepped by one pair of launches -- frames
+ * w * window .. of its trial, the last window being the remainder -- until the longest trial has run out; a model whose trial
+ * is over is left alone by the later pairs.  Window w's loss goes to d_losses[w]; apply_step is taken as 1.  Also refuses a
+ * window outside 1 .. max_window.  Returns the number of pairs launched, max over the models of ceil(len / window). */
+int dss_vad_group_trial_dev(dss_vad_group *g, const dss_vad_group_trial *trials, int window, int frames_are_f64, void *hip_stream);
 
 #ifdef __cplusplus
 }
