@@ -121,7 +121,7 @@ extern "C" int dss_gate_segment_dev(dss_gate *g, int stream, int event, float *d
     const float *src; int len;
     int rc = gate_segment_src(g, stream, event, cap_frames, &src, &len);
     if (rc) return rc;
-    if (!d_dst) { dss_set_error("null argument"); return DSS_EINVAL; }
+    if (len && !d_dst) { dss_set_error("null argument"); return DSS_EINVAL; }    // a tensor of 0 rows has no storage: nothing to copy
     DSS_HIP_CHECK(hipSetDevice(g->device));
     if (len) DSS_HIP_CHECK(hipMemcpyAsync(d_dst, src, sizeof(float) * (size_t)len * g->d.C, hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
     return len;
@@ -154,7 +154,7 @@ extern "C" int dss_gate_segment(dss_gate *g, int stream, int event, float *dst, 
     const float *src; int len;
     int rc = gate_segment_src(g, stream, event, cap_frames, &src, &len);
     if (rc) return rc;
-    if (!dst) { dss_set_error("null argument"); return DSS_EINVAL; }
+    if (len && !dst) { dss_set_error("null argument"); return DSS_EINVAL; }
     DSS_HIP_CHECK(hipSetDevice(g->device));
     if (len) DSS_HIP_CHECK(hipMemcpy(dst, src, sizeof(float) * (size_t)len * g->d.C, hipMemcpyDeviceToHost));
     return len;

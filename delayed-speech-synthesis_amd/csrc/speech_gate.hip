@@ -10,10 +10,13 @@
 // including their modulo arithmetic when a segment is longer than the ring.
 //
 // Mapping: one workgroup of four waves per stream.  Wave 0 runs the frame loop: a lane owns feature columns c, c+64, ...
-// of every ring, so a lane only ever reads back what it wrote itself and the loop needs no barrier.  The scalar
-// bookkeeping (pointers, counters, the label window as a 64-bit mask) is computed redundantly by every thread, so all four
-// waves agree on when a segment closes; its rows are then copied out by all 256 threads, four loads in flight per thread
-// (one wave copying row after row, each load waiting for the store before it, took ~0.3 ms for a 3.5-s segment -- on the
+// of every ring, so a lane only ever reads back what it wrote itself and the rings need no barrier inside the loop.  The
+// scalar bookkeeping (pointers, counters, the label window as a 64-bit mask) is computed redundantly by every thread from the
+// state every thread reads at entry, so all four waves agree on when a segment closes.  Thread 0 writes the next state over
+// the same words at exit: ONE barrier behind the loop keeps that write behind every wave's entry reads (on a push that
+// closes no segment it is the only barrier a wave meets; without it a wave that starts late could read the next state and
+// then disagree with the others about the barriers of a copy-out).  A closing segment's rows are copied out by all 256
+// threads, four loads in flight per thread (one wave copying row after row, each load waiting for the store before it, took ~0.3 ms for a 3.5-s segment -- on the
 // tick's critical path).  Time is the serial axis (one tick has a handful of frames); streams x features are the parallel
 // ones; every access is a coalesced row segment.
 #include "dss_common.h"
@@ -97,6 +100,7 @@ speech_gate_kernel(DssGateDev g, const double *__restrict__ frames, const int *_
             }
         }
     }
+    __syncthreads();                                          // every wave has read st[] before it is overwritten (W is uniform)
     if (tid == 0) {
         st[0] = sm_w; st[1] = sm_r; st[2] = h_w; st[3] = speech; st[4] = future;
         st[5] = (int)(unsigned)(mask & 0xffffffffull); st[6] = (int)(unsigned)(mask >> 32);

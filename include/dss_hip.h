@@ -368,7 +368,8 @@ int dss_gate_push(dss_gate *g, const double *frames, const int *labels, int n_fr
 int dss_gate_push_dev(dss_gate *g, const double *d_frames, const int *d_labels, int n_frames, int *events,
                       void *hip_stream);
 /* Copy segment `event` that `stream` completed in the LAST push: (length, nb_features) float32, at most
- * cap_frames rows.  Returns its length. */
+ * cap_frames rows.  Returns its length.  A segment of 0 rows (a speech run of buffer_size - 2 * context frames, modulo
+ * buffer_size) copies nothing and takes a null destination. */
 int dss_gate_segment(dss_gate *g, int stream, int event, float *dst, int cap_frames);
 int dss_gate_segment_dev(dss_gate *g, int stream, int event, float *d_dst, int cap_frames, void *hip_stream);
 /* The same for n segments of the LAST push in one launch: segment (streams[i], events[i]) goes to row dst_rows[i] of d_dst, a
