@@ -9,9 +9,14 @@
 // The reference's arithmetic is numpy's pocketfft and BLAS, not a fixed C sequence, so results are held to it to ~1e-12 on
 // the log energy (tests/test_gpu_acoustic_vad.py), not bit for bit; the library is built with -ffp-contract=off, so every
 // fused multiply-add here is written out (__builtin_fma, the fp64 MFMA).  Everything is float64.  Both kernels are pure
-// functions of their trial: the same trial gives the same bits alone or in any list, run after run (no atomics, every sum
-// in a fixed order).
+// functions of their trial: the same trial gives the same bits alone or in any list, run after run (every sum in a fixed
+// order; the one atomic of this file is the integer max of the peak kernel, which has no order to depend on).
+//
+// Opt-in, the trial's audio is first prepared as prepare_corpus.py:63-69 prepares it (loudness through pydub's two gains; the
+// arithmetic is avad_gain.h): a peak launch in front, the energy kernel's GAIN instantiation, and a kernel that writes the
+// prepared int16 audio out when the caller wants it (what the reference hands its feature encoder).
 #include "acoustic_vad.h"
+#include "avad_gain.h"
 
 #define AVAD_THREADS 256
 
@@ -27,9 +32,14 @@ typedef double avad_d4 __attribute__((ext_vector_type(4)));
 // B[sample l >> 4][bin l & 15]; of the f64 result, register r of lane l is [frame (l >> 4) + 4 r][bin l & 15].
 // Magnitudes go to LDS, then every (frame, band) pair sums the nonzero run of its band's column in bin order, takes
 // log(. + 1e-7), and one lane per frame adds the bands in order.
+//
+// GAIN = true is the same kernel on the PREPARED audio of a normalised call (avad_gain.h): a trial flagged `normalize` has every
+// sample scaled twice, by the factor of its peak (peaks[], avad_peak_kernel) and by the post gain, on its way into LDS; all that
+// follows sees the integers it would see had the prepared audio been handed over.  GAIN = false reads nothing of that.
+template <bool GAIN>
 __global__ void __launch_bounds__(AVAD_THREADS)
 avad_energy_kernel(const short *__restrict__ audio, const DssAvadTrialDesc *__restrict__ desc, const DssAvadTile *__restrict__ tiles,
-                   DssAvadDev p, double *__restrict__ log_energy)
+                   DssAvadDev p, double *__restrict__ log_energy, const int *__restrict__ peaks)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int N = p.N, shift = p.shift, bins = p.bins, bands = p.bands;
@@ -51,9 +61,17 @@ avad_energy_kernel(const short *__restrict__ audio, const DssAvadTrialDesc *__re
     }
     // sample s of the trial: zero in front of `lead`, audio[first + s - lead] behind it; nothing is read at or past n
     const long long s0 = (long long)frame0 * shift;
-    for (int t = tid; t < span; t += AVAD_THREADS) {
-        const long long s = s0 + t;
-        xs[t] = (s >= d.lead && s < d.n) ? (int)audio[d.first + (s - d.lead)] : 0;
+    if (GAIN && d.normalize) {
+        const double gain = p.gain[peaks[d.index]], post = p.post_gain;
+        for (int t = tid; t < span; t += AVAD_THREADS) {
+            const long long s = s0 + t;
+            xs[t] = (s >= d.lead && s < d.n) ? (int)avad_prepared(audio[d.first + (s - d.lead)], gain, post) : 0;
+        }
+    } else {
+        for (int t = tid; t < span; t += AVAD_THREADS) {
+            const long long s = s0 + t;
+            xs[t] = (s >= d.lead && s < d.n) ? (int)audio[d.first + (s - d.lead)] : 0;
+        }
     }
     __syncthreads();
 
@@ -155,8 +173,96 @@ size_t dss_avad_energy_lds_bytes(int N, int shift, int bins, int bands)
     return ((size_t)3 * N + (size_t)AVAD_TILE_FRAMES * bins) * sizeof(double) + tail;
 }
 
+// ---- peak and prepared audio -----------------------------------------------------------------------------------------------
+// max |x| over a trial's cut audio[first .. first + n): a workgroup takes AVAD_PEAK_TILE samples of one trial -- 16-byte loads
+// where the address allows (`first` may be odd: the samples in front of the first aligned address and behind the last full
+// vector are read one by one) --, reduces them in registers and LDS and joins the trial's other tiles through one integer
+// atomicMax into peaks[trial], which the host zeroed on the same stream.  Integer max has no order: the same bits on every run.
+__device__ static inline int avad_abs_pair(unsigned w)
+{
+    const int a = avad_abs16((short)(w & 0xffffu)), b = avad_abs16((short)(w >> 16));
+    return a > b ? a : b;
+}
+
+__global__ void __launch_bounds__(AVAD_THREADS)
+avad_peak_kernel(const short *__restrict__ audio, const DssAvadPeakTile *__restrict__ tiles, int *__restrict__ peaks)
+{
+    __shared__ int part[AVAD_THREADS / 64];
+    const int tid = threadIdx.x;
+    const DssAvadPeakTile tile = tiles[blockIdx.x];
+    const short *x = audio + tile.first;
+    const int cnt = tile.n;
+    int head = (int)(((16u - (unsigned)((size_t)x & 15u)) & 15u) >> 1);
+    if (head > cnt) head = cnt;
+    const int nvec = (cnt - head) >> 3;
+    int m = 0;
+    if (tid < head) m = avad_abs16(x[tid]);
+    const uint4 *xv = reinterpret_cast<const uint4 *>(x + head);
+    for (int i = tid; i < nvec; i += AVAD_THREADS) {
+        const uint4 v = xv[i];
+        const int a = avad_abs_pair(v.x), b = avad_abs_pair(v.y), c = avad_abs_pair(v.z), e = avad_abs_pair(v.w);
+        const int ab = a > b ? a : b, ce = c > e ? c : e;
+        const int q = ab > ce ? ab : ce;
+        m = m > q ? m : q;
+    }
+    for (int i = head + 8 * nvec + tid; i < cnt; i += AVAD_THREADS) {
+        const int a = avad_abs16(x[i]);
+        m = m > a ? m : a;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const int other = __shfl_xor(m, o);
+        m = m > other ? m : other;
+    }
+    if ((tid & 63) == 0) part[tid >> 6] = m;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < AVAD_THREADS / 64; ++w) m = m > part[w] ? m : part[w];
+        atomicMax(peaks + tile.index, m);
+    }
+}
+
+// The prepared trials themselves, int16, trial after trial in list order: `lead` zeros, then the first n - lead samples of the
+// cut, scaled as the energy kernel scales them when the trial is flagged.  A workgroup writes AVAD_PEAK_TILE samples of one trial.
+__global__ void __launch_bounds__(AVAD_THREADS)
+avad_prepare_kernel(const short *__restrict__ audio, const DssAvadTrialDesc *__restrict__ desc, const DssAvadTile *__restrict__ tiles,
+                    DssAvadDev p, const int *__restrict__ peaks, short *__restrict__ prepared)
+{
+    const int tid = threadIdx.x;
+    const DssAvadTile tile = tiles[blockIdx.x];
+    const DssAvadTrialDesc d = desc[tile.trial];
+    const int s0 = tile.frame0;                                       // first sample of the tile, not a frame
+    const int s1 = d.n - s0 < AVAD_PEAK_TILE ? d.n : s0 + AVAD_PEAK_TILE;
+    short *out = prepared + d.out_sample;
+    const short *in = audio + d.first - d.lead;
+    if (d.normalize) {
+        const double gain = p.gain[peaks[d.index]], post = p.post_gain;
+        for (int s = s0 + tid; s < s1; s += AVAD_THREADS) out[s] = s >= d.lead ? avad_prepared(in[s], gain, post) : (short)0;
+    } else {
+        for (int s = s0 + tid; s < s1; s += AVAD_THREADS) out[s] = s >= d.lead ? in[s] : (short)0;
+    }
+}
+
+int dss_launch_avad_peak(const short *d_audio, const DssAvadPeakTile *d_tiles, int n_tiles, int *d_peaks, hipStream_t s)
+{
+    if (n_tiles <= 0) return DSS_OK;
+    hipLaunchKernelGGL(avad_peak_kernel, dim3((unsigned)n_tiles), dim3(AVAD_THREADS), 0, s, d_audio, d_tiles, d_peaks);
+    DSS_HIP_CHECK(hipGetLastError());
+    return DSS_OK;
+}
+
+int dss_launch_avad_prepare(const DssAvadDev &v, const short *d_audio, const DssAvadTrialDesc *d_desc, const DssAvadTile *d_tiles,
+                            int n_tiles, const int *d_peaks, short *d_prepared, hipStream_t s)
+{
+    if (n_tiles <= 0) return DSS_OK;
+    hipLaunchKernelGGL(avad_prepare_kernel, dim3((unsigned)n_tiles), dim3(AVAD_THREADS), 0, s, d_audio, d_desc, d_tiles, v, d_peaks,
+                       d_prepared);
+    DSS_HIP_CHECK(hipGetLastError());
+    return DSS_OK;
+}
+
+// d_peaks == NULL: the plain kernel on the audio as it is; else the prepared audio of the trials flagged `normalize`
 int dss_launch_avad_energy(const DssAvadDev &v, const short *d_audio, const DssAvadTrialDesc *d_desc, const DssAvadTile *d_tiles,
-                           int n_tiles, double *d_log_energy, hipStream_t s)
+                           int n_tiles, double *d_log_energy, const int *d_peaks, hipStream_t s)
 {
     if (n_tiles <= 0) return DSS_OK;
     const size_t bytes = dss_avad_energy_lds_bytes(v.N, v.shift, v.bins, v.bands);
@@ -164,9 +270,15 @@ int dss_launch_avad_energy(const DssAvadDev &v, const short *d_audio, const DssA
         dss_set_error("acoustic VAD: a window of %d samples with %d bands does not fit the energy kernel", v.N, v.bands);
         return DSS_EINVAL;
     }
-    DSS_HIP_CHECK(hipFuncSetAttribute((const void *)avad_energy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    hipLaunchKernelGGL(avad_energy_kernel, dim3((unsigned)n_tiles), dim3(AVAD_THREADS), bytes, s, d_audio, d_desc, d_tiles, v,
-                       d_log_energy);
+    if (d_peaks) {
+        DSS_HIP_CHECK(hipFuncSetAttribute((const void *)avad_energy_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        hipLaunchKernelGGL(avad_energy_kernel<true>, dim3((unsigned)n_tiles), dim3(AVAD_THREADS), bytes, s, d_audio, d_desc, d_tiles, v,
+                           d_log_energy, d_peaks);
+    } else {
+        DSS_HIP_CHECK(hipFuncSetAttribute((const void *)avad_energy_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        hipLaunchKernelGGL(avad_energy_kernel<false>, dim3((unsigned)n_tiles), dim3(AVAD_THREADS), bytes, s, d_audio, d_desc, d_tiles, v,
+                           d_log_energy, d_peaks);
+    }
     DSS_HIP_CHECK(hipGetLastError());
     return DSS_OK;
 }

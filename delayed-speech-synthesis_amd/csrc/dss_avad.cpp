@@ -2,13 +2,15 @@
 //
 // Owns the tables (window, twiddles, the mel matrix's nonzero runs), the descriptor and tile tables of a call and the
 // staging of the host-buffer form; the arithmetic of steps 3-5 runs in csrc/acoustic_vad.hip only.  Every check and the
-// threshold / vote of one trial are handle-free host functions, so they are testable without a device.
+// threshold / vote of one trial are handle-free host functions, so they are testable without a device; so are the peak and
+// the scaling of the prepared audio, which are avad_gain.h's functions, the ones the kernels call.
 #include <math.h>
 
 #include <algorithm>
 #include <vector>
 
 #include "acoustic_vad.h"
+#include "avad_gain.h"
 #include "dss_host.h"
 
 struct dss_avad {
@@ -29,6 +31,24 @@ struct dss_avad {
     unsigned char *d_labels = nullptr;   size_t labels_cap = 0;
     double *d_le_out = nullptr;          size_t le_out_cap = 0;
     double *d_thr = nullptr;             size_t thr_cap = 0;
+    // the prepared audio (dss_avad_set_gain, dss_avad_prepare_trials*)
+    double *d_gain = nullptr;            bool gain_set = false;
+    std::vector<DssAvadPeakTile> ptiles;
+    std::vector<DssAvadTile> stiles;
+    DssAvadPeakTile *d_ptiles = nullptr; size_t ptiles_cap = 0;
+    DssAvadTile *d_stiles = nullptr;     size_t stiles_cap = 0;
+    int *d_peaks = nullptr;              size_t peaks_cap = 0;
+    short *d_prep = nullptr;             size_t prep_cap = 0;
+};
+
+// One call's outputs and options, all optional but for what the entry point demands.
+struct AvadCall {
+    const unsigned char *silence = nullptr, *normalize = nullptr;
+    unsigned char *d_labels = nullptr;
+    double *d_le = nullptr, *d_thr = nullptr;
+    short *d_prepared = nullptr;
+    int *d_peaks = nullptr;
+    long long n_avail = 0;               // samples behind audio_base that d_audio holds (the peak's cut is clamped there)
 };
 
 extern "C" int dss_avad_check_params(const dss_avad_params *p)
@@ -56,8 +76,9 @@ extern "C" int dss_avad_trial_frames_for(int n, int window, int shift)
     return (n - window) / shift + 1;
 }
 
-extern "C" int dss_avad_check_trials(long long n_audio, int n_trials, const long long *first, const int *len, const int *lead,
-                                     int window, int shift)
+// frames = false: the list of a call that wants the prepared audio only, where a trial may be shorter than one window
+static int avad_check_list(long long n_audio, int n_trials, const long long *first, const int *len, const int *lead, int window,
+                           int shift, bool frames)
 {
     if (window <= 0 || shift <= 0) { dss_set_error("acoustic VAD: bad frame shape"); return DSS_EINVAL; }
     if (n_trials < 0 || n_audio < 0) { dss_set_error("bad trial list: negative count"); return DSS_EINVAL; }
@@ -71,11 +92,36 @@ extern "C" int dss_avad_check_trials(long long n_audio, int n_trials, const long
                           first[i] + (long long)(len[i] - lead[i]), n_audio);
             return DSS_EINVAL;
         }
+        if (!frames) continue;
         if (len[i] < window) { dss_set_error("trial %d: %d samples are shorter than one window (%d samples)", i, len[i], window); return DSS_EINVAL; }
         total += (len[i] - window) / shift + 1;
         if (total > 0x7fffffffLL) { dss_set_error("trial list emits more than 2^31 - 1 frames"); return DSS_EINVAL; }
     }
     return (int)total;
+}
+
+extern "C" int dss_avad_check_trials(long long n_audio, int n_trials, const long long *first, const int *len, const int *lead,
+                                     int window, int shift)
+{
+    return avad_check_list(n_audio, n_trials, first, len, lead, window, shift, true);
+}
+
+extern "C" int dss_avad_peak_tile(void) { return AVAD_PEAK_TILE; }
+
+extern "C" int dss_avad_peak_host(const int16_t *x, long long n)
+{
+    if (n < 0 || (n && !x)) { dss_set_error("acoustic VAD peak: bad arguments"); return DSS_EINVAL; }
+    int m = 0;
+    for (long long i = 0; i < n; ++i) m = std::max(m, avad_abs16(x[i]));
+    return m;
+}
+
+extern "C" int dss_avad_scale_host(const int16_t *x, long long n, double factor, int16_t *out)
+{
+    if (n < 0 || (n && (!x || !out))) { dss_set_error("acoustic VAD scale: bad arguments"); return DSS_EINVAL; }
+    if (!isfinite(factor)) { dss_set_error("acoustic VAD scale: the factor is not finite"); return DSS_EINVAL; }
+    for (long long i = 0; i < n; ++i) out[i] = avad_scale(x[i], factor);
+    return DSS_OK;
 }
 
 // the sum of the device kernel (avad_vote_kernel): 256 strided running sums, then a halving tree
@@ -176,35 +222,104 @@ extern "C" dss_avad *dss_avad_create(const dss_avad_params *p, const double *win
     return h;
 }
 
-// The trial list on device-resident audio.  d_audio holds samples audio_base .. of the caller's array.
+extern "C" int dss_avad_set_gain(dss_avad *h, const double *gain_by_peak, double post_gain)
+{
+    if (!gain_by_peak) { dss_set_error("acoustic VAD gain: bad arguments"); return DSS_EINVAL; }
+    // the data is judged before the handle is looked at, so that the refusals need no device
+    for (int k = 0; k < AVAD_GAIN_ENTRIES; ++k)
+        if (!isfinite(gain_by_peak[k]) || gain_by_peak[k] < 0.0) {
+            dss_set_error("acoustic VAD gain: the factor of peak %d is negative or not finite", k);
+            return DSS_EINVAL;
+        }
+    if (!isfinite(post_gain) || post_gain < 0.0) { dss_set_error("acoustic VAD gain: the post gain is negative or not finite"); return DSS_EINVAL; }
+    if (!h) { dss_set_error("acoustic VAD gain: no handle"); return DSS_EINVAL; }
+    DSS_HIP_CHECK(hipSetDevice(h->device));
+    DSS_HIP_CHECK(hipDeviceSynchronize());                            // a call still queued reads the table it was issued with
+    if (!h->d_gain) {
+        int rc = h->blocks.upload(gain_by_peak, (size_t)AVAD_GAIN_ENTRIES, &h->d_gain);
+        if (rc) return rc;
+    } else {
+        DSS_HIP_CHECK(hipMemcpy(h->d_gain, gain_by_peak, sizeof(double) * AVAD_GAIN_ENTRIES, hipMemcpyHostToDevice));
+    }
+    h->d.gain = h->d_gain;
+    h->d.post_gain = post_gain;
+    h->gain_set = true;
+    return DSS_OK;
+}
+
+// The trial list on device-resident audio.  d_audio holds samples audio_base .. audio_base + c.n_avail of the caller's array.
+// Launches: peak (when a trial is normalised or the peaks are asked for), energy and vote (when labels are asked for), prepared
+// audio (when asked for); nothing waits for the device in between.
 static int avad_run(dss_avad *h, const short *d_audio, long long audio_base, int n_trials, const long long *first, const int *len,
-                    const int *lead, const unsigned char *silence, unsigned char *d_labels, double *d_le, double *d_thr, hipStream_t st)
+                    const int *lead, const AvadCall &c, hipStream_t st)
 {
     const int N = h->p.window, shift = h->p.shift;
+    const bool want_frames = c.d_labels != nullptr;
+    bool use_gain = false;
+    for (int i = 0; c.normalize && i < n_trials; ++i) use_gain = use_gain || c.normalize[i];
+    if (use_gain && !h->gain_set) { dss_set_error("acoustic VAD: trials to normalise but no gain table set (dss_avad_set_gain)"); return DSS_EINVAL; }
+    const bool want_peaks = use_gain || c.d_peaks;
     // descriptor table, longest trial first: the long trials' tiles start first and the short ones fill the tail
     const std::vector<int> order = trials_longest_first(n_trials, len);
-    std::vector<long long> out_frame((size_t)n_trials);
-    long long total = 0;
-    for (int i = 0; i < n_trials; ++i) { out_frame[i] = total; total += (len[i] - N) / shift + 1; }
+    std::vector<long long> out_frame((size_t)n_trials), out_sample((size_t)n_trials);
+    long long total = 0, samples = 0;
+    for (int i = 0; i < n_trials; ++i) {
+        out_frame[i] = total; out_sample[i] = samples;
+        if (want_frames) total += (len[i] - N) / shift + 1;
+        samples += len[i];
+    }
     h->desc.resize((size_t)n_trials);
-    h->tiles.clear();
+    h->tiles.clear(); h->ptiles.clear(); h->stiles.clear();
     for (int k = 0; k < n_trials; ++k) {
         const int i = order[k];
         DssAvadTrialDesc &t = h->desc[k];
-        t.first = first[i] - audio_base; t.out_frame = out_frame[i]; t.n = len[i]; t.lead = lead[i];
-        t.W = (len[i] - N) / shift + 1; t.silence = silence && silence[i] ? 1 : 0; t.index = i; t.pad = 0;
+        t.first = first[i] - audio_base; t.out_frame = out_frame[i]; t.out_sample = out_sample[i]; t.n = len[i]; t.lead = lead[i];
+        t.W = want_frames ? (len[i] - N) / shift + 1 : 0; t.silence = c.silence && c.silence[i] ? 1 : 0; t.index = i;
+        t.normalize = c.normalize && c.normalize[i] ? 1 : 0;
         for (int f0 = 0; f0 < t.W; f0 += AVAD_TILE_FRAMES) h->tiles.push_back(DssAvadTile{k, f0});
+        if (want_peaks) {
+            // the cut audio[first .. first + n), clamped where the audio ends: the last `lead` samples count although the shift drops them
+            const long long cut = std::min((long long)len[i], c.n_avail - t.first);
+            for (long long s0 = 0; s0 < cut; s0 += AVAD_PEAK_TILE)
+                h->ptiles.push_back(DssAvadPeakTile{t.first + s0, (int)std::min((long long)AVAD_PEAK_TILE, cut - s0), i});
+        }
+        if (c.d_prepared)
+            for (long long s0 = 0; s0 < t.n; s0 += AVAD_PEAK_TILE) h->stiles.push_back(DssAvadTile{k, (int)s0});
     }
-    if (h->tiles.size() > 0x7fffffffULL) { dss_set_error("acoustic VAD: too many tiles for one launch"); return DSS_EINVAL; }
+    if (h->tiles.size() > 0x7fffffffULL || h->ptiles.size() > 0x7fffffffULL || h->stiles.size() > 0x7fffffffULL) {
+        dss_set_error("acoustic VAD: too many tiles for one launch");
+        return DSS_EINVAL;
+    }
+    double *d_le = c.d_le;
+    int *d_peaks = c.d_peaks;
     int rc = h->blocks.grow_headroom(&h->d_desc, &h->desc_cap, h->desc.size());
     if (!rc) rc = h->blocks.grow_headroom(&h->d_tiles, &h->tiles_cap, h->tiles.size());
-    if (!rc && !d_le) { rc = h->blocks.grow_headroom(&h->d_le, &h->le_cap, (size_t)total); d_le = h->d_le; }
+    if (!rc && want_frames && !d_le) { rc = h->blocks.grow_headroom(&h->d_le, &h->le_cap, (size_t)total); d_le = h->d_le; }
+    if (!rc && want_peaks) rc = h->blocks.grow_headroom(&h->d_ptiles, &h->ptiles_cap, h->ptiles.size());
+    if (!rc && want_peaks && !d_peaks) { rc = h->blocks.grow_headroom(&h->d_peaks, &h->peaks_cap, (size_t)n_trials); d_peaks = h->d_peaks; }
+    if (!rc && c.d_prepared) rc = h->blocks.grow_headroom(&h->d_stiles, &h->stiles_cap, h->stiles.size());
     if (rc) return rc;
     DSS_HIP_CHECK(hipMemcpyAsync(h->d_desc, h->desc.data(), sizeof(DssAvadTrialDesc) * h->desc.size(), hipMemcpyHostToDevice, st));
-    DSS_HIP_CHECK(hipMemcpyAsync(h->d_tiles, h->tiles.data(), sizeof(DssAvadTile) * h->tiles.size(), hipMemcpyHostToDevice, st));
-    rc = dss_launch_avad_energy(h->d, d_audio, h->d_desc, h->d_tiles, (int)h->tiles.size(), d_le, st);
-    if (!rc) rc = dss_launch_avad_vote(h->d, h->d_desc, n_trials, d_le, d_labels, d_thr, st);
-    return rc ? rc : (int)total;
+    if (!h->tiles.empty())
+        DSS_HIP_CHECK(hipMemcpyAsync(h->d_tiles, h->tiles.data(), sizeof(DssAvadTile) * h->tiles.size(), hipMemcpyHostToDevice, st));
+    if (want_peaks) {
+        DSS_HIP_CHECK(hipMemsetAsync(d_peaks, 0, sizeof(int) * (size_t)n_trials, st));
+        if (!h->ptiles.empty())
+            DSS_HIP_CHECK(hipMemcpyAsync(h->d_ptiles, h->ptiles.data(), sizeof(DssAvadPeakTile) * h->ptiles.size(), hipMemcpyHostToDevice, st));
+        rc = dss_launch_avad_peak(d_audio, h->d_ptiles, (int)h->ptiles.size(), d_peaks, st);
+        if (rc) return rc;
+    }
+    if (want_frames) {
+        rc = dss_launch_avad_energy(h->d, d_audio, h->d_desc, h->d_tiles, (int)h->tiles.size(), d_le, use_gain ? d_peaks : nullptr, st);
+        if (!rc) rc = dss_launch_avad_vote(h->d, h->d_desc, n_trials, d_le, c.d_labels, c.d_thr, st);
+        if (rc) return rc;
+    }
+    if (c.d_prepared && !h->stiles.empty()) {
+        DSS_HIP_CHECK(hipMemcpyAsync(h->d_stiles, h->stiles.data(), sizeof(DssAvadTile) * h->stiles.size(), hipMemcpyHostToDevice, st));
+        rc = dss_launch_avad_prepare(h->d, d_audio, h->d_desc, h->d_stiles, (int)h->stiles.size(), d_peaks, c.d_prepared, st);
+        if (rc) return rc;
+    }
+    return (int)total;
 }
 
 extern "C" int dss_avad_labels_trials_dev(dss_avad *h, const int16_t *d_audio, long long n_audio, int n_trials, const long long *first,
@@ -216,7 +331,9 @@ extern "C" int dss_avad_labels_trials_dev(dss_avad *h, const int16_t *d_audio, l
     if (total <= 0) return total;
     if (!d_audio || !d_labels) { dss_set_error("bad arguments"); return DSS_EINVAL; }
     DSS_HIP_CHECK(hipSetDevice(h->device));
-    return avad_run(h, d_audio, 0, n_trials, first, len, lead, silence, d_labels, d_log_energy, d_threshold, (hipStream_t)hip_stream);
+    AvadCall c;
+    c.silence = silence; c.d_labels = d_labels; c.d_le = d_log_energy; c.d_thr = d_threshold; c.n_avail = n_audio;
+    return avad_run(h, d_audio, 0, n_trials, first, len, lead, c, (hipStream_t)hip_stream);
 }
 
 extern "C" int dss_avad_labels_trials(dss_avad *h, const int16_t *audio, long long n_audio, int n_trials, const long long *first,
@@ -237,10 +354,73 @@ extern "C" int dss_avad_labels_trials(dss_avad *h, const int16_t *audio, long lo
     if (!rc) rc = h->blocks.grow_headroom(&h->d_thr, &h->thr_cap, (size_t)n_trials);
     if (rc) return rc;
     if (hi > lo) DSS_HIP_CHECK(hipMemcpy(h->d_audio, audio + lo, sizeof(short) * (size_t)(hi - lo), hipMemcpyHostToDevice));
-    rc = avad_run(h, h->d_audio, lo, n_trials, first, len, lead, silence, h->d_labels, h->d_le_out, h->d_thr, nullptr);
+    AvadCall c;
+    c.silence = silence; c.d_labels = h->d_labels; c.d_le = h->d_le_out; c.d_thr = h->d_thr; c.n_avail = hi - lo;
+    rc = avad_run(h, h->d_audio, lo, n_trials, first, len, lead, c, nullptr);
     if (rc < 0) return rc;
     DSS_HIP_CHECK(hipMemcpy(labels, h->d_labels, (size_t)total, hipMemcpyDeviceToHost));
     if (log_energy) DSS_HIP_CHECK(hipMemcpy(log_energy, h->d_le_out, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost));
     if (threshold) DSS_HIP_CHECK(hipMemcpy(threshold, h->d_thr, sizeof(double) * (size_t)n_trials, hipMemcpyDeviceToHost));
+    return total;
+}
+
+// ---- the prepared audio: labels of normalised trials, and the int16 trials themselves ------------------------------------------
+static int avad_prepare_check(dss_avad *h, long long n_audio, int n_trials, const long long *first, const int *len, const int *lead,
+                              const void *labels, const void *log_energy, const void *threshold, const void *prepared, const void *peaks)
+{
+    if (!h) { dss_set_error("bad arguments"); return DSS_EINVAL; }
+    if (!labels && (log_energy || threshold)) { dss_set_error("acoustic VAD: log energies and thresholds come with the labels only"); return DSS_EINVAL; }
+    if (!labels && !prepared && !peaks) { dss_set_error("acoustic VAD: no output asked for"); return DSS_EINVAL; }
+    return avad_check_list(n_audio, n_trials, first, len, lead, h->p.window, h->p.shift, labels != nullptr);
+}
+
+extern "C" int dss_avad_prepare_trials_dev(dss_avad *h, const int16_t *d_audio, long long n_audio, int n_trials, const long long *first,
+                                           const int *len, const int *lead, const unsigned char *silence, const unsigned char *normalize,
+                                           unsigned char *d_labels, double *d_log_energy, double *d_threshold, int16_t *d_prepared,
+                                           int *d_peaks, void *hip_stream)
+{
+    const int total = avad_prepare_check(h, n_audio, n_trials, first, len, lead, d_labels, d_log_energy, d_threshold, d_prepared, d_peaks);
+    if (total < 0 || n_trials == 0) return total;
+    if (!d_audio) { dss_set_error("bad arguments"); return DSS_EINVAL; }
+    DSS_HIP_CHECK(hipSetDevice(h->device));
+    AvadCall c;
+    c.silence = silence; c.normalize = normalize; c.d_labels = d_labels; c.d_le = d_log_energy; c.d_thr = d_threshold;
+    c.d_prepared = d_prepared; c.d_peaks = d_peaks; c.n_avail = n_audio;
+    return avad_run(h, d_audio, 0, n_trials, first, len, lead, c, (hipStream_t)hip_stream);
+}
+
+extern "C" int dss_avad_prepare_trials(dss_avad *h, const int16_t *audio, long long n_audio, int n_trials, const long long *first,
+                                       const int *len, const int *lead, const unsigned char *silence, const unsigned char *normalize,
+                                       unsigned char *labels, double *log_energy, double *threshold, int16_t *prepared, int *peaks)
+{
+    const int total = avad_prepare_check(h, n_audio, n_trials, first, len, lead, labels, log_energy, threshold, prepared, peaks);
+    if (total < 0 || n_trials == 0) return total;
+    if (!audio) { dss_set_error("bad arguments"); return DSS_EINVAL; }
+    DSS_HIP_CHECK(hipSetDevice(h->device));
+    // the whole cut of every trial crosses the bus (the peak is taken over the samples the shift drops too), clamped at the end
+    long long lo, hi, samples = 0;
+    trials_hull(n_trials, first, len, nullptr, &lo, &hi);
+    hi = std::max(lo, std::min(hi, n_audio));
+    for (int i = 0; i < n_trials; ++i) samples += len[i];
+    int rc = h->blocks.grow_headroom(&h->d_audio, &h->audio_cap, (size_t)(hi - lo) + 1);
+    if (!rc && labels) rc = h->blocks.grow_headroom(&h->d_labels, &h->labels_cap, (size_t)total);
+    if (!rc && labels) rc = h->blocks.grow_headroom(&h->d_le_out, &h->le_out_cap, (size_t)total);
+    if (!rc && labels) rc = h->blocks.grow_headroom(&h->d_thr, &h->thr_cap, (size_t)n_trials);
+    if (!rc && prepared) rc = h->blocks.grow_headroom(&h->d_prep, &h->prep_cap, (size_t)samples + 1);
+    if (!rc && peaks) rc = h->blocks.grow_headroom(&h->d_peaks, &h->peaks_cap, (size_t)n_trials);
+    if (rc) return rc;
+    if (hi > lo) DSS_HIP_CHECK(hipMemcpy(h->d_audio, audio + lo, sizeof(short) * (size_t)(hi - lo), hipMemcpyHostToDevice));
+    AvadCall c;
+    c.silence = silence; c.normalize = normalize; c.n_avail = hi - lo;
+    if (labels) { c.d_labels = h->d_labels; c.d_le = h->d_le_out; c.d_thr = h->d_thr; }
+    if (prepared) c.d_prepared = h->d_prep;
+    if (peaks) c.d_peaks = h->d_peaks;
+    rc = avad_run(h, h->d_audio, lo, n_trials, first, len, lead, c, nullptr);
+    if (rc < 0) return rc;
+    if (labels && total) DSS_HIP_CHECK(hipMemcpy(labels, h->d_labels, (size_t)total, hipMemcpyDeviceToHost));
+    if (log_energy && total) DSS_HIP_CHECK(hipMemcpy(log_energy, h->d_le_out, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost));
+    if (threshold) DSS_HIP_CHECK(hipMemcpy(threshold, h->d_thr, sizeof(double) * (size_t)n_trials, hipMemcpyDeviceToHost));
+    if (prepared && samples) DSS_HIP_CHECK(hipMemcpy(prepared, h->d_prep, sizeof(short) * (size_t)samples, hipMemcpyDeviceToHost));
+    if (peaks) DSS_HIP_CHECK(hipMemcpy(peaks, h->d_peaks, sizeof(int) * (size_t)n_trials, hipMemcpyDeviceToHost));
     return total;
 }

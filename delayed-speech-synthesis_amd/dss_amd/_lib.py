@@ -130,6 +130,12 @@ def _declare(L):
         "dss_avad_labels_trials": (i, [vp, vp, C.c_longlong, i, vp, vp, vp, vp, vp, vp, vp]),
         "dss_avad_labels_trials_dev": (i, [vp, vp, C.c_longlong, i, vp, vp, vp, vp, vp, vp, vp, vp]),
         "dss_avad_vote_host": (i, [vp, i, vp, vp, vp]),
+        "dss_avad_peak_host": (i, [vp, C.c_longlong]),
+        "dss_avad_scale_host": (i, [vp, C.c_longlong, C.c_double, vp]),
+        "dss_avad_peak_tile": (i, []),
+        "dss_avad_set_gain": (i, [vp, vp, C.c_double]),
+        "dss_avad_prepare_trials": (i, [vp, vp, C.c_longlong, i] + [vp] * 10),
+        "dss_avad_prepare_trials_dev": (i, [vp, vp, C.c_longlong, i] + [vp] * 11),
         "dss_trials_check": (i, [C.c_longlong, i, vp, vp, vp]),
         "dss_vad_forward_trials_dev": (i, [vp, vp, i, C.c_longlong, i, vp, vp, vp, vp, vp]),
         "dss_vad_score_trials_dev": (i, [vp, vp, vp, i, vp, vp, vp, vp, vp]),

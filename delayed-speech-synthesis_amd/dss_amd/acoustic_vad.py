@@ -6,9 +6,13 @@ The ``vad_labels`` of the training corpus (``prepare_corpus.get_vad_labels``, pr
 mean log energy and a vote over neighbouring frames.  ``AcousticVadGPU.labels_trials`` does that for a whole trial list in
 two launches (csrc/acoustic_vad.hip) on audio that crosses the bus once.
 
-The audio is taken *as the caller hands it over*: the reference also normalises the loudness of every non-silence trial
-through ``pydub`` (``prepare_corpus._normalize_audio``) before it labels it, and that step is not part of this package.  Pass
-the raw session wav, or your own normalised trial audio concatenated, plus one ``(first sample, length)`` range per trial.
+By default the audio is taken *as the caller hands it over*.  The reference also normalises the loudness of every non-silence
+trial through ``pydub`` (``prepare_corpus._normalize_audio``) before it labels it; that step is opt-in here: ``set_gain()`` and
+``normalize=True`` give the labels of the audio as the reference prepares it (a peak launch in front, the two gains applied
+as the energy kernel stages its samples), and ``prepared_audio_trials`` returns that audio itself, which is what the
+reference's feature encoder is given.  The arithmetic is pinned by tests/golden/trial_audio.npz (Python's own ``audioop``);
+the gain table is data from ``dss_amd.trial_audio``.  Pass the raw session wav plus one ``(first sample, length)`` range per
+trial.
 
 The window and the mel matrix are computed here, from their definitions, and handed to the library as data.
 """
@@ -20,7 +24,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _lib, trial_audio
 
 
 class AvadParams(C.Structure):
@@ -142,13 +146,41 @@ class AcousticVadGPU:
                 raise ValueError("silence must hold one flag per trial")
         return first, length, ld, sil, total
 
+    def set_gain(self, table=None, post: Optional[float] = None):
+        """The loudness step's data: ``table`` float64 (32769,) factor by peak (default ``trial_audio.pydub_gain_table()``:
+        pydub's ``effects.normalize`` at 0.1 dB headroom) and the ``post`` factor (default ``trial_audio.post_gain()``: -3 dB).
+        Uploaded once; DssError for a negative or non-finite entry."""
+        t = np.ascontiguousarray(trial_audio.pydub_gain_table() if table is None else table, dtype=np.float64).reshape(-1)
+        if len(t) != trial_audio.N_PEAKS:
+            raise ValueError("the gain table holds one factor per peak 0 .. 32768")
+        _lib.check(self._L.dss_avad_set_gain(self._h, t.ctypes.data, float(trial_audio.post_gain() if post is None else post)))
+        self._gain_set = True
+
+    def _normalize_flags(self, normalize, sil, n_trials):
+        """None -> None; True -> every trial that is not silent; a sequence -> one flag per trial."""
+        if normalize is None:
+            return None
+        if isinstance(normalize, (bool, np.bool_)):
+            flags = np.full(n_trials, bool(normalize))
+            if sil is not None:
+                flags &= ~sil.astype(bool)
+        else:
+            flags = np.asarray(normalize).astype(bool).reshape(-1)
+            if len(flags) != n_trials:
+                raise ValueError("normalize must hold one flag per trial")
+        if flags.any() and not getattr(self, "_gain_set", False):
+            self.set_gain()
+        return np.ascontiguousarray(flags.astype(np.uint8))
+
     def labels_trials(self, audio: np.ndarray, ranges, lead=0, silence: Optional[Sequence[bool]] = None,
-                      return_energy: bool = False):
-        """``audio`` int16 (n,) host, as the caller hands it over (no loudness normalisation is applied); ``ranges``
+                      return_energy: bool = False, normalize=None):
+        """``audio`` int16 (n,) host, as the caller hands it over (no loudness normalisation unless ``normalize``); ``ranges``
         [(first sample, length)]: trial i is ``lead`` zeros followed by ``audio[first : first + length - lead]`` (the
         reference's 16 ms shift is ``lead=256``); ``silence``: trials that get all-zero labels.  Returns bool (sum W_i,)
         labels, trial after trial in list order; with ``return_energy`` also the float64 log energies (sum W_i,) and the
-        thresholds (n_trials,)."""
+        thresholds (n_trials,).  ``normalize``: None is the plain call; True labels every trial that is not silent on its
+        audio as the reference prepares it (module docstring; ``set_gain`` with the pydub defaults unless called before); a
+        sequence flags the trials one by one."""
         a = np.asarray(audio)
         if a.dtype != np.int16 or a.ndim != 1:
             raise ValueError("audio must be a one-dimensional int16 array")
@@ -157,7 +189,14 @@ class AcousticVadGPU:
         labels = np.zeros(total, dtype=np.uint8)
         le = np.zeros(total, dtype=np.float64) if return_energy else None
         thr = np.zeros(len(first), dtype=np.float64) if return_energy else None
-        if total:
+        norm = self._normalize_flags(normalize, sil, len(first))
+        if total and norm is not None:
+            got = _lib.check(self._L.dss_avad_prepare_trials(
+                self._h, a.ctypes.data, len(a), len(first), first.ctypes.data, length.ctypes.data, ld.ctypes.data,
+                sil.ctypes.data if sil is not None else None, norm.ctypes.data, labels.ctypes.data,
+                le.ctypes.data if return_energy else None, thr.ctypes.data if return_energy else None, None, None))
+            assert got == total
+        elif total:
             got = _lib.check(self._L.dss_avad_labels_trials(
                 self._h, a.ctypes.data, len(a), len(first), first.ctypes.data, length.ctypes.data, ld.ctypes.data,
                 sil.ctypes.data if sil is not None else None, labels.ctypes.data,
@@ -166,7 +205,7 @@ class AcousticVadGPU:
         return (labels.astype(bool), le, thr) if return_energy else labels.astype(bool)
 
     def labels_trials_torch(self, audio, ranges, lead=0, silence: Optional[Sequence[bool]] = None,
-                            return_energy: bool = False, stream=None):
+                            return_energy: bool = False, stream=None, normalize=None):
         """Device-resident form: CUDA int16 (n,) tensor -> CUDA uint8 (sum W_i,) labels (and float64 log energies and
         thresholds); queued on the current (or the given) stream, no synchronisation.  The same audio contract as
         ``labels_trials``."""
@@ -178,10 +217,70 @@ class AcousticVadGPU:
         le = torch.empty(total, dtype=torch.float64, device=dev) if return_energy else None
         thr = torch.empty(len(first), dtype=torch.float64, device=dev) if return_energy else None
         s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        if total:
+        norm = self._normalize_flags(normalize, sil, len(first))
+        if total and norm is not None:
+            got = _lib.check(self._L.dss_avad_prepare_trials_dev(
+                self._h, audio.data_ptr(), audio.shape[0], len(first), first.ctypes.data, length.ctypes.data, ld.ctypes.data,
+                sil.ctypes.data if sil is not None else None, norm.ctypes.data, labels.data_ptr(),
+                le.data_ptr() if return_energy else None, thr.data_ptr() if return_energy else None, None, None, s))
+            assert got == total
+        elif total:
             got = _lib.check(self._L.dss_avad_labels_trials_dev(
                 self._h, audio.data_ptr(), audio.shape[0], len(first), first.ctypes.data, length.ctypes.data, ld.ctypes.data,
                 sil.ctypes.data if sil is not None else None, labels.data_ptr(),
                 le.data_ptr() if return_energy else None, thr.data_ptr() if return_energy else None, s))
             assert got == total
         return (labels, le, thr) if return_energy else labels
+
+    def _audio_args(self, ranges, lead, silence, normalize):
+        first, length, ld = _trial_arrays(ranges, lead)
+        sil = None
+        if silence is not None:
+            sil = np.ascontiguousarray(np.asarray(silence).astype(bool).astype(np.uint8).reshape(-1))
+            if len(sil) != len(first):
+                raise ValueError("silence must hold one flag per trial")
+        norm = self._normalize_flags(normalize, sil, len(first))
+        if np.any(length < 0):
+            raise _lib.DssError("negative trial length")
+        offsets = np.concatenate([[0], np.cumsum(length.astype(np.int64))])
+        return first, length, ld, norm, offsets
+
+    def prepared_audio_trials(self, audio: np.ndarray, ranges, lead=0, normalize=None, return_peaks: bool = False,
+                              silence: Optional[Sequence[bool]] = None):
+        """The trials' audio as the reference prepares it before anything reads it (prepare_corpus.py:63-69): int16
+        (sum length_i,), trial i at ``sum(length[:i])``: ``lead`` zeros, then the first ``length - lead`` samples of the cut
+        ``audio[first : first + length]``, of a trial flagged by ``normalize`` scaled by the factor of the cut's peak and by the
+        post gain (two roundings, as pydub's two ``audioop.mul``).  ``normalize`` as in ``labels_trials``; ``True`` leaves the
+        trials flagged in ``silence`` as they are.  A trial may be shorter than one window.  With ``return_peaks`` also the
+        int32 peak of every trial's cut."""
+        a = np.asarray(audio)
+        if a.dtype != np.int16 or a.ndim != 1:
+            raise ValueError("audio must be a one-dimensional int16 array")
+        a = np.ascontiguousarray(a)
+        first, length, ld, norm, offsets = self._audio_args(ranges, lead, silence, normalize)
+        out = np.zeros(int(offsets[-1]), dtype=np.int16)
+        peaks = np.zeros(len(first), dtype=np.int32)
+        if len(first):
+            _lib.check(self._L.dss_avad_prepare_trials(
+                self._h, a.ctypes.data, len(a), len(first), first.ctypes.data, length.ctypes.data, ld.ctypes.data, None,
+                norm.ctypes.data if norm is not None else None, None, None, None, out.ctypes.data,
+                peaks.ctypes.data if return_peaks else None))
+        return (out, peaks) if return_peaks else out
+
+    def prepared_audio_trials_torch(self, audio, ranges, lead=0, normalize=None, return_peaks: bool = False,
+                                    silence: Optional[Sequence[bool]] = None, stream=None):
+        """Device-resident form of ``prepared_audio_trials``: CUDA int16 (n,) -> CUDA int16 (sum length_i,) (and CUDA int32
+        peaks); queued on the current (or the given) stream, no synchronisation."""
+        import torch
+        assert audio.is_cuda and audio.dtype == torch.int16 and audio.is_contiguous() and audio.dim() == 1
+        first, length, ld, norm, offsets = self._audio_args(ranges, lead, silence, normalize)
+        dev = audio.device
+        out = torch.empty(int(offsets[-1]), dtype=torch.int16, device=dev)
+        peaks = torch.empty(len(first), dtype=torch.int32, device=dev) if return_peaks else None
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        if len(first):
+            _lib.check(self._L.dss_avad_prepare_trials_dev(
+                self._h, audio.data_ptr(), audio.shape[0], len(first), first.ctypes.data, length.ctypes.data, ld.ctypes.data, None,
+                norm.ctypes.data if norm is not None else None, None, None, None, out.data_ptr(),
+                peaks.data_ptr() if return_peaks else None, s))
+        return (out, peaks) if return_peaks else out

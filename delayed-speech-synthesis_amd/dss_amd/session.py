@@ -14,9 +14,10 @@ and with them the statistics, are bit-identical to the reference chain.  Parsing
 
   * ``prepare_corpus.py:78-137,202-234``: the corpus file of a recording -- ``hga_activity`` (the z-scored frames),
     ``vad_labels`` (an ``EnergyBasedVad`` per trial on the session's wav) and ``trial_ids``: ``session_corpus`` below, with
-    the labels of all trials in one pass over the audio (``AcousticVadGPU.labels_trials``).  Two things of that script
-    stay outside: the per-trial loudness normalisation through pydub (the audio is labelled as it is handed over), and
-    ``lpc_coefficients``, which need xiph's LPCNet feature encoder.
+    the labels of all trials in one pass over the audio (``AcousticVadGPU.labels_trials``).  The per-trial loudness
+    normalisation through pydub is opt-in (``normalize_audio=True``; by default the audio is labelled as it is handed over);
+    its arithmetic is pinned by tests/golden/trial_audio.npz.  ``lpc_coefficients`` stay outside: they need xiph's LPCNet
+    feature encoder.  The array that encoder is given per trial is ``session_trial_audio``.
 """
 from __future__ import annotations
 
@@ -108,11 +109,14 @@ def trial_audio_ranges(trials, fs: int = 1000, fs_audio: int = 16000, n_audio: O
 
 
 def session_vad_labels(wav: np.ndarray, trials, stimulus_labels, fs: int = 1000, fs_audio: int = 16000,
-                       shift_seconds: float = 0.016, vad: Optional[acoustic_vad.AcousticVadGPU] = None) -> np.ndarray:
+                       shift_seconds: float = 0.016, vad: Optional[acoustic_vad.AcousticVadGPU] = None,
+                       normalize: bool = False) -> np.ndarray:
     """np.concatenate of every trial's EnergyBasedVad labels (prepare_corpus.get_vad_labels): bool (sum W_i,).  ``wav`` is the
-    session's int16 audio AS IT IS: the reference's per-trial pydub loudness normalisation is not applied (normalise the audio
-    yourself first if your corpus needs it).  Every trial is shifted by ``shift_seconds`` (zeros in front, the tail dropped,
-    prepare_corpus.py:91-93); trials whose stimulus label is "SILENCE" get all-zero labels (prepare_corpus.py:99-100)."""
+    session's int16 audio.  By default it is labelled AS IT IS; with ``normalize`` every trial whose stimulus label is not
+    "SILENCE" is first brought to the reference's loudness (prepare_corpus.py:88-89: pydub's normalize and -3 dB, on the
+    device; ``AcousticVadGPU.set_gain``'s defaults unless ``vad`` was given other data).  Every trial is shifted by
+    ``shift_seconds`` (zeros in front, the tail dropped, prepare_corpus.py:91-93); trials whose stimulus label is "SILENCE" get
+    all-zero labels (prepare_corpus.py:99-100)."""
     wav = np.asarray(wav)
     ranges = trial_audio_ranges(trials, fs, fs_audio, len(wav))
     silence = [label == "SILENCE" for label in stimulus_labels]
@@ -121,10 +125,36 @@ def session_vad_labels(wav: np.ndarray, trials, stimulus_labels, fs: int = 1000,
     own = vad is None
     v = acoustic_vad.AcousticVadGPU(fs=fs_audio) if own else vad
     try:
-        return v.labels_trials(wav, ranges, lead=int(shift_seconds * fs_audio), silence=silence)
+        return v.labels_trials(wav, ranges, lead=int(shift_seconds * fs_audio), silence=silence,
+                               normalize=True if normalize else None)
     finally:
         if own:
             v.close()
+
+
+def session_trial_audio(wav: np.ndarray, trials, stimulus_labels, fs: int = 1000, fs_audio: int = 16000,
+                        shift_seconds: float = 0.016, norm_db: float = -3.0,
+                        vad: Optional[acoustic_vad.AcousticVadGPU] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """Per trial exactly the array prepare_corpus.py:73 hands ``LPCFeatureEncoder.compute_LPC_features``
+    (prepare_corpus.py:58-69): the cut, normalised through pydub's two gains unless the stimulus is "SILENCE", shifted by
+    ``shift_seconds``.  Returns ``(int16 concatenation, offsets)``: trial i is ``audio[offsets[i] : offsets[i + 1]]``.  A trial
+    may be shorter than a VAD window here.  ``norm_db`` is get_lpc_coefficients' ``norm``.  A ``vad`` handed in is left with
+    pydub's table and that post gain set (``AcousticVadGPU.set_gain``)."""
+    from . import trial_audio
+    wav = np.asarray(wav)
+    ranges = trial_audio_ranges(trials, fs, fs_audio, len(wav))
+    silence = [label == "SILENCE" for label in stimulus_labels]
+    if len(silence) != len(ranges):
+        raise ValueError("one stimulus label per trial")
+    own = vad is None
+    v = acoustic_vad.AcousticVadGPU(fs=fs_audio) if own else vad
+    try:
+        v.set_gain(post=trial_audio.post_gain(norm_db))
+        out = v.prepared_audio_trials(wav, ranges, lead=int(shift_seconds * fs_audio), normalize=True, silence=silence)
+    finally:
+        if own:
+            v.close()
+    return out, np.concatenate([[0], np.cumsum([n for _, n in ranges], dtype=np.int64)]).astype(np.int64)
 
 
 def trial_ids(trials, stimulus_labels, stimuli, fs: int = 1000) -> np.ndarray:
@@ -148,14 +178,16 @@ def trial_ids(trials, stimulus_labels, stimuli, fs: int = 1000) -> np.ndarray:
 
 def session_corpus(recording: np.ndarray, wav: np.ndarray, trials, stimulus_labels, stimuli, normalization: np.ndarray,
                    fs: int = 1000, fs_audio: int = 16000, bad_channels: Optional[Sequence[int]] = None,
-                   contaminated_channels: Optional[Sequence[int]] = None, shift_seconds: float = 0.016) -> dict:
+                   contaminated_channels: Optional[Sequence[int]] = None, shift_seconds: float = 0.016,
+                   normalize_audio: bool = False) -> dict:
     """Three of the four arrays prepare_corpus.main stores per recording (prepare_corpus.py:218-234), ready for the user's own
     ``save_data_to_hdf``: ``hga_activity`` = (session_features - mean) / std with ``normalization`` = vstack([mean, std]) of the
     day, ``vad_labels`` (bool), ``trial_ids`` (int16).  Raises ValueError when a trial's frame count differs between the
     features and the labels (a trial clamped at the end of the wav, a sampling-rate ratio that truncates): the reference
     would write misaligned arrays.  ``lpc_coefficients`` is not a key: it needs xiph's LPCNet feature encoder, which this
-    package does not have (its five symbols fail cleanly).  The wav is labelled as it is handed over (no pydub loudness
-    normalisation)."""
+    package does not have (its five symbols fail cleanly).  By default the wav is labelled as it is handed over; with
+    ``normalize_audio`` every non-SILENCE trial gets the reference's pydub loudness normalisation first (on the device), which
+    is what prepare_corpus.get_vad_labels labels."""
     trials = [(int(a), int(b)) for a, b in trials]
     stats = np.asarray(normalization, dtype=np.float64)
     if stats.ndim != 2 or stats.shape[0] != 2:
@@ -167,7 +199,10 @@ def session_corpus(recording: np.ndarray, wav: np.ndarray, trials, stimulus_labe
         if w_hga != w_vad:
             raise ValueError(f"trial {k}: {w_hga} feature frames but {w_vad} label frames")
     feats = session_features(recording, trials, fs, bad_channels, contaminated_channels)
-    labels = session_vad_labels(wav, trials, stimulus_labels, fs, fs_audio, shift_seconds)
+    if normalize_audio:
+        labels = session_vad_labels(wav, trials, stimulus_labels, fs, fs_audio, shift_seconds, normalize=True)
+    else:
+        labels = session_vad_labels(wav, trials, stimulus_labels, fs, fs_audio, shift_seconds)
     ids = trial_ids(trials, stimulus_labels, stimuli, fs)
     if not (len(feats) == len(labels) == len(ids)):
         raise ValueError(f"misaligned corpus: {len(feats)} feature frames, {len(labels)} labels, {len(ids)} trial ids")

@@ -450,8 +450,9 @@ int dss_dec_forward_rows_dev(dss_dec *v, const void *d_frames, int frames_are_f6
  * the bands, 2 * sum; threshold = energy_threshold + energy_mean_scale * sum(log energy) / W (the mean term is skipped when
  * the scale is 0); frame i is voiced iff, over the frames t in [i - frames_context, i + frames_context) inside the trial,
  * (number with log energy > threshold) >= (number of frames) * proportion_threshold in float64.
- * Here a whole trial list runs in two launches (csrc/acoustic_vad.hip).  The audio is taken AS THE CALLER HANDS IT OVER: the
- * reference's per-trial loudness normalisation through pydub (prepare_corpus._normalize_audio) is not part of this library.
+ * Here a whole trial list runs in two launches (csrc/acoustic_vad.hip).  The audio is taken AS THE CALLER HANDS IT OVER by
+ * dss_avad_labels_trials*: the reference's per-trial loudness normalisation through pydub (prepare_corpus._normalize_audio) is
+ * opt-in, through dss_avad_set_gain and dss_avad_prepare_trials* at the end of this part.
  * Trial i is `lead[i]` zero samples followed by audio[first[i] .. first[i] + len[i] - lead[i]): len[i] samples in all, which
  * is the reference's 16 ms shift (prepare_corpus.py:91-93) with lead = 256.  Ranges may overlap.  A trial shorter than one
  * window has no frame (the reference divides by zero there) and is refused.  silence[i] != 0 gives the trial all-zero labels
@@ -494,6 +495,42 @@ int dss_avad_labels_trials_dev(dss_avad *h, const int16_t *d_audio, long long n_
  * reference's; the sum behind the mean is taken in the device kernel's order (256 strided running sums, then a halving
  * tree), not numpy's pairwise one.  labels: W bytes; threshold may be NULL. */
 int dss_avad_vote_host(const double *log_energy, int W, const dss_avad_params *p, unsigned char *labels, double *threshold);
+/* Opt-in: the trial's audio as prepare_corpus.py prepares it (prepare_corpus.py:33-40, 58-69, 84-93), which the entry points
+ * above leave out.  Every trial whose stimulus is not SILENCE goes through pydub there: effects.normalize, then apply_gain(-3),
+ * each one audioop.mul over the int16 samples.  Here, for a trial with normalize[i] != 0:
+ *   peak      = max |x| over the cut audio[first .. first + len) (where the audio ends before that, over what is there), 0 ..
+ *               32768 (-32768 counts as 32768); the last `lead` samples count although the shift drops them;
+ *   scale(x, f) = (int16) floor(v), v = (double) x * f, v > 32767 -> 32767, v < -32767 -> -32768 (audioop's fbound);
+ *   prepared  = scale(scale(x, gain_by_peak[peak]), post_gain): two roundings, never one folded product;
+ * and the prepared trial is `lead` zeros followed by the first len - lead prepared samples.  A trial with normalize[i] == 0 (a
+ * SILENCE trial) keeps its samples.  gain_by_peak is DATA: the library evaluates no log and no pow (dss_amd.trial_audio
+ * computes pydub's table).  Labels, log energies and thresholds of a normalised call are, bit for bit, those of the plain call
+ * on the prepared audio. */
+/* The two functions the kernels share with the host (csrc/avad_gain.h); no device needed.  Peak of n samples; DSS_EINVAL for
+ * a NULL array. */
+int dss_avad_peak_host(const int16_t *x, long long n);
+/* out[i] = scale(x[i], factor); a non-finite factor is refused. */
+int dss_avad_scale_host(const int16_t *x, long long n, double factor, int16_t *out);
+/* Samples one workgroup of the peak kernel takes (a trial's tiles are joined by an integer atomic max). */
+int dss_avad_peak_tile(void);
+/* Uploads gain_by_peak[32769] (index = peak) and the post gain into the handle, once; both stay until set again.  Refuses a
+ * negative or non-finite entry (before it looks at the handle: the refusals need no device).  Waits for the handle's device. */
+int dss_avad_set_gain(dss_avad *h, const double *gain_by_peak, double post_gain);
+/* The arguments of dss_avad_labels_trials plus: normalize (n_trials bytes, NULL = no trial), prepared (int16[sum len]: the
+ * prepared trials, leading zeros included, trial i from sum(len[:i]) on; may be NULL), peaks (int32[n_trials], the peak of
+ * EVERY trial, normalised or not; may be NULL).  labels may be NULL as well -- then log_energy and threshold must be, the energy
+ * and vote launches are skipped, a trial shorter than one window is allowed, and 0 is returned.  At least one output must be
+ * asked for.  A call that normalises a trial before dss_avad_set_gain fails with the reason in dss_last_error().  Launches:
+ * peak, energy, vote, and a fourth for `prepared`. */
+int dss_avad_prepare_trials(dss_avad *h, const int16_t *audio, long long n_audio, int n_trials, const long long *first,
+                            const int *len, const int *lead, const unsigned char *silence, const unsigned char *normalize,
+                            unsigned char *labels, double *log_energy, double *threshold, int16_t *prepared, int *peaks);
+/* Device-resident form: d_audio and the five outputs are device pointers, the lists HOST arrays; nothing waits for the device
+ * between the launches; one call per handle may be in flight. */
+int dss_avad_prepare_trials_dev(dss_avad *h, const int16_t *d_audio, long long n_audio, int n_trials, const long long *first,
+                                const int *len, const int *lead, const unsigned char *silence, const unsigned char *normalize,
+                                unsigned char *d_labels, double *d_log_energy, double *d_threshold, int16_t *d_prepared,
+                                int *d_peaks, void *hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Part 8 -- the two recurrent models over the trials of a corpus, and their validation scores.  A corpus is concatenated
