@@ -31,6 +31,7 @@
 #define DSS_HCX 32            // ... in the instantiation with the extended paths (8 VGPRs)
 #define DSS_HX 32             // max h-gate blocks per row group beyond DSS_HCX (column ids from LDS)
 #define DSS_HBLK_BYTES 151552  // dynamic LDS left after the kernel's static 11.9 KB (160 KB per CU)
+#define DSS_TANSIG_Y 208       // distance (floats) between the two halves of the activation table pair (lpcnet_device.h)
 
 void dss_set_error(const char *fmt, ...);
 
@@ -66,7 +67,7 @@ struct DssModelDev {
     const float *gru_b_w_rec;                               // [16][48]
     const float *fc_bias, *fc_w, *fc_factor;                // [512], [256][2][16], [512]
     // derived tables (host libm, see dss_capi.cpp)
-    const float *tansig;          // [201]
+    const float *tansig;          // [201] y = tanh(.04 i) as tansig_table.h rounds it; [DSS_TANSIG_Y + i]: 1 - y*y (see lpcnet_device.h)
     const float *logit_table;     // [256]
     const float *ulaw2lin;        // [256]
     const float *dct_table;       // [18*18]
@@ -151,6 +152,7 @@ int dss_launch_sample_network_generic(const DssModelDev &m, DssBatchDev &b, int 
                                       int trace, hipStream_t s, int *frames_done = nullptr);
 int dss_launch_exp10_selftest(const float *d_x, const float *d_comp, float *d_out, long n, hipStream_t s);
 int dss_launch_lin2ulaw_selftest(unsigned start, unsigned stride, long n, unsigned char *d_out, hipStream_t s);
+int dss_launch_tansig_selftest(const float *d_tab, int which, unsigned start, unsigned long long n, unsigned long long *d_res, hipStream_t s);
 int dss_launch_lpcnet_reset(const DssModelDev &m, DssBatchDev &b, int utt, hipStream_t s);
 
 // ---- speech-segment gate (speech_gate.hip) ---------------------------------------------------------------

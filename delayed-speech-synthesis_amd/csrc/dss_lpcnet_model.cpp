@@ -51,6 +51,18 @@ static float host_ulaw2lin(float u)           // xiph common.h
     return s * scale_1 * (exp(u / 128. * 5.5451774445f) - 1);
 }
 
+// The activation table and, DSS_TANSIG_Y floats behind it, the 1 - y*y that vec.h tanh_approx forms from the entry it
+// reads: two separately rounded fp32 operations.  The square goes through a volatile float, so that no compiler setting
+// (contraction, excess precision) can fuse it into the subtraction or keep it wider than fp32.
+static void dss_tansig_tables(float *t)
+{
+    for (int i = 0; i < 201; ++i) {
+        t[i] = (float)(floor(tanh(.04 * i) * 1e6 + .5) / 1e6);                                       // tansig_table.h
+        volatile float yy = t[i] * t[i];
+        t[DSS_TANSIG_Y + i] = 1.f - yy;
+    }
+}
+
 struct BlobView {
     const float *embed_pitch, *conv1_w, *conv1_b, *conv2_w, *conv2_b, *dense1_w, *dense1_b, *dense2_w, *dense2_b;
     const float *gru_a_dense_w, *gru_a_dense_b, *gru_b_dense_w, *gru_b_dense_b, *embed_sig, *embed_pred, *embed_exc;
@@ -482,10 +494,10 @@ static int upload_model(HostModel *hm, int device, DssModelDev &m)
     }
     // ---- derived tables (host libm, exactly as xiph builds them at run time) ---------------------------
     {
-        float tansig[201], logit[256], u2l[256], dct[18 * 18], costab[320], ia[160], ib[160];
+        float tansig[DSS_TANSIG_Y + 201] = {0}, logit[256], u2l[256], dct[18 * 18], costab[320], ia[160], ib[160];
         int iband[160];
         double lagw[17];
-        for (int i = 0; i < 201; ++i) tansig[i] = (float)(floor(tanh(.04 * i) * 1e6 + .5) / 1e6);   // tansig_table.h
+        dss_tansig_tables(tansig);
         for (int i = 0; i < 256; ++i) {                                                              // lpcnet_init()
             float prob = .025 + .95 * i / 255.;
             logit[i] = -log((1 - prob) / prob);
@@ -509,7 +521,7 @@ static int upload_model(HostModel *hm, int device, DssModelDev &m)
         }
         for (int i = 0; i < 17; ++i) lagw[i] = (1 - 6e-5 * i * i);
         float *d; int *di; double *dd;
-        rc = mem.upload<float>(tansig, 201, &d); if (rc) return rc; m.tansig = d;
+        rc = mem.upload<float>(tansig, DSS_TANSIG_Y + 201, &d); if (rc) return rc; m.tansig = d;
         rc = mem.upload<float>(logit, 256, &d); if (rc) return rc; m.logit_table = d;
         rc = mem.upload<float>(u2l, 256, &d); if (rc) return rc; m.ulaw2lin = d;
         rc = mem.upload<float>(dct, 324, &d); if (rc) return rc; m.dct_table = d;
@@ -589,6 +601,34 @@ extern "C" int dss_lpcnet_model_info(int *fast_path, int *zr_slots_max, int *h_s
     if (gru_a_order) *gru_a_order = hm->h.gru_a_order;
     release_model(hm);
     return DSS_OK;
+}
+
+// Host-only: the activation table pair exactly as load_model uploads it, out[0..201) = y, out[DSS_TANSIG_Y .. +201) = 1 - y*y
+// (tests/test_cpu_tansig_pairs.py compares the second half with numpy's two fp32 operations).
+extern "C" int dss_selftest_tansig_table(float *out, int n)
+{
+    if (!out || n != DSS_TANSIG_Y + 201) { dss_set_error("dss_selftest_tansig_table: out must hold %d floats", DSS_TANSIG_Y + 201); return DSS_EINVAL; }
+    memset(out, 0, sizeof(float) * (size_t)n);
+    dss_tansig_tables(out);
+    return DSS_OK;
+}
+
+extern "C" int dss_selftest_tansig(int which, unsigned start_bits, unsigned long long n, unsigned long long *res)
+{
+    if (!res || which < 0 || which > 2 || n == 0 || n > (1ull << 32)) { dss_set_error("dss_selftest_tansig: bad arguments"); return DSS_EINVAL; }
+    int rc = dss_ensure_device();
+    if (rc) return rc;
+    float tab[DSS_TANSIG_Y + 201] = {0};
+    dss_tansig_tables(tab);
+    const unsigned long long init[2] = {0, ~0ull};
+    DssDevBlocks mem;
+    float *dtab = nullptr;
+    unsigned long long *dres = nullptr;
+    rc = mem.upload<float>(tab, DSS_TANSIG_Y + 201, &dtab) | mem.upload<unsigned long long>(init, 2, &dres);
+    if (!rc) rc = dss_launch_tansig_selftest(dtab, which, start_bits, n, dres, 0);
+    if (!rc && hipMemcpy(res, dres, sizeof(init), hipMemcpyDeviceToHost) != hipSuccess) rc = DSS_ENODEV;
+    mem.free_all();
+    return rc;
 }
 
 // Host-only check of build_fast_layout(): walks every lane's z, r and h lists through the arrays exactly as the kernel

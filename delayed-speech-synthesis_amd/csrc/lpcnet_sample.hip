@@ -116,6 +116,13 @@
                                   //   Later (profiles/wave7_dtob_experiment.md), once wave 7 no longer waits for the threshold table between D and B:
                                   //   D..B  wave 3 at 3, level with wave 7 on its SIMD;  B..C  wave 6 at 0 from its last hand-over on (speculation
                                   //         and thresholds are needed at barrier C only; its SIMD neighbour, wave 2, ends its h chain 150 cycles before C).
+#ifndef DSS_ACT_SHORT
+#define DSS_ACT_SHORT 7           // sites that take the short table activations of lpcnet_device.h (same bits, 10 dependent instructions per
+#endif                            //   round instead of 17):  1 GRU A z/r, 2 GRU A h, 4 GRU B gates (wave 7), 8 dual-FC.  Never in the extended
+                                  //   instantiation, whose second state buffer is in use.  Same-box A/B, 256 x 1 s, parent 37.10 ms
+                                  //   (profiles/activation_experiment.md): 1 alone 37.44, 2 alone 37.32, 1 + 2 36.70, 4 alone 36.90, 1 + 2 + 4 36.58;
+                                  //   8 LOSES wherever it is added (alone 37.63, 4 + 8 37.35, 1 + 2 + 8 36.98, all four 36.63): the dual-FC keeps
+                                  //   the plain form.
 #ifndef GB4H
 #define GB4H 32
 #endif
@@ -148,6 +155,13 @@ struct SampleLds {
     int idx[4];                           // last_sig_ulaw, pred_ulaw, last_exc
     short pcm[DSS_FRAME_SIZE];
 };
+
+// The 1 - y*y table of the short activations (lpcnet_device.h) lives in the second GRU A state buffer, which only the
+// extended paths use: they keep the plain activations.  (SampleLds has 160 bytes to spare, the table takes 804.)
+static_assert(NA >= 201, "the dy table must leave the zero column of the second state buffer alone");
+static_assert(offsetof(SampleLds, tansig) - offsetof(SampleLds, state_a) - (NA + 4) * sizeof(float) > 255 * sizeof(float),
+              "y and dy tables more than 255 words apart: two reads with immediate offsets, not a ds_read2_b32 behind a v_add");
+__device__ __forceinline__ float *dss_tansig_dy(SampleLds &L) { return L.state_a[1]; }
 
 // Products of a relay segment formed ahead of its sums.  Resident weights: N inputs (multiple of 16) starting at AN, weights
 // WB[WOFF..] (pairs), into PQ[0 .. N/4); the state values are read one group of 16 inputs ahead.
@@ -343,6 +357,7 @@ __device__ __forceinline__ void dss_role_a(SampleLds &L, float *hblk_lds, const 
     const float u2l_c = L.ulaw2lin[(HAS_FC ? 128 + tid : tid - 64 * DSS_SPEC_WAVE + 64) & 255];   // this lane's excitation candidate (waves 0, 1, DSS_SPEC_WAVE)
     const int level = 31 - __clz(tid | 1);                       // FC node = (1 << level) | prefix
     const bool recur_first = m.h.gru_a_order == DSS_GRUA_RECUR_FIRST;     // wave-uniform (kernel argument)
+    const float *dtab = dss_tansig_dy(L);
     int cur = 0, seq = 0;
     float st = L.state_a[0][unit];
     unsigned sa[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, ta = 0;   // diagnostic build only ([8]: barrier D .. the first embedding load is about to go out)
@@ -440,10 +455,14 @@ __device__ __forceinline__ void dss_role_a(SampleLds &L, float *hblk_lds, const 
                 if (recur_first) { az = gz + az; ar = gr + ar; }
                 if (STAMP) { asm volatile("" :: "v"(az), "v"(ar)); const unsigned t = DSS_NOW(); sa[2] += t - ta; ta = t; }
                 float z, r;
-                dss_sigmoid_approx2(L.tansig, az, ar, z, r);
+                if constexpr ((DSS_ACT_SHORT & 1) && !EXT) dss_sigmoid_short2(L.tansig, dtab, az, ar, z, r);
+                else dss_sigmoid_approx2(L.tansig, az, ar, z, r);
                 float h = ahv * r + gh;
-                h = dss_tanh_approx(L.tansig, h);
-                st = z * st + (1 - z) * h;
+                if constexpr ((DSS_ACT_SHORT & 2) && !EXT) st = z * st + dss_tanh_times(L.tansig, dtab, 1 - z, h);   // (1 - z) * tanh(h)
+                else {
+                    h = dss_tanh_approx(L.tansig, h);
+                    st = z * st + (1 - z) * h;
+                }
                 L.state_a[DSS_NEW(cur)][unit] = st;
                 if (STAMP) { asm volatile("" :: "v"(st)); const unsigned t = DSS_NOW(); sa[3] += t - ta; ta = t; }
             }
@@ -498,10 +517,14 @@ __device__ __forceinline__ void dss_role_a(SampleLds &L, float *hblk_lds, const 
                     s12 += q3;
                 }
                 float s1 = s12.x, s2 = s12.y;
-                float t1, t2;
-                dss_tanh_approx2(L.tansig, s1, s2, t1, t2);
-                s1 = ff0 * t1;
-                s2 = ff1 * t2;
+                if constexpr ((DSS_ACT_SHORT & 8) && !EXT) {
+                    dss_tanh_times2(L.tansig, dtab, ff0, s1, ff1, s2, s1, s2);
+                } else {
+                    float t1, t2;
+                    dss_tanh_approx2(L.tansig, s1, s2, t1, t2);
+                    s1 = ff0 * t1;
+                    s2 = ff1 * t2;
+                }
                 s1 += s2;
                 bool bit = thr_lv < s1;
                 if constexpr (TRACE) {               // teacher forcing (tests): record every logit, bend the walk
@@ -560,7 +583,10 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
     for (int k = tid * 4; k < m.hblk_floats; k += 512 * 4)
         *reinterpret_cast<f32x4 *>(&hblk_lds[k]) = *reinterpret_cast<const f32x4 *>(&m.hblk[k]);
     for (int k = tid; k < NB * NB3; k += 512) L.gb_wrec[k] = m.gru_b_w_rec[k];
-    if (tid < 201) L.tansig[tid] = m.tansig[tid];
+    if (tid < 201) {
+        L.tansig[tid] = m.tansig[tid];
+        if (DSS_ACT_SHORT && !EXT) dss_tansig_dy(L)[tid] = m.tansig[DSS_TANSIG_Y + tid];     // 1 - y*y, formed by the host
+    }
     if (tid < 256) L.ulaw2lin[tid] = m.ulaw2lin[tid];
     if (tid < NA) L.state_a[0][tid] = b.gru_a_state[(size_t)slot * NA + tid];
     if (tid < 8) L.state_a[tid >> 2][NA + (tid & 3)] = 0.f;
@@ -784,14 +810,16 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
                     // row/half swaps (VALU) instead of ds_bpermute (an LDS round trip each, on the sample's critical
                     // path); the new state is formed in the h lanes.  Only the first result of a swap is used, with
                     // distinct operands: the second one came back wrong from this compiler.
-                    const float zr = dss_sigmoid_approx(L.tansig, acc + rec);
+                    const float zr = ((DSS_ACT_SHORT & 4) && !EXT) ? dss_sigmoid_short(L.tansig, dss_tansig_dy(L), acc + rec) : dss_sigmoid_approx(L.tansig, acc + rec);
                     const unsigned zb = __builtin_bit_cast(unsigned, zr);
                     const unsigned r_row0 = __builtin_amdgcn_permlane16_swap(zb, 0u, false, false)[1];                  // lanes 0..15 <- 16..31
                     const float r_for_h = __builtin_bit_cast(float, __builtin_amdgcn_permlane32_swap(0u, r_row0, false, false)[0]);  // 32..47 <- 0..15
                     const float z_for_h = __builtin_bit_cast(float, __builtin_amdgcn_permlane32_swap(0u, zb, false, false)[0]);      // 32..47 <- 0..15
                     float hh = acc + rec * r_for_h;
-                    hh = dss_tanh_approx(L.tansig, hh);
-                    if (lane >= 2 * NB && lane < NB3) L.state_b[lane - 2 * NB] = z_for_h * sb_old + (1 - z_for_h) * hh;
+                    float upd;
+                    if constexpr ((DSS_ACT_SHORT & 4) && !EXT) upd = dss_tanh_times(L.tansig, dss_tansig_dy(L), 1 - z_for_h, hh);
+                    else upd = (1 - z_for_h) * dss_tanh_approx(L.tansig, hh);
+                    if (lane >= 2 * NB && lane < NB3) L.state_b[lane - 2 * NB] = z_for_h * sb_old + upd;
                 }
 #if DSS_RELAY_MASK
                 }
@@ -839,6 +867,54 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
             b.last_exc[slot] = last_exc;                     // (the generator's state: wave 6)
         }
     }
+}
+
+// ---- self-test of the short table activations (lpcnet_device.h) against the forms they replace, tables in LDS as in the
+// kernel above.  Pattern k < n is the fp32 x with bits start + k (wrapping).  which 0: tanh (sign folded into a factor 1),
+// 1: sigmoid, 2: the two-operand fold a * tanh(x) with a drawn from a hash of k (every exponent, subnormals, +-0).
+// res[0] counts the patterns whose results differ in any bit (two NaNs count as equal), res[1] is the smallest such k.
+__global__ void __launch_bounds__(256)
+tansig_selftest_kernel(const float *__restrict__ tab, int which, unsigned start, unsigned long long n, unsigned long long *res)
+{
+    __shared__ float T[2 * DSS_TANSIG_Y];                     // [0, 208) dy, [208, 416) y
+    for (int k = threadIdx.x; k < 2 * DSS_TANSIG_Y; k += blockDim.x) T[k] = 0.f;
+    __syncthreads();
+    if (threadIdx.x < 201) { T[DSS_TANSIG_Y + threadIdx.x] = tab[threadIdx.x]; T[threadIdx.x] = tab[DSS_TANSIG_Y + threadIdx.x]; }
+    __syncthreads();
+    const float *y_tab = T + DSS_TANSIG_Y, *dtab = T;
+    unsigned long long bad = 0, first = ~0ull;
+    for (unsigned long long k = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (unsigned long long)gridDim.x * blockDim.x) {
+        const float x = __uint_as_float(start + (unsigned)k);
+        float a = 1.f;
+        if (which == 2) {
+            unsigned hsh = (unsigned)k * 2654435761u + 0x9e3779b9u;
+            hsh ^= hsh >> 15; hsh *= 2246822519u; hsh ^= hsh >> 13;
+            if ((k & 15) == 0) hsh &= 0x807fffffu;            // a subnormal or a zero
+            if ((hsh & 0x7f800000u) == 0x7f800000u) hsh &= ~0x00800000u;      // finite factors only
+            a = __uint_as_float(hsh);
+        }
+        float want, got;
+        if (which == 1) { want = dss_sigmoid_approx(y_tab, x); got = dss_sigmoid_short(y_tab, dtab, x); }
+        else { want = a * dss_tanh_approx(y_tab, x); got = dss_tanh_times(y_tab, dtab, a, x); }
+        // the two-at-once forms: x in the first place, -x in the second (whose reference value is that of -x)
+        const float xm = -x;
+        float want2, got_a, got_b;
+        if (which == 1) { want2 = dss_sigmoid_approx(y_tab, xm); dss_sigmoid_short2(y_tab, dtab, x, xm, got_a, got_b); }
+        else { want2 = a * dss_tanh_approx(y_tab, xm); dss_tanh_times2(y_tab, dtab, a, x, a, xm, got_a, got_b); }
+        const bool same = (__float_as_uint(want) == __float_as_uint(got) || (want != want && got != got)) &&
+                          (__float_as_uint(want) == __float_as_uint(got_a) || (want != want && got_a != got_a)) &&
+                          (__float_as_uint(want2) == __float_as_uint(got_b) || (want2 != want2 && got_b != got_b));
+        if (!same) { ++bad; if (k < first) first = k; }
+    }
+    if (bad) { atomicAdd(&res[0], bad); atomicMin(&res[1], first); }
+}
+
+int dss_launch_tansig_selftest(const float *d_tab, int which, unsigned start, unsigned long long n, unsigned long long *d_res, hipStream_t s)
+{
+    const unsigned long long blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(tansig_selftest_kernel, dim3((unsigned)(blocks < 4096 ? (blocks ? blocks : 1) : 4096)), dim3(256), 0, s, d_tab, which, start, n, d_res);
+    DSS_HIP_CHECK(hipGetLastError());
+    return DSS_OK;
 }
 
 // Number of CUs of the current device, asked once per device (the eager streaming tick launches this kernel every 40 ms).

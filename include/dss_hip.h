@@ -223,6 +223,14 @@ int dss_selftest_exp10(const float *x, const float *comp, float *out, long n);
 /* Self-test of the device's lin2ulaw (xiph common.h; evaluated in a shorter instruction sequence):
  * out[i] = lin2ulaw(x) for the fp32 x whose bit pattern is start_bits + i * stride (wrapping), i < n (host buffer). */
 int dss_selftest_lin2ulaw(unsigned start_bits, unsigned stride, long n, unsigned char *out);
+/* Self-test of the short table activations of the CU-resident sample kernel (csrc/lpcnet_device.h) against the forms they
+ * replace, on the device: pattern k < n (n <= 2^32) is the fp32 x with bits start_bits + k (wrapping).  which 0: tanh,
+ * 1: sigmoid, 2: a * tanh(x) with the sign folded into a pseudo-random factor a.  res[0] = number of patterns whose two
+ * results differ in any bit (two NaNs are equal), res[1] = the smallest such k (all ones when there is none). */
+int dss_selftest_tansig(int which, unsigned start_bits, unsigned long long n, unsigned long long *res);
+/* Host-only (no GPU): the activation tables a loaded model carries, out[0..201) = y, out[208..409) = 1 - y*y as two
+ * separately rounded fp32 operations; n must be 409. */
+int dss_selftest_tansig_table(float *out, int n);
 /* Host-only (no GPU): lays the model out for the CU-resident sample kernel and walks every lane's z, r and h block lists
  * through that layout as the kernel indexes it.  info[8]: fast_path (0/1/2 as in dss_lpcnet_model_info), zr blocks max,
  * h blocks max, LDS bytes, register slots per gate on waves 4-5, tail blocks, mismatching rows, out-of-range reads. */
