@@ -9,7 +9,8 @@ vad_training_reference.py.
   one defect of the kind a kernel could have can be injected (``DEFECTS``); without a defect it agrees with autograd to rounding.
 * ``reference_loop``: the script's loop (train_bidirectional_model.py:134-152) on the float64 four-LSTM module with
   ``torch.optim.RMSprop`` and given masks.  ``rmsprop64`` is vad_training_reference's.
-* the inputs of the GPU tests (``GRAD_CASES``, ``case_inputs``, ``learning_problem``, ``LEARN``) and their bounds.
+* the inputs of the GPU tests (``GRAD_CASES``, ``case_inputs``, ``learning_problem``, ``LEARN``), their bounds, and the checker
+  that tests/test_gpu_decoder_training.py and tests/test_gpu_training_cases.py share (``check_trial``, ``loss_bound``).
 
 GRAD_BOUND -- per tensor, max|g - g_f64| / max|g_f64| -- is 4 x the worst error of torch float32 CPU autograd against
 ``autograd_trial`` over GRAD_CASES (every case with and without a mask), rounded up to one significant digit;
@@ -27,7 +28,10 @@ KEYS = tuple(f"lstm.{n}_l{layer}{rev}" for layer in (0, 1) for rev in ("", "_rev
 
 # torch float32 CPU autograd, worst tensor over the cases: 1.48e-6 (lstm.weight_hh_l0 at (100, 64, 37) x 4 with a mask; 1.0e-6 at
 # (100, 64, 2); 9.2e-7 at the 350-frame trial, which therefore needs no constant of its own);  x 4 = 5.9e-6 -> 6e-6.
-# The kernels on MI355X, worst tensor over the same cases: not measured (no run on an MI355X has been recorded).
+# The kernels on MI355X, worst tensor over the same cases: 1.97e-6 (at (100, 64, 37) x 4; 8.5e-7 or less at every case of scale 1).
+# The case table of tests/training_cases.py fits the same constant: torch float32 1.30e-6 at worst ((7, 5, 9) x 4 without a mask);
+# the kernels on MI355X 1.52e-6 in a gradient ((6, 5, 513) with 20 outputs), 7.7e-9 in the loss, 1.9e-7 in the features at scale 4
+# and 8.1e-8 at scale 1.
 GRAD_BOUND = 6e-6
 
 # (H, C, T, scale of the LSTM weights)
@@ -43,12 +47,19 @@ def _np64(sd):
     return {k: np.array(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float64) for k, v in sd.items()}
 
 
-def case_inputs(case, mask: str | None = "random"):
+def case_inputs(case, mask: str | None = "random", outputs: int | None = None):
     """The inputs of one gradient case: state_dict (float32 tensors, 20 outputs), x (T, C) float64 holding float32 values
     (N(0, 1) x 2), y (T, 20) float32 targets (N(0, 1)), mask (T, 2H) float32 multipliers of 0 / 2 or None.
-    mask: None, "random", or "zero_row" (random with row T // 2 all zero)."""
+    mask: None, "random", or "zero_row" (random with row T // 2 all zero).
+    outputs: None leaves the state_dict's own 20-output regressor; a count draws a regressor of that many outputs at torch's
+    default init of ``nn.Linear(2H, outputs)`` from a seed of the case's (tests/training_cases.py), and y is (T, outputs)."""
     H, C, T, scale = case
     sd = R.decoder_state_dict(H, C, scale)
+    if outputs is not None:
+        import torch
+        torch.manual_seed(300 + 7 * H + outputs)
+        head = torch.nn.Linear(2 * H, outputs)
+        sd["regressor.weight"], sd["regressor.bias"] = head.weight.detach().clone(), head.bias.detach().clone()
     x = R.frames("x2", 1, T, C, 7100 + 13 * T + H)[0]
     rng = np.random.default_rng(9100 + 17 * T + H + scale)
     y = rng.standard_normal((T, sd["regressor.weight"].shape[0])).astype(np.float32)
@@ -208,6 +219,42 @@ def rel_errors(got: dict, want: dict) -> dict:
         diff, ref = float(np.abs(np.asarray(got[k], np.float64) - want[k]).max()), float(np.abs(want[k]).max())
         out[k] = diff / ref if ref > 0 else (0.0 if diff == 0 else float("inf"))
     return out
+
+
+# ---- what the GPU tests hold a trial to ---------------------------------------------------------------------------------------
+
+def loss_bound(feat64, y, scale):
+    """loss = mean over the T x O elements of (f - y)^2.  With |f - f64| <= b = bound(scale) per element,
+    |(f - y)^2 - (f64 - y)^2| = |f - f64| |(f - y) + (f64 - y)| <= b (2 |f64 - y| + b), so
+    |loss - loss64| <= b (2 mean|f64 - y| + b): the loss's gradient in the features has L1 norm 2 mean|f64 - y|, the second term is
+    the curvature.  The kernel's own sum is float64 over float32 features and adds nothing at this size."""
+    b = R.bound(scale)
+    return b * (2.0 * float(np.mean(np.abs(feat64 - np.asarray(y, np.float64)))) + b)
+
+
+def check_trial(tr, sd, x, y, m, scale, f64_frames, what, want=None):
+    """One ``trial(step=False)`` of the trainer ``tr`` (a DecoderTrainerGPU that holds ``sd``) against ``autograd_trial`` (or
+    ``want``, its result): every gradient within GRAD_BOUND, the loss within ``loss_bound``, the features within
+    lstm_reference.bound(scale).  Prints the figures, then asserts; returns (gradient, loss, feature) errors."""
+    import torch
+    xs = torch.from_numpy(x if f64_frames else x.astype(np.float32))
+    loss = tr.trial(xs, y, mask=m, step=False)
+    return compare_trial(tr, loss, y, scale, what, want or autograd_trial(sd, x, y, m))
+
+
+def compare_trial(tr, loss, y, scale, what, want):
+    """The read-backs of the trainer's last trial and its loss against ``want`` = (loss, gradients, features) in float64."""
+    want_loss, want_g, want_f = want
+    err = rel_errors(tr.gradients(), want_g)
+    ef = float(np.abs(tr.features() - want_f).max())
+    lb = loss_bound(want_f, y, scale)
+    print(f"{what}: gradient {max(err.values()):.3g} ({max(err, key=err.get)}), loss {abs(loss - want_loss):.3g} (bound {lb:.3g}), "
+          f"features {ef:.3g}")
+    for k in KEYS:
+        assert err[k] <= GRAD_BOUND, (what, k, err[k])
+    assert abs(loss - want_loss) <= lb, (what, loss, want_loss)
+    assert ef <= R.bound(scale), (what, ef)
+    return max(err.values()), abs(loss - want_loss), ef
 
 
 # ---- the script's loop -----------------------------------------------------------------------------------------------------------

@@ -4,12 +4,13 @@ kernel's own read-back values; publish; determinism; the forward half against th
 
 Bounds: gradients D.GRAD_BOUND per tensor (max|g - g64| / max|g64|; 4 x torch float32 CPU autograd's own error, see the helper);
 features lstm_reference.bound(scale), the inference kernel's bound, which the forward half shares with its arithmetic; the loss
-from that bound (see ``_loss_bound``)."""
+from that bound (see ``D.loss_bound``)."""
 import numpy as np
 import pytest
 
 import lstm_reference as R
 import decoder_training_reference as D
+import training_cases as TC
 
 pytestmark = pytest.mark.gpu
 
@@ -20,30 +21,9 @@ def T():
     return training
 
 
-def _loss_bound(feat64, y, scale):
-    """loss = mean over the T x O elements of (f - y)^2.  With |f - f64| <= b = bound(scale) per element,
-    |(f - y)^2 - (f64 - y)^2| = |f - f64| |(f - y) + (f64 - y)| <= b (2 |f64 - y| + b), so
-    |loss - loss64| <= b (2 mean|f64 - y| + b): the loss's gradient in the features has L1 norm 2 mean|f64 - y|, the second term is
-    the curvature.  The kernel's own sum is float64 over float32 features and adds nothing at this size."""
-    b = R.bound(scale)
-    return b * (2.0 * float(np.mean(np.abs(feat64 - np.asarray(y, np.float64)))) + b)
-
-
-def _check_trial(tr, sd, x, y, m, scale, f64_frames, what, want=None):
-    import torch
-    xs = torch.from_numpy(x if f64_frames else x.astype(np.float32))
-    loss = tr.trial(xs, y, mask=m, step=False)
-    want_loss, want_g, want_f = want or D.autograd_trial(sd, x, y, m)
-    err = D.rel_errors(tr.gradients(), want_g)
-    ef = float(np.abs(tr.features() - want_f).max())
-    lb = _loss_bound(want_f, y, scale)
-    print(f"{what}: gradient {max(err.values()):.3g} ({max(err, key=err.get)}), loss {abs(loss - want_loss):.3g} (bound {lb:.3g}), "
-          f"features {ef:.3g}")
-    for k in D.KEYS:
-        assert err[k] <= D.GRAD_BOUND, (what, k, err[k])
-    assert abs(loss - want_loss) <= lb, (what, loss, want_loss)
-    assert ef <= R.bound(scale), (what, ef)
-    return max(err.values())
+def _check_trial(*args, **kw):
+    """The checker lives in the helper module (tests/test_gpu_training_cases.py runs it too); the worst gradient error."""
+    return D.check_trial(*args, **kw)[0]
 
 
 @pytest.mark.parametrize("case", D.GRAD_CASES, ids=str)
@@ -82,7 +62,7 @@ def _ulp32(v):
     return (np.nextafter(v, np.float32(np.inf)) - v).astype(np.float64)
 
 
-@pytest.mark.parametrize("case", (D.GRAD_CASES[6], D.GRAD_CASES[5]), ids=str)
+@pytest.mark.parametrize("case", (D.GRAD_CASES[6], D.GRAD_CASES[5]) + TC.RMSPROP_CASES, ids=str)
 def test_rmsprop_update_is_the_float64_formula(T, case):
     """Two consecutive steps (the first from sq = 0): p', sq' against the float64 formula on the read-back float32 p, sq and the
     kernel's own g, with the detector test's bounds (sq: 4 x 2^-24 relative; p: one ulp + 4 x 2^-24 |dp|); bias_ih / bias_hh: equal

@@ -10,6 +10,7 @@ import pytest
 
 import lstm_reference as R
 import vad_training_reference as V
+import training_cases as TC
 
 pytestmark = pytest.mark.gpu
 
@@ -20,21 +21,9 @@ def T():
     return training
 
 
-def _check_window(tr, sd, x, y, state, m, scale, f64_frames, what):
-    import torch
-    tr.set_state(*state)
-    xs = torch.from_numpy(x if f64_frames else x.astype(np.float32))
-    loss = tr.window(xs, y, mask=m, step=False)
-    want_loss, want, (wh, wc) = V.autograd_window(sd, x, y, state, m)
-    err = V.rel_errors(tr.gradients(), want)
-    h, c = tr.state()
-    eh, ec = np.abs(h - wh).max(), (np.abs(c - wc) / np.maximum(np.abs(wc), 1.0)).max()
-    print(f"{what}: gradient {max(err.values()):.3g} ({max(err, key=err.get)}), loss {abs(loss - want_loss):.3g}, h {eh:.3g}, c {ec:.3g}")
-    for k in V.KEYS:
-        assert err[k] <= V.GRAD_BOUND, (what, k, err[k])
-    assert abs(loss - want_loss) <= 2 * R.bound(scale), (what, loss, want_loss)
-    assert eh <= R.bound(scale) and ec <= R.C_REL, (what, eh, ec)
-    return max(err.values())
+def _check_window(*args, **kw):
+    """The checker lives in the helper module (tests/test_gpu_training_cases.py runs it too); the worst gradient error."""
+    return V.check_window(*args, **kw)[0]
 
 
 @pytest.mark.parametrize("case", V.GRAD_CASES, ids=str)
@@ -71,7 +60,7 @@ def _ulp32(v):
     return (np.nextafter(v, np.float32(np.inf)) - v).astype(np.float64)
 
 
-@pytest.mark.parametrize("case", (V.GRAD_CASES[0], V.GRAD_CASES[5]), ids=str)
+@pytest.mark.parametrize("case", (V.GRAD_CASES[0], V.GRAD_CASES[5]) + TC.RMSPROP_CASES, ids=str)
 def test_rmsprop_update_is_the_float64_formula(T, case):
     """Two consecutive steps (the first from sq = 0): p', sq' against the float64 formula on the read-back float32 p, sq and the
     kernel's own g; bias_ih / bias_hh: equal g, separate updates; step=False leaves p and sq bit-identical; publish: b0 = b_ih + b_hh."""
@@ -117,37 +106,7 @@ TRIALS = [(16, 8, 120), (16, 8, 101), (150, 64, 120), (150, 64, 101)]
 
 @pytest.mark.parametrize("H, C, n", TRIALS)
 def test_trial_in_one_call_is_its_windows_one_by_one(T, H, C, n):
-    sd = R.vad_state_dict(H, C, 1)
-    x = R.frames("x2", 1, n, C, 31 * n + H)[0]
-    rng = np.random.default_rng(n + H)
-    y = rng.integers(0, 2, n).astype(np.uint8)
-    masks = (rng.random((n, H)) >= 0.5).astype(np.float32) * np.float32(2.0)
-    lr = 1e-3
-    runs = []
-    for _ in range(2):                                     # the same trial twice from the same loaded state: the same bits
-        tr = T.VadTrainerGPU(sd, max_window=50)
-        tr.set_state(np.ones((2, H), np.float32), np.ones((2, H), np.float32))          # train_trial resets it
-        losses = tr.train_trial(x, y, window=50, masks=masks, lr=lr)
-        runs.append((losses, tr.state_dict(), tr.square_avg(), tr.state()))
-    assert len(runs[0][0]) == -(-n // 50)
-    tr = T.VadTrainerGPU(sd, max_window=50)
-    tr.set_state(np.ones((2, H), np.float32), np.ones((2, H), np.float32))
-    tr.reset_state()
-    seq = []
-    for a in range(0, n, 50):
-        cur, state = tr.state_dict(), tr.state()
-        seq.append(tr.window(x[a:a + 50], y[a:a + 50], mask=masks[a:a + 50], step=True, lr=lr))
-        _, want, _ = V.autograd_window(cur, x[a:a + 50], y[a:a + 50], state, masks[a:a + 50])
-        err = V.rel_errors(tr.gradients(), want)
-        print(f"H {H} trial {n} window at {a}: gradient error {max(err.values()):.3g}")
-        assert max(err.values()) <= V.GRAD_BOUND, (a, err)
-    seq = (np.array(seq), tr.state_dict(), tr.square_avg(), tr.state())
-    for other in (runs[1], seq):
-        assert np.array_equal(runs[0][0], other[0])
-        for k in V.KEYS:
-            assert np.array_equal(runs[0][1][k].numpy(), other[1][k].numpy()), k
-            assert np.array_equal(runs[0][2][k], other[2][k]), k
-        assert np.array_equal(runs[0][3][0], other[3][0]) and np.array_equal(runs[0][3][1], other[3][1])
+    V.check_trial_is_its_windows(T, H, C, n, window=50)   # (tests/test_gpu_training_cases.py runs it at other windows)
 
 
 def test_publish_then_validation_is_validation_of_the_state_dict(T):

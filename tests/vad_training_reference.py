@@ -8,7 +8,8 @@
 * ``rmsprop64``: the RMSprop formula in float64 from given p, sq, g.
 * ``reference_loop``: the script's loop (train_unidirectional_vad.py:144-175) on the float64 two-LSTM module with
   ``torch.optim.RMSprop`` and given masks.
-* the inputs of the GPU tests (``GRAD_CASES``, ``case_inputs``, ``learning_problem``) and their bounds.
+* the inputs of the GPU tests (``GRAD_CASES``, ``case_inputs``, ``learning_problem``), their bounds, and the checkers that
+  tests/test_gpu_vad_training.py and tests/test_gpu_training_cases.py share (``check_window``, ``check_trial_is_its_windows``).
 
 GRAD_BOUND -- per tensor, max|g - g_f64| / max|g_f64| -- is 4 x the worst error of torch float32 CPU autograd against
 ``autograd_window`` over GRAD_CASES (every case with and without a mask, plus the zero-row mask and the one-class window), rounded up to one significant digit;
@@ -26,7 +27,9 @@ KEYS = ("lstm.weight_ih_l0", "lstm.weight_hh_l0", "lstm.bias_ih_l0", "lstm.bias_
 
 # torch float32 CPU autograd, worst tensor over the cases: 1.44e-6 (lstm.bias_ih_l1 at (150, 64, 4), no mask; 1.38e-6 at
 # (150, 64, 37) x 4);  x 4 = 5.74e-6 -> 6e-6.
-# The kernels on MI355X, worst tensor over the same cases: not measured (no run on an MI355X has been recorded).
+# The kernels on MI355X, worst tensor over the same cases: 1.81e-6 (at (150, 64, 4); 1.25e-6 at (150, 64, 37) x 4).
+# The case table of tests/training_cases.py fits the same constant: torch float32 1.32e-6 at worst ((159, 127, 5) without a mask);
+# the kernels on MI355X 7.96e-7 in a gradient (the same entry), 9.9e-9 in the loss, 2.9e-7 in h and 3.6e-7 (relative) in c.
 GRAD_BOUND = 6e-6
 
 # (H, C, T, scale of the LSTM weights)
@@ -186,8 +189,73 @@ def manual_window(sd, x, y, state, mask=None, defect: str | None = None, max_win
 
 
 def rel_errors(got: dict, want: dict) -> dict:
-    """Per tensor: max|got - want| / max|want|."""
-    return {k: float(np.abs(np.asarray(got[k], np.float64) - want[k]).max() / np.abs(want[k]).max()) for k in KEYS}
+    """Per tensor: max|got - want| / max|want|.  A tensor whose true gradient is all zero (weight_hh of a one-frame window from
+    the zero state) must be zero: 0 if it is, inf if not -- as decoder_training_reference.rel_errors has it."""
+    out = {}
+    for k in KEYS:
+        diff, ref = float(np.abs(np.asarray(got[k], np.float64) - want[k]).max()), float(np.abs(want[k]).max())
+        out[k] = diff / ref if ref > 0 else (0.0 if diff == 0 else float("inf"))
+    return out
+
+
+# ---- what the GPU tests hold a window and a trial to ------------------------------------------------------------------------
+
+def check_window(tr, sd, x, y, state, m, scale, f64_frames, what, want=None):
+    """One ``window(step=False)`` of the trainer ``tr`` (a VadTrainerGPU that holds ``sd``) from ``state`` against
+    ``autograd_window`` (or ``want``, its result): every gradient within GRAD_BOUND, the loss within 2 x lstm_reference.bound(scale),
+    the new h within bound(scale), the new c within C_REL.  Prints the figures, then asserts; returns (gradient, loss, h, c) errors."""
+    import torch
+    tr.set_state(*state)
+    xs = torch.from_numpy(x if f64_frames else x.astype(np.float32))
+    loss = tr.window(xs, y, mask=m, step=False)
+    want_loss, want_g, (wh, wc) = want or autograd_window(sd, x, y, state, m)
+    err = rel_errors(tr.gradients(), want_g)
+    h, c = tr.state()
+    eh, ec = float(np.abs(h - wh).max()), float((np.abs(c - wc) / np.maximum(np.abs(wc), 1.0)).max())
+    print(f"{what}: gradient {max(err.values()):.3g} ({max(err, key=err.get)}), loss {abs(loss - want_loss):.3g}, h {eh:.3g}, c {ec:.3g}")
+    for k in KEYS:
+        assert err[k] <= GRAD_BOUND, (what, k, err[k])
+    assert abs(loss - want_loss) <= 2 * R.bound(scale), (what, loss, want_loss)
+    assert eh <= R.bound(scale) and ec <= R.C_REL, (what, eh, ec)
+    return max(err.values()), abs(loss - want_loss), eh, ec
+
+
+def check_trial_is_its_windows(training, H, C, n, window=50):
+    """A trial of n frames through ``VadTrainerGPU.train_trial`` in windows of ``window`` frames (the trainer's ``max_window``),
+    twice from the same loaded state, and once more window by window: ceil(n / window) losses, the same bits all three times
+    (losses, parameters, square averages, carried state), and every window's gradients within GRAD_BOUND of autograd on the
+    weights read back before it."""
+    sd = R.vad_state_dict(H, C, 1)
+    x = R.frames("x2", 1, n, C, 31 * n + H)[0]
+    rng = np.random.default_rng(n + H)
+    y = rng.integers(0, 2, n).astype(np.uint8)
+    masks = (rng.random((n, H)) >= 0.5).astype(np.float32) * np.float32(2.0)
+    lr = 1e-3
+    runs = []
+    for _ in range(2):                                     # the same trial twice from the same loaded state: the same bits
+        tr = training.VadTrainerGPU(sd, max_window=window)
+        tr.set_state(np.ones((2, H), np.float32), np.ones((2, H), np.float32))          # train_trial resets it
+        losses = tr.train_trial(x, y, window=window, masks=masks, lr=lr)
+        runs.append((losses, tr.state_dict(), tr.square_avg(), tr.state()))
+    assert len(runs[0][0]) == -(-n // window)
+    tr = training.VadTrainerGPU(sd, max_window=window)
+    tr.set_state(np.ones((2, H), np.float32), np.ones((2, H), np.float32))
+    tr.reset_state()
+    seq = []
+    for a in range(0, n, window):
+        cur, state = tr.state_dict(), tr.state()
+        seq.append(tr.window(x[a:a + window], y[a:a + window], mask=masks[a:a + window], step=True, lr=lr))
+        _, want, _ = autograd_window(cur, x[a:a + window], y[a:a + window], state, masks[a:a + window])
+        err = rel_errors(tr.gradients(), want)
+        print(f"H {H} trial {n} window at {a}: gradient error {max(err.values()):.3g}")
+        assert max(err.values()) <= GRAD_BOUND, (a, err)
+    seq = (np.array(seq), tr.state_dict(), tr.square_avg(), tr.state())
+    for other in (runs[1], seq):
+        assert np.array_equal(runs[0][0], other[0])
+        for k in KEYS:
+            assert np.array_equal(runs[0][1][k].numpy(), other[1][k].numpy()), k
+            assert np.array_equal(runs[0][2][k], other[2][k]), k
+        assert np.array_equal(runs[0][3][0], other[3][0]) and np.array_equal(runs[0][3][1], other[3][1])
 
 
 # ---- optimiser -----------------------------------------------------------------------------------------------------------------

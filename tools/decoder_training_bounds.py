@@ -7,6 +7,10 @@ of these figures, rounded up to one significant digit; it is stored as ``GRAD_BO
 whether the stored constant still equals what it measures.  The worst case of at most 50 frames and the 350-frame trial are
 reported apart: were the long trial to set the bound far above the short cases, it would get a constant of its own.
 
+The case table of tests/training_cases.py (odd sizes, frame tiles, long trials, output counts) is walked the same way and reported
+beside it.  It does not set the bound: it has to fit it, 4 x its worst figure being at most the stored ``GRAD_BOUND``
+(tests/test_cpu_training_cases.py asserts that per entry).
+
     python tools/decoder_training_bounds.py
 """
 import math
@@ -44,7 +48,18 @@ def main() -> int:
     bound = round_up_1(4.0 * w)
     print(f"4 x {w:.3g} = {4 * w:.3g}  ->  bound {bound:g}")
     print(f"stored GRAD_BOUND = {D.GRAD_BOUND:g}" + ("" if math.isclose(bound, D.GRAD_BOUND, rel_tol=1e-9) else "   (differs: this CPU's torch rounds differently, or the cases changed)"))
-    return 0
+    import training_cases as TC
+    table = (0.0, None)
+    for e, mask in TC.runs(TC.DECODER):
+        err, k = TC.float32_error(e, mask)
+        print(f"(H, C, T, scale, O) = {tuple(e[:5])}  mask = {mask!s:8}  worst tensor {k:30} {err[k]:.3g}")
+        if err[k] > table[0]:
+            table = (err[k], (tuple(e[:5]), mask, k))
+    fits = 4.0 * table[0] <= D.GRAD_BOUND
+    print(f"torch float32 worst, the case table: {table[0]:.3g} at {table[1]}  (GRAD_CASES: {w:.3g})")
+    print(f"4 x {table[0]:.3g} = {4 * table[0]:.3g}  " + (f"<= stored GRAD_BOUND = {D.GRAD_BOUND:g}: the table fits the bound" if fits else
+                                                        f">  stored GRAD_BOUND = {D.GRAD_BOUND:g}: the table does NOT fit the bound; replace the entry"))
+    return 0 if fits else 1
 
 
 if __name__ == "__main__":

@@ -6,6 +6,10 @@ with the float64 reference (``autograd_window``) per tensor: max|g32 - g64| / ma
 of these figures, rounded up to one significant digit; it is stored as ``GRAD_BOUND`` in the helper module, and this tool says
 whether the stored constant still equals what it measures.
 
+The case table of tests/training_cases.py (odd sizes, windows beyond 256 and 640 frames) is walked the same way and reported beside
+it.  It does not set the bound: it has to fit it, 4 x its worst figure being at most the stored ``GRAD_BOUND``
+(tests/test_cpu_training_cases.py asserts that per entry).
+
     python tools/vad_training_bounds.py
 """
 import math
@@ -41,7 +45,18 @@ def main() -> int:
     bound = round_up_1(4.0 * worst[0])
     print(f"torch float32 worst: {worst[0]:.3g} at {worst[1]};  4 x = {4 * worst[0]:.3g}  ->  bound {bound:g}")
     print(f"stored GRAD_BOUND = {V.GRAD_BOUND:g}" + ("" if math.isclose(bound, V.GRAD_BOUND, rel_tol=1e-9) else "   (differs: this CPU's torch rounds differently, or the cases changed)"))
-    return 0
+    import training_cases as TC
+    table = (0.0, None)
+    for e, mask in TC.runs(TC.DETECTOR):
+        err, k = TC.float32_error(e, mask)
+        print(f"(H, C, T, scale) = {TC.case(e)}  mask = {mask!s:8}  worst tensor {k:22} {err[k]:.3g}")
+        if err[k] > table[0]:
+            table = (err[k], (TC.case(e), mask, k))
+    fits = 4.0 * table[0] <= V.GRAD_BOUND
+    print(f"torch float32 worst, the case table: {table[0]:.3g} at {table[1]}  (GRAD_CASES: {worst[0]:.3g})")
+    print(f"4 x {table[0]:.3g} = {4 * table[0]:.3g}  " + (f"<= stored GRAD_BOUND = {V.GRAD_BOUND:g}: the table fits the bound" if fits else
+                                                        f">  stored GRAD_BOUND = {V.GRAD_BOUND:g}: the table does NOT fit the bound; replace the entry"))
+    return 0 if fits else 1
 
 
 if __name__ == "__main__":
