@@ -16,7 +16,7 @@
 // of the input half come from L2 once per workgroup and chunk of DEC_TP steps, the row of W_hh stays in the thread's registers
 // for the whole call, the inputs come from LDS as broadcast reads; h lives in LDS, c in the registers of the thread that owns
 // (stream, unit).  Time steps are sequential; streams x gate rows x directions are the parallel axes.
-#include "dec_lstm_dot.h"
+#include "lstm_blocks.h"
 
 // One layer, both directions (blockIdx.y): in (S, T, Cin) -> out (S, T, 2H), forward h in [0, H), backward in [H, 2H).
 // Ragged form (segments of different lengths in one call, dss_dec_forward_rows_dev): stream s has counts[s] <= T frames (NULL:
@@ -28,7 +28,7 @@ bilstm_layer_kernel(const InT *__restrict__ in, int S, int T, int Cin, int H, co
                     const float *__restrict__ wT_b, const float *__restrict__ b_f, const float *__restrict__ b_b,
                     float *__restrict__ out, const int *__restrict__ counts, const int *__restrict__ in_row, int Tin)
 {
-    typedef typename DecVec<W>::type V;
+    typedef typename LstmVec<W>::type V;
     __shared__ __attribute__((aligned(16))) V xin[DEC_TP][DEC_MAXC];      // [step of the chunk][input][stream of this workgroup]
     __shared__ __attribute__((aligned(16))) V hs[DEC_MAXH];               // [unit][stream]; units H .. Hp-1 stay zero
     __shared__ __attribute__((aligned(16))) V gates[4 * DEC_MAXH];        // [gate row][stream]
@@ -52,12 +52,8 @@ bilstm_layer_kernel(const InT *__restrict__ in, int S, int T, int Cin, int H, co
     const float bias = rowt ? (dir ? b_b : b_f)[tid] : 0.f;
     // this thread's row of W_hh stays in its registers for all steps (DEC_MAXH values, zero beyond H): a step's recurrent half
     // then costs LDS reads of h and arithmetic only -- with the row streamed from L2 every step, L2 latency set the step time
-    df4 whh[DEC_MAXH / 4];
-    {
-        const df4 *wr = reinterpret_cast<const df4 *>(wT + (size_t)Cp * H4) + (rowt ? tid : 0);
-#pragma unroll
-        for (int q = 0; q < DEC_MAXH / 4; ++q) whh[q] = (rowt && 4 * q < Hp) ? wr[(size_t)q * H4] : (df4){0.f, 0.f, 0.f, 0.f};
-    }
+    f4 whh[DEC_MAXH / 4];
+    lstm_load_row<DEC_MAXH>(whh, wT + (size_t)Cp * H4, H4, tid, rowt, Hp);
     __syncthreads();
     int Tw = 0;                                            // the longest of this workgroup's streams
 #pragma unroll
@@ -79,37 +75,25 @@ bilstm_layer_kernel(const InT *__restrict__ in, int S, int T, int Cin, int H, co
         for (int tt = 0; tt < DEC_TP; ++tt)
 #pragma unroll
             for (int s = 0; s < W; ++s) pre[tt][s] = 0.f;
-        if (rowt) dec_dot_steps<W, V>(pre, wT, H4, tid, xin, Cp);               // (steps beyond nst: stale inputs, never used)
+        if (rowt) lstm_dot_steps<W, V, DEC_MAXC, DEC_TP>(pre, wT, H4, tid, xin, Cp);        // (steps beyond nst: stale inputs, never used)
 #pragma unroll
         for (int tt = 0; tt < DEC_TP; ++tt) {
             if (tt >= nst) break;
             const int step = step0 + tt;
             if (rowt) {                                    // gate pre-activations: W_ih x + W_hh h + (b_ih + b_hh)
                 V acc = pre[tt];
-#pragma unroll
-                for (int q = 0; q < DEC_MAXH / 4; ++q) {
-                    if (4 * q >= Hp) break;
-                    const V x0 = hs[4 * q], x1 = hs[4 * q + 1], x2 = hs[4 * q + 2], x3 = hs[4 * q + 3];
-#pragma unroll
-                    for (int s = 0; s < W; ++s) {
-                        acc[s] = __builtin_fmaf(whh[q].x, x0[s], acc[s]);
-                        acc[s] = __builtin_fmaf(whh[q].y, x1[s], acc[s]);
-                        acc[s] = __builtin_fmaf(whh[q].z, x2[s], acc[s]);
-                        acc[s] = __builtin_fmaf(whh[q].w, x3[s], acc[s]);
-                    }
-                }
+                lstm_dot_row<W, V, DEC_MAXH>(acc, whh, hs, Hp);
 #pragma unroll
                 for (int s = 0; s < W; ++s) acc[s] += bias;
                 gates[tid] = acc;
             }
             __syncthreads();
-            if (tid < W * H && step < Tc) {                // cell update of (stream cs, unit cu): c' = f c + i g, h' = o tanh(c')
-                const float gi = reinterpret_cast<const float *>(&gates[cu])[cs];
-                const float gf = reinterpret_cast<const float *>(&gates[H + cu])[cs];
-                const float gg = reinterpret_cast<const float *>(&gates[2 * H + cu])[cs];
-                const float go = reinterpret_cast<const float *>(&gates[3 * H + cu])[cs];
-                c = dec_sigmoid(gf) * c + dec_sigmoid(gi) * tanhf(gg);
-                const float h = dec_sigmoid(go) * tanhf(c);
+            if (tid < W * H && step < Tc) {                // cell update of (stream cs, unit cu)
+                float gi = reinterpret_cast<const float *>(&gates[cu])[cs];
+                float gf = reinterpret_cast<const float *>(&gates[H + cu])[cs];
+                float gg = reinterpret_cast<const float *>(&gates[2 * H + cu])[cs];
+                float go = reinterpret_cast<const float *>(&gates[3 * H + cu])[cs];
+                const float h = lstm_cell(gi, gf, gg, go, c);
                 reinterpret_cast<float *>(&hs[cu])[cs] = h;
                 out[((size_t)(s0 + cs) * T + (dir ? Tc - 1 - step : step)) * (2 * H) + dir * H + cu] = h;
             }

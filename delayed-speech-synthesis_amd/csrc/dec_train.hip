@@ -9,8 +9,8 @@
 //                                         1 / (1 - p); the mask is an INPUT here, (T, 2H) multipliers or NULL
 // The steps of one direction of one layer are serial; the two directions of a layer are independent, and so are the frames
 // everywhere else.  Seven launches per trial on one stream ("Training the decoder"):
-//   dec_train_layer_kernel<0>, <1>   a workgroup per direction: bilstm_layer_kernel's chain for one stream (dec_lstm_dot.h, the
-//                                    row of W_hh in registers, the same cell update) with the stash the backward pass needs
+//   dec_train_layer_kernel<0>, <1>   a workgroup per direction: bilstm_layer_kernel's chain for one stream (lstm_blocks.h: the
+//                                    dot products, the row of W_hh in registers, the cell update) with the stash the backward pass needs
 //   dec_train_head_kernel            a workgroup per 8 frames: features (dec_regress_kernel's dot product), dfeat, the per-frame
 //                                    loss terms, dtop = W_r^T dfeat
 //   dec_train_bptt_kernel<1>         a workgroup per direction: backward through time, the gate gradients dG1[dir][T][4H]; a
@@ -26,8 +26,7 @@
 // argument, because two kernels run it: the single trainer's (above), and the group form at the end of this file, which steps
 // several trainers in one launch (blockIdx.y is the model; DESIGN.md, "Training several decoders at once").  The arithmetic is
 // stated once, so a model's bits do not depend on which of the two ran it.
-#include "dec_lstm_dot.h"
-#include "dss_global_ptr.h"
+#include "lstm_blocks.h"
 
 // offsets of the eighteen tensors in the flat parameter array (state_dict order; also of the gradients and the square averages)
 __host__ __device__ static inline DssDecTrainOff dec_train_off(int C, int H, int O)
@@ -60,7 +59,7 @@ template <typename InT, int LAYER>
 __device__ __forceinline__ void dec_train_layer_body(const DssDecTrainDev &d, const int dir, const InT *__restrict__ in, const int T,
                                                      const float *__restrict__ mask)
 {
-    typedef typename DecVec<1>::type V;
+    typedef typename LstmVec<1>::type V;
     __shared__ __attribute__((aligned(16))) V xin[DEC_TP][DEC_MAXC];
     __shared__ __attribute__((aligned(16))) V hs[DEC_MAXH];               // units H .. Hp-1 stay zero
     __shared__ __attribute__((aligned(16))) V gates[4 * DEC_MAXH];
@@ -75,12 +74,8 @@ __device__ __forceinline__ void dec_train_layer_body(const DssDecTrainDev &d, co
     for (int k = tid; k < DEC_TP * DEC_MAXC; k += DEC_THREADS) reinterpret_cast<float *>(xin)[k] = 0.f;
     if (own) { cst[tid] = 0.f; hst[tid] = 0.f; }           // row 0 of the stashes: the zero state
     const float bias = rowt ? dss_gp(d.b[LAYER][dir])[tid] : 0.f;
-    df4 whh[DEC_MAXH / 4];                                 // this thread's row of W_hh, in registers for all steps
-    {
-        const df4 *wr = reinterpret_cast<const df4 *>(wT + (size_t)Cp * H4) + (rowt ? tid : 0);
-#pragma unroll
-        for (int q = 0; q < DEC_MAXH / 4; ++q) whh[q] = (rowt && 4 * q < Hp) ? wr[(size_t)q * H4] : (df4){0.f, 0.f, 0.f, 0.f};
-    }
+    f4 whh[DEC_MAXH / 4];                                  // this thread's row of W_hh, in registers for all steps
+    lstm_load_row<DEC_MAXH>(whh, wT + (size_t)Cp * H4, H4, tid, rowt, Hp);
     __syncthreads();
     for (int step0 = 0; step0 < T; step0 += DEC_TP) {
         const int nst = min(DEC_TP, T - step0);
@@ -95,32 +90,22 @@ __device__ __forceinline__ void dec_train_layer_body(const DssDecTrainDev &d, co
         V pre[DEC_TP];
 #pragma unroll
         for (int tt = 0; tt < DEC_TP; ++tt) pre[tt].v = 0.f;
-        if (rowt) dec_dot_steps<1, V>(pre, wT, H4, tid, xin, Cp);          // (steps beyond nst: stale inputs, never used)
+        if (rowt) lstm_dot_steps<1, V, DEC_MAXC, DEC_TP>(pre, wT, H4, tid, xin, Cp);   // (steps beyond nst: stale inputs, never used)
 #pragma unroll
         for (int tt = 0; tt < DEC_TP; ++tt) {
             if (tt >= nst) break;
             const int step = step0 + tt, t = dir ? T - 1 - step : step;
             if (rowt) {
                 V acc = pre[tt];
-#pragma unroll
-                for (int q = 0; q < DEC_MAXH / 4; ++q) {
-                    if (4 * q >= Hp) break;
-                    const V x0 = hs[4 * q], x1 = hs[4 * q + 1], x2 = hs[4 * q + 2], x3 = hs[4 * q + 3];
-                    acc.v = __builtin_fmaf(whh[q].x, x0.v, acc.v);
-                    acc.v = __builtin_fmaf(whh[q].y, x1.v, acc.v);
-                    acc.v = __builtin_fmaf(whh[q].z, x2.v, acc.v);
-                    acc.v = __builtin_fmaf(whh[q].w, x3.v, acc.v);
-                }
+                lstm_dot_row<1, V, DEC_MAXH>(acc, whh, hs, Hp);
                 acc.v += bias;
                 gates[tid] = acc;
             }
             __syncthreads();
             if (own) {
-                const float gi = dec_sigmoid(gates[tid].v), gf = dec_sigmoid(gates[H + tid].v), gg = tanhf(gates[2 * H + tid].v),
-                            go = dec_sigmoid(gates[3 * H + tid].v);
-                c = gf * c + gi * gg;
-                const float h = go * tanhf(c);
-                hs[tid].v = h;                             // the unmasked h is what the direction carries to its own next step
+                float gi = gates[tid].v, gf = gates[H + tid].v, gg = gates[2 * H + tid].v, go = gates[3 * H + tid].v;
+                const float h = lstm_cell(gi, gf, gg, go, c);
+                hs[tid].v = h;                            // the unmasked h is what the direction carries to its own next step
                 float *a = act + (size_t)step * H4;
                 a[tid] = gi; a[H + tid] = gf; a[2 * H + tid] = gg; a[3 * H + tid] = go;
                 cst[(size_t)(step + 1) * H + tid] = c;
@@ -267,7 +252,7 @@ __device__ __forceinline__ void dec_train_bptt_body(const DssDecTrainDev &d, con
 #pragma unroll
             for (int k = 0; k < DEC_MAXH / 4; ++k) {
                 if (4 * k >= H) break;
-                const df4 g4 = *reinterpret_cast<const df4 *>(&dgs[q][4 * k]);
+                const f4 g4 = *reinterpret_cast<const f4 *>(&dgs[q][4 * k]);
                 acc = __builtin_fmaf(wt[4 * k], g4.x, acc);
                 acc = __builtin_fmaf(wt[4 * k + 1], g4.y, acc);
                 acc = __builtin_fmaf(wt[4 * k + 2], g4.z, acc);
@@ -322,7 +307,7 @@ __device__ __forceinline__ void dec_train_dmid_body(const DssDecTrainDev &d, con
             for (int u = 0; u < 4; ++u) w[u] = W[(size_t)(r + u) * K];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const df4 g0 = *reinterpret_cast<const df4 *>(&dgl[dd][r + u][0]), g1 = *reinterpret_cast<const df4 *>(&dgl[dd][r + u][4]);
+                const f4 g0 = *reinterpret_cast<const f4 *>(&dgl[dd][r + u][0]), g1 = *reinterpret_cast<const f4 *>(&dgl[dd][r + u][4]);
                 acc[dd][0] = __builtin_fmaf(w[u], g0.x, acc[dd][0]); acc[dd][1] = __builtin_fmaf(w[u], g0.y, acc[dd][1]);
                 acc[dd][2] = __builtin_fmaf(w[u], g0.z, acc[dd][2]); acc[dd][3] = __builtin_fmaf(w[u], g0.w, acc[dd][3]);
                 acc[dd][4] = __builtin_fmaf(w[u], g1.x, acc[dd][4]); acc[dd][5] = __builtin_fmaf(w[u], g1.y, acc[dd][5]);
@@ -353,88 +338,40 @@ dec_train_dmid_kernel(DssDecTrainDev d, int T, const float *__restrict__ mask)
 // against dfeat.  The inputs: layer 0 reads the frames (xs), layer 1 the masked output of layer 0 (midm), the head layer 1's output
 // (top); the W_hh columns read the direction's own h of the step before -- frame t is step t forward, step T - 1 - t backward, and
 // row s of the stash is h before step s (row 0: zeros).
-// The update is evaluated per element in float64 from the stored float32 values and rounded once (vad_train.hip's vad_rmsprop).
-// bias_ih and bias_hh get the same g and each its own square average; the packed bias is their float32 sum.
+// The sums, the update and the write-back are lstm_train_step_row (lstm_blocks.h), the detector's too.
 // Two columns per thread: a row has at most max(C, 2H) + H + 1 <= 256 + 128 + 1 = 385 <= 2 x 256 columns.
 #define DTS_THREADS 256
-
-__device__ __forceinline__ float dec_rmsprop(const DssDecTrainDev &d, int k, float g, int apply, double lr, double alpha, double eps)
-{
-    float *dp = dss_gp(d.p), *dsq = dss_gp(d.sq);
-    dss_gp(d.g)[k] = g;
-    if (!apply) return dp[k];
-    const float sq = (float)(alpha * (double)dsq[k] + (1.0 - alpha) * ((double)g * (double)g));
-    dsq[k] = sq;
-    const float p = (float)((double)dp[k] - lr * (double)g / (sqrt((double)sq) + eps));
-    dp[k] = p;
-    return p;
-}
 
 __device__ __forceinline__ void dec_train_step_body(const DssDecTrainDev &d, const int b, const int T, const int apply, const double lr,
                                                     const double alpha, const double eps)
 {
-    __shared__ float dgt[DTS_THREADS];
-    const int tid = threadIdx.x, C = d.C, H = d.H, H4 = 4 * H, O = d.O;
+    const int C = d.C, H = d.H, H4 = 4 * H, O = d.O;
     const bool head = b >= 4 * H4;
     const int LD = head ? 0 : b / H4, L = LD >> 1, dir = LD & 1, r = head ? b - 4 * H4 : b - LD * H4;
-    const float *dg = dss_gp(head ? d.dfeat : d.dg[L][dir]) + r;
-    const int dgs = head ? O : H4;
-    const float *inA = dss_gp(head ? d.top : (L ? d.midm : d.xs)), *inB = dss_gp(d.h[L][dir]);
-    const int nA = head || L ? 2 * H : C, nB = head ? 0 : H, ncol = nA + nB + 1;
-    const int Cp = (nA + 3) & ~3;
     // the flat offsets of this (layer, direction)'s four tensors, and of the head (dec_train_off, without an indexed table)
     const int sz0 = H4 * (C + H + 2), sz1 = H4 * (3 * H + 2);
+    const int nA = head || L ? 2 * H : C;
     const int o_wih = LD < 2 ? LD * sz0 : 2 * sz0 + (LD - 2) * sz1, o_whh = o_wih + H4 * nA, o_bih = o_whh + H4 * H, o_bhh = o_bih + H4;
     const int o_wr = 2 * sz0 + 2 * sz1, o_br = o_wr + O * 2 * H;
-    const float *src[2];
-    long stride[2];
-    int col[2];
-    bool live[2], bias[2];
-    float acc[2] = {0.f, 0.f};
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        col[u] = tid + u * DTS_THREADS;
-        live[u] = col[u] < ncol;
-        bias[u] = col[u] == ncol - 1;
-        const bool a = col[u] < nA;
-        if (!live[u] || bias[u]) { src[u] = inA; stride[u] = 0; }
-        else if (a) { src[u] = inA + col[u]; stride[u] = nA; }
-        else { src[u] = inB + (col[u] - nA) + (dir ? (size_t)(T - 1) * H : 0); stride[u] = dir ? -(long)H : (long)H; }
-    }
-    for (int t0 = 0; t0 < T; t0 += DTS_THREADS) {
-        const int n = min(DTS_THREADS, T - t0);
-        if (tid < n) dgt[tid] = dg[(size_t)(t0 + tid) * dgs];
-        __syncthreads();
-        for (int tt = 0; tt < n; ++tt) {
-            const float g = dgt[tt];
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const float x = bias[u] ? 1.f : dss_gp(src[u])[(long)(t0 + tt) * stride[u]];
-                acc[u] = __builtin_fmaf(g, x, acc[u]);
-            }
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        if (!live[u]) continue;
-        const int k = col[u];
-        if (head) {
-            dec_rmsprop(d, bias[u] ? o_br + r : o_wr + r * nA + k, acc[u], apply, lr, alpha, eps);
-        } else if (bias[u]) {
-            const float bi = dec_rmsprop(d, o_bih + r, acc[u], apply, lr, alpha, eps);
-            const float bh = dec_rmsprop(d, o_bhh + r, acc[u], apply, lr, alpha, eps);
-            if (apply) dss_gp(d.b[L][dir])[r] = bi + bh;
-        } else {
-            const bool a = k < nA;
-            const int pk = a ? o_wih + r * nA + k : o_whh + r * H + (k - nA);
-            const float p = dec_rmsprop(d, pk, acc[u], apply, lr, alpha, eps);
-            // the packed copy: [inputs / 4][4H rows][4 consecutive inputs], W_hh behind W_ih's padded inputs
-            const int ki = a ? k : Cp + (k - nA);
-            if (apply) dss_gp(d.wT[L][dir])[((size_t)(ki >> 2) * H4 + r) * 4 + (ki & 3)] = p;
-        }
-    }
+    LstmStepRow w;
+    w.dg = dss_gp(head ? d.dfeat : d.dg[L][dir]) + r;
+    w.dgs = head ? O : H4;
+    w.inA = dss_gp(head ? d.top : (L ? d.midm : d.xs));
+    w.nA = nA;
+    // frame t is step T - 1 - t of the backward direction: its stash of h is read from the last row upward
+    w.inB = dss_gp(d.h[L][dir]) + (dir ? (size_t)(T - 1) * H : 0);
+    w.nB = head ? 0 : H;
+    w.strideB = dir ? -(long)H : (long)H;
+    w.o_A = (head ? o_wr : o_wih) + r * nA;
+    w.o_B = o_whh + r * H;
+    w.o_bias = head ? o_br + r : o_bih + r;
+    w.o_bias2 = o_bhh + r;
+    w.wpk = head ? nullptr : dss_gp(d.wT[L][dir]);
+    w.bpk = dss_gp(d.b[L][dir]) + r;
+    w.r = r; w.H4 = H4; w.kB = (nA + 3) & ~3;
+    lstm_train_step_row<DTS_THREADS>(w, dss_gp(d.p), dss_gp(d.sq), dss_gp(d.g), T, apply, lr, alpha, eps);
 }
+
 
 __global__ void __launch_bounds__(DTS_THREADS)
 dec_train_step_kernel(DssDecTrainDev d, int T, int apply, double lr, double alpha, double eps)

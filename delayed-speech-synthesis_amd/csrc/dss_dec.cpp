@@ -88,12 +88,9 @@ extern "C" int dss_dec_load_weights(dss_dec *v, const float *const *w)
             const float *b_ih = w[(layer * 2 + dir) * 4 + 2], *b_hh = w[(layer * 2 + dir) * 4 + 3];
             // the kernel's copy: [inputs / 4][4H rows][4 consecutive inputs], input counts padded to multiples of 4 with zero weights
             std::vector<float> t((size_t)(Cp + Hp) * H4, 0.f), b(H4);
-            auto put = [&](int k, int r, float x) { t[((size_t)(k >> 2) * H4 + r) * 4 + (k & 3)] = x; };
-            for (int r = 0; r < H4; ++r) {
-                for (int k = 0; k < Cin; ++k) put(k, r, w_ih[(size_t)r * Cin + k]);
-                for (int k = 0; k < H; ++k) put(Cp + k, r, w_hh[(size_t)r * H + k]);
-                b[r] = b_ih[r] + b_hh[r];
-            }
+            dss_pack_rows(t.data(), H4, 0, w_ih, Cin);
+            dss_pack_rows(t.data(), H4, Cp, w_hh, H);
+            for (int r = 0; r < H4; ++r) b[r] = b_ih[r] + b_hh[r];
             rc |= v->blocks.upload<float>(t.data(), t.size(), &nw[layer * 2 + dir]);
             rc |= v->blocks.upload<float>(b.data(), b.size(), &nw[4 + layer * 2 + dir]);
         }

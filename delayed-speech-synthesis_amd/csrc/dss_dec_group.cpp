@@ -1,9 +1,7 @@
 // csrc/dss_dec_group.cpp -- host side of Part 13 of include/dss_hip.h: several decoders of equal sizes trained side by side, one
 // set of seven launches per step (the group kernels of csrc/dec_train.hip).  A group owns M trainers of Part 10 -- so loading,
 // reading and publishing a member are Part 10's own functions on that member -- a device table of their M descriptors, written
-// once, and a ring of trial tables: a step fills the next page-locked slot, copies it to the slot's device table in stream order
-// and launches on that table, so a step enqueued while earlier ones still run never rewrites a table they read.  A slot is
-// reused only after the event behind its step's last launch (DssPinnedRing: the ninth step in flight waits for the first).
+// once, and a ring of trial tables (DssGroupTables, dss_host.h).
 #include <vector>
 
 #include "dss_host.h"
@@ -12,11 +10,7 @@ struct dss_dec_group {
     int device = 0;
     int M = 0, C = 0, H = 0, O = 0, Tmax = 0;
     std::vector<dss_dec_trainer *> tr;
-    DssDecTrainDev *d_models = nullptr;                   // [M]
-    DssDecGroupTrial *d_trials[DssPinnedRing::K] = {};    // [K][M]
-    DssDevBlocks blocks;                                  // the two kinds of table; a member's memory is the member's
-    DssPinnedRing ring;
-    bool ring_ok = false;
+    DssGroupTables<DssDecTrainDev, DssDecGroupTrial> tables;
 };
 
 extern "C" int dss_dec_group_check(int n_models, int n_inputs, int hidden_units, int n_outputs, int max_frames)
@@ -35,8 +29,7 @@ extern "C" void dss_dec_group_destroy(dss_dec_group *g)
     if (!g) return;
     hipSetDevice(g->device);
     hipDeviceSynchronize();
-    g->blocks.free_all();
-    if (g->ring_ok) g->ring.destroy();
+    g->tables.destroy();
     for (dss_dec_trainer *t : g->tr) dss_dec_trainer_destroy(t);
     delete g;
 }
@@ -56,14 +49,7 @@ extern "C" dss_dec_group *dss_dec_group_create(int n_models, int n_inputs, int h
         int device = 0, loaded = 0;
         dss_dec_trainer_view(t, &table[m], &device, &loaded);
     }
-    const size_t tb = (size_t)n_models * sizeof(DssDecGroupTrial);
-    bool ok = g->blocks.alloc_bytes(table.size() * sizeof(DssDecTrainDev), (void **)&g->d_models) == DSS_OK &&
-              hipMemcpy(g->d_models, table.data(), table.size() * sizeof(DssDecTrainDev), hipMemcpyHostToDevice) == hipSuccess;
-    for (int k = 0; ok && k < DssPinnedRing::K; ++k)
-        ok = g->blocks.alloc_bytes(tb, (void **)&g->d_trials[k]) == DSS_OK && hipMemset(g->d_trials[k], 0, tb) == hipSuccess;
-    g->ring_ok = true;
-    if (ok) ok = g->ring.init((tb + sizeof(int) - 1) / sizeof(int)) == DSS_OK;
-    if (!ok) {
+    if (g->tables.init(table)) {
         dss_set_error("device allocation failed for the tables of a group of %d decoder trainers", n_models);
         dss_dec_group_destroy(g);
         return nullptr;
@@ -132,7 +118,7 @@ extern "C" int dss_dec_group_step_dev(dss_dec_group *g, const dss_dec_group_tria
     if (!max_T) { dss_set_error("dss_dec_group_step_dev: every model sits out (all T are 0): nothing to launch"); return DSS_EINVAL; }
     DSS_HIP_CHECK(hipSetDevice(g->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    DssDecGroupTrial *slot = (DssDecGroupTrial *)g->ring.acquire();
+    DssDecGroupTrial *slot = g->tables.acquire();
     if (!slot) { dss_set_error("dss_dec_group_step_dev: waiting for a free trial table failed"); return DSS_ENODEV; }
     for (int m = 0; m < g->M; ++m) {
         const dss_dec_group_trial &t = trials[m];
@@ -141,10 +127,11 @@ extern "C" int dss_dec_group_step_dev(dss_dec_group *g, const dss_dec_group_tria
         e.lr = t.lr; e.alpha = t.alpha; e.eps = t.eps;
         e.T = t.T; e.apply = t.apply_step;
     }
-    DssDecGroupTrial *d_slot = g->d_trials[g->ring.cur];
-    DSS_HIP_CHECK(hipMemcpyAsync(d_slot, slot, (size_t)g->M * sizeof(DssDecGroupTrial), hipMemcpyHostToDevice, st));
-    int rc = dss_launch_dec_train_group(g->d_models, d_slot, g->M, g->C, g->H, g->O, max_T, frames_are_f64, st);
+    const DssDecGroupTrial *d_slot = nullptr;
+    int rc = g->tables.upload(st, &d_slot);
+    if (rc) return rc;
+    rc = dss_launch_dec_train_group(g->tables.d_models, d_slot, g->M, g->C, g->H, g->O, max_T, frames_are_f64, st);
     // behind the launches, not only the copy: the device table of the slot is read until the step's last launch has run
-    int rc2 = g->ring.commit(st);
+    int rc2 = g->tables.commit_after_launch(st);
     return rc ? rc : rc2;
 }

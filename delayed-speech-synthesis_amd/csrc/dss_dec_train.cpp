@@ -116,12 +116,9 @@ extern "C" int dss_dec_trainer_load(dss_dec_trainer *tr, const float *const *w)
             flat.insert(flat.end(), b_ih, b_ih + H4);
             flat.insert(flat.end(), b_hh, b_hh + H4);
             std::vector<float> t(tr->n_wT[L], 0.f), b(H4);
-            auto put = [&](int k, int r, float x) { t[((size_t)(k >> 2) * H4 + r) * 4 + (k & 3)] = x; };
-            for (int r = 0; r < H4; ++r) {
-                for (int k = 0; k < Cin; ++k) put(k, r, w_ih[(size_t)r * Cin + k]);
-                for (int k = 0; k < H; ++k) put(Cp + k, r, w_hh[(size_t)r * H + k]);
-                b[r] = b_ih[r] + b_hh[r];
-            }
+            dss_pack_rows(t.data(), H4, 0, w_ih, Cin);
+            dss_pack_rows(t.data(), H4, Cp, w_hh, H);
+            for (int r = 0; r < H4; ++r) b[r] = b_ih[r] + b_hh[r];
             DSS_HIP_CHECK(hipMemcpy(d.wT[L][dir], t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
             DSS_HIP_CHECK(hipMemcpy(d.b[L][dir], b.data(), b.size() * sizeof(float), hipMemcpyHostToDevice));
         }

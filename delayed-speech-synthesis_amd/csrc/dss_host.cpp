@@ -2,6 +2,13 @@
 #include <algorithm>
 
 #include "dss_host.h"
+#include "lstm_blocks.h"
+
+void dss_pack_rows(float *packed, int H4, int k0, const float *w, int n)
+{
+    for (int r = 0; r < H4; ++r)
+        for (int k = 0; k < n; ++k) packed[lstm_packed_index(k0 + k, r, H4)] = w[(size_t)r * n + k];
+}
 
 int DssDevBlocks::alloc_bytes(size_t bytes, void **p)
 {

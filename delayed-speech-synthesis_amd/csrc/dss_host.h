@@ -42,6 +42,11 @@ static int trials_reduce(const char *what, int n_trials, const int *len, F launc
     return DSS_OK;
 }
 
+// A row-major [4H][n] gate matrix (torch.nn.LSTM's layout) into the kernels' packed copy, as the copy's inputs k0 .. k0 + n: W_ih at
+// 0, W_hh behind W_ih's input count padded to a multiple of 4.  The layout itself is lstm_packed_index (lstm_blocks.h), which the
+// training kernels' update of the same copy uses.  `packed` starts out zeroed: the padded inputs keep zero weights.
+DSS_LOCAL void dss_pack_rows(float *packed, int H4, int k0, const float *w, int n);
+
 static inline size_t dss_headroom(size_t need) { return need + need / 4 + 64; }
 
 // One owner for the device memory of a handle (and of the model, per device).  Every block allocated through it is remembered
@@ -175,6 +180,50 @@ struct DssPinnedRing {
         pending[cur] = true;
         return DSS_OK;
     }
+};
+
+// The tables of a group of trainers stepped by one set of launches (Parts 13 and 15), over the two plain structs the group kernels
+// read: a device table of the members' M descriptors, written once, and a ring of trial tables.  A step fills the next page-locked
+// slot (acquire), copies it to the slot's device table in stream order (upload) and launches on that table, so a step enqueued
+// while earlier ones still run never rewrites a table they read; a slot is reused only after the event behind its step's LAST
+// launch (commit_after_launch: the device table is read until then, not only by the copy).  The ninth step in flight waits for
+// the first.  The members' own memory is the members'.
+template <typename Model, typename Trial>
+struct DssGroupTables {
+    int M = 0;
+    Model *d_models = nullptr;                            // [M]
+    Trial *d_trials[DssPinnedRing::K] = {};               // [K][M]
+    DssDevBlocks blocks;
+    DssPinnedRing ring;
+    bool ring_ok = false;
+
+    int init(const std::vector<Model> &table)
+    {
+        M = (int)table.size();
+        const size_t tb = (size_t)M * sizeof(Trial);
+        bool ok = blocks.alloc_bytes(table.size() * sizeof(Model), (void **)&d_models) == DSS_OK &&
+                  hipMemcpy(d_models, table.data(), table.size() * sizeof(Model), hipMemcpyHostToDevice) == hipSuccess;
+        for (int k = 0; ok && k < DssPinnedRing::K; ++k)
+            ok = blocks.alloc_bytes(tb, (void **)&d_trials[k]) == DSS_OK && hipMemset(d_trials[k], 0, tb) == hipSuccess;
+        ring_ok = true;
+        if (ok) ok = ring.init((tb + sizeof(int) - 1) / sizeof(int)) == DSS_OK;
+        return ok ? DSS_OK : DSS_ENOMEM;
+    }
+    void destroy()
+    {
+        blocks.free_all();
+        if (ring_ok) ring.destroy();
+    }
+    // the host slot this step may fill (nullptr on a HIP error)
+    Trial *acquire() { return (Trial *)ring.acquire(); }
+    // the acquired slot to its device table; *d_slot is what the step's launches read
+    int upload(hipStream_t s, const Trial **d_slot)
+    {
+        DSS_HIP_CHECK(hipMemcpyAsync(d_trials[ring.cur], ring.host[ring.cur], (size_t)M * sizeof(Trial), hipMemcpyHostToDevice, s));
+        *d_slot = d_trials[ring.cur];
+        return DSS_OK;
+    }
+    int commit_after_launch(hipStream_t s) { return ring.commit(s); }
 };
 
 // One grow-only page-locked block for a call's variable-size table (the trial lists of Part 8): acquire(bytes) waits until the

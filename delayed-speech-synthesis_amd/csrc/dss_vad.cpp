@@ -73,12 +73,11 @@ extern "C" int dss_vad_load_weights(dss_vad *v, const float *w_ih0, const float 
     const int C = v->d.C, H = v->d.H, H4 = 4 * H, Cp = (C + 3) & ~3, Hp = (H + 3) & ~3;
     // the kernel's copies: [inputs / 4][4H rows][4 consecutive inputs], input counts padded to multiples of 4 with zero weights
     std::vector<float> t0((size_t)(Cp + Hp) * H4, 0.f), t1((size_t)2 * Hp * H4, 0.f), b0(H4), b1(H4);
-    auto put = [&](std::vector<float> &t, int k, int r, float w) { t[((size_t)(k >> 2) * H4 + r) * 4 + (k & 3)] = w; };
+    dss_pack_rows(t0.data(), H4, 0, w_ih0, C);
+    dss_pack_rows(t0.data(), H4, Cp, w_hh0, H);
+    dss_pack_rows(t1.data(), H4, 0, w_ih1, H);
+    dss_pack_rows(t1.data(), H4, Hp, w_hh1, H);
     for (int r = 0; r < H4; ++r) {
-        for (int k = 0; k < C; ++k) put(t0, k, r, w_ih0[(size_t)r * C + k]);
-        for (int k = 0; k < H; ++k) put(t0, Cp + k, r, w_hh0[(size_t)r * H + k]);
-        for (int k = 0; k < H; ++k) put(t1, k, r, w_ih1[(size_t)r * H + k]);
-        for (int k = 0; k < H; ++k) put(t1, Hp + k, r, w_hh1[(size_t)r * H + k]);
         b0[r] = b_ih0[r] + b_hh0[r];
         b1[r] = b_ih1[r] + b_hh1[r];
     }

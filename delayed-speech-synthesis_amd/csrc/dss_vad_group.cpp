@@ -1,10 +1,7 @@
 // csrc/dss_vad_group.cpp -- host side of Part 15 of include/dss_hip.h: several detectors of equal sizes trained side by side, one
 // pair of launches per window (the group kernels of csrc/vad_train.hip).  A group owns M trainers of Part 9 -- so loading,
 // reading, state access and publishing a member are Part 9's own functions on that member -- a device table of their M
-// descriptors, written once, and a ring of trial tables: a step fills the next page-locked slot, copies it to the slot's device
-// table in stream order and launches on that table, so a step enqueued while earlier ones still run never rewrites a table they
-// read.  A slot is reused only after the event behind its step's last launch (DssPinnedRing: the ninth step in flight waits for
-// the first).
+// descriptors, written once, and a ring of trial tables (DssGroupTables, dss_host.h).
 #include <vector>
 
 #include "dss_host.h"
@@ -13,11 +10,7 @@ struct dss_vad_group {
     int device = 0;
     int M = 0, C = 0, H = 0, Tmax = 0;
     std::vector<dss_vad_trainer *> tr;
-    DssVadTrainDev *d_models = nullptr;                   // [M]
-    DssVadGroupTrial *d_trials[DssPinnedRing::K] = {};    // [K][M]
-    DssDevBlocks blocks;                                  // the two kinds of table; a member's memory is the member's
-    DssPinnedRing ring;
-    bool ring_ok = false;
+    DssGroupTables<DssVadTrainDev, DssVadGroupTrial> tables;
 };
 
 extern "C" int dss_vad_group_check(int n_models, int n_inputs, int hidden_units, int max_window)
@@ -36,8 +29,7 @@ extern "C" void dss_vad_group_destroy(dss_vad_group *g)
     if (!g) return;
     hipSetDevice(g->device);
     hipDeviceSynchronize();
-    g->blocks.free_all();
-    if (g->ring_ok) g->ring.destroy();
+    g->tables.destroy();
     for (dss_vad_trainer *t : g->tr) dss_vad_trainer_destroy(t);
     delete g;
 }
@@ -57,14 +49,7 @@ extern "C" dss_vad_group *dss_vad_group_create(int n_models, int n_inputs, int h
         int device = 0, loaded = 0;
         dss_vad_trainer_view(t, &table[m], &device, &loaded);
     }
-    const size_t tb = (size_t)n_models * sizeof(DssVadGroupTrial);
-    bool ok = g->blocks.alloc_bytes(table.size() * sizeof(DssVadTrainDev), (void **)&g->d_models) == DSS_OK &&
-              hipMemcpy(g->d_models, table.data(), table.size() * sizeof(DssVadTrainDev), hipMemcpyHostToDevice) == hipSuccess;
-    for (int k = 0; ok && k < DssPinnedRing::K; ++k)
-        ok = g->blocks.alloc_bytes(tb, (void **)&g->d_trials[k]) == DSS_OK && hipMemset(g->d_trials[k], 0, tb) == hipSuccess;
-    g->ring_ok = true;
-    if (ok) ok = g->ring.init((tb + sizeof(int) - 1) / sizeof(int)) == DSS_OK;
-    if (!ok) {
+    if (g->tables.init(table)) {
         dss_set_error("device allocation failed for the tables of a group of %d detector trainers", n_models);
         dss_vad_group_destroy(g);
         return nullptr;
@@ -141,7 +126,7 @@ static int group_step(dss_vad_group *g, const dss_vad_group_trial *trials, int w
     if (!n_windows) { dss_set_error("%s: every model sits out (all len are 0): nothing to launch", who); return DSS_EINVAL; }
     DSS_HIP_CHECK(hipSetDevice(g->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    DssVadGroupTrial *slot = (DssVadGroupTrial *)g->ring.acquire();
+    DssVadGroupTrial *slot = g->tables.acquire();
     if (!slot) { dss_set_error("%s: waiting for a free trial table failed", who); return DSS_ENODEV; }
     for (int m = 0; m < g->M; ++m) {
         const dss_vad_group_trial &t = trials[m];
@@ -150,11 +135,12 @@ static int group_step(dss_vad_group *g, const dss_vad_group_trial *trials, int w
         e.lr = t.lr; e.alpha = t.alpha; e.eps = t.eps;
         e.len = t.len; e.apply = whole_trials ? 1 : t.apply_step;
     }
-    DssVadGroupTrial *d_slot = g->d_trials[g->ring.cur];
-    DSS_HIP_CHECK(hipMemcpyAsync(d_slot, slot, (size_t)g->M * sizeof(DssVadGroupTrial), hipMemcpyHostToDevice, st));
-    int rc = dss_launch_vad_train_group(g->d_models, d_slot, g->M, g->C, g->H, n_windows, win, whole_trials ? 1 : 0, frames_are_f64, st);
+    const DssVadGroupTrial *d_slot = nullptr;
+    int rc = g->tables.upload(st, &d_slot);
+    if (rc) return rc;
+    rc = dss_launch_vad_train_group(g->tables.d_models, d_slot, g->M, g->C, g->H, n_windows, win, whole_trials ? 1 : 0, frames_are_f64, st);
     // behind the last launch, not only the copy: the device table of the slot is read until the step's last window has run
-    int rc2 = g->ring.commit(st);
+    int rc2 = g->tables.commit_after_launch(st);
     return rc ? rc : rc2 ? rc2 : n_windows;
 }
 

@@ -108,12 +108,11 @@ extern "C" int dss_vad_trainer_load(dss_vad_trainer *tr, const float *w_ih0, con
                             (size_t)2 * H, 2};
     for (int k = 0; k < 10; ++k) flat.insert(flat.end(), src[k], src[k] + cnt[k]);
     std::vector<float> t0(tr->n_wT0, 0.f), t1(tr->n_wT1, 0.f), b0(H4), b1(H4);
-    auto put = [&](std::vector<float> &t, int k, int r, float w) { t[((size_t)(k >> 2) * H4 + r) * 4 + (k & 3)] = w; };
+    dss_pack_rows(t0.data(), H4, 0, w_ih0, C);
+    dss_pack_rows(t0.data(), H4, Cp, w_hh0, H);
+    dss_pack_rows(t1.data(), H4, 0, w_ih1, H);
+    dss_pack_rows(t1.data(), H4, Hp, w_hh1, H);
     for (int r = 0; r < H4; ++r) {
-        for (int k = 0; k < C; ++k) put(t0, k, r, w_ih0[(size_t)r * C + k]);
-        for (int k = 0; k < H; ++k) put(t0, Cp + k, r, w_hh0[(size_t)r * H + k]);
-        for (int k = 0; k < H; ++k) put(t1, k, r, w_ih1[(size_t)r * H + k]);
-        for (int k = 0; k < H; ++k) put(t1, Hp + k, r, w_hh1[(size_t)r * H + k]);
         b0[r] = b_ih0[r] + b_hh0[r];
         b1[r] = b_ih1[r] + b_hh1[r];
     }

@@ -15,30 +15,34 @@
 // streams from LDS as broadcast reads.  h lives in LDS, c
 // in the registers of the thread that owns (stream, unit).  The time steps and the two layers are sequential; streams x
 // gate rows are the parallel axes.  Weights 1.24 MB fp32 for H = 150: L2-resident after the first workgroup has read them.
-#include "vad_lstm_dot.h"
+#include "lstm_blocks.h"
 
-template <typename FrameT, int SW>
-__global__ void __launch_bounds__(VAD_THREADS)
-vad_lstm_kernel(DssVadDev v, const FrameT *__restrict__ frames, int W, int *__restrict__ labels, float *__restrict__ logits)
+// The forward pass of one workgroup: SW streams, W frames each, through both layers and the classifier.  Stream s of the call
+// (s0 <= s < min(s0 + SW, S)) reads frames[(s * W + w) * C ..] and writes labels[s * W + w] and, unless logits is NULL,
+// logits[(s * W + w) * 2 ..].  CARRY: (h, c) of both layers come from the handle and go back to it; otherwise the streams start
+// from zeros (create_new_initial_state, models.py:22-24) and the handle's state is not touched.  Both kernels below run this
+// body, so a frame's bits do not depend on which of them stepped it.
+template <typename FrameT, int SW, bool CARRY>
+__device__ __forceinline__ void vad_forward_body(const DssVadDev &v, const FrameT *__restrict__ frames, const int W, int *__restrict__ labels,
+                                                 float *__restrict__ logits, const int s0, const int S)
 {
-    typedef typename VadVec<SW>::type V;
+    typedef typename LstmVec<SW>::type V;
     __shared__ __attribute__((aligned(16))) V xin[VAD_TP][VAD_MAXC];      // [frame of the chunk][input][stream of this workgroup]
     __shared__ __attribute__((aligned(16))) V h0s[VAD_TP][VAD_MAXH];      // layer 0's h of the chunk's frames (layer 1's inputs)
     __shared__ __attribute__((aligned(16))) V hs[2][VAD_MAXH];            // [layer][unit][stream]; units H .. Hp-1 stay zero
     __shared__ __attribute__((aligned(16))) V gates[4 * VAD_MAXH];        // [gate row][stream]
     __shared__ float lg[SW][2];
-    const int tid = threadIdx.x, S = v.S, C = v.C, H = v.H, H4 = 4 * H;
+    const int tid = threadIdx.x, C = v.C, H = v.H, H4 = 4 * H;
     const int Cp = (C + 3) & ~3, Hp = (H + 3) & ~3;        // the padded input counts the weight copies were built for
-    const int s0 = blockIdx.x * SW;
     // the (stream, unit) this thread owns in the cell updates
-    const int cs = tid / H, cu = tid - cs * H;
+    const int cs = SW == 1 ? 0 : tid / H, cu = tid - cs * H;
     const bool cell = tid < SW * H && s0 + cs < S;
     float c0 = 0.f, c1 = 0.f;
     for (int k = tid; k < 2 * VAD_MAXH * SW; k += VAD_THREADS) reinterpret_cast<float *>(hs)[k] = 0.f;
     for (int k = tid; k < VAD_TP * VAD_MAXH * SW; k += VAD_THREADS) reinterpret_cast<float *>(h0s)[k] = 0.f;
     for (int k = tid; k < VAD_TP * VAD_MAXC * SW; k += VAD_THREADS) reinterpret_cast<float *>(xin)[k] = 0.f;
     __syncthreads();
-    if (cell) {
+    if (CARRY && cell) {
         const size_t o = (size_t)(s0 + cs) * H + cu;
         reinterpret_cast<float *>(&hs[0][cu])[cs] = v.h[o];
         reinterpret_cast<float *>(&hs[1][cu])[cs] = v.h[(size_t)S * H + o];
@@ -66,8 +70,8 @@ vad_lstm_kernel(DssVadDev v, const FrameT *__restrict__ frames, int W, int *__re
 #pragma unroll
                 for (int s = 0; s < SW; ++s) pre[tt][s] = 0.f;
             if (rowt) {                                    // (frames beyond nst: stale inputs, never used)
-                if (layer == 0) vad_dot_steps<SW, V, VAD_MAXC>(pre, v.wT0, H4, tid, xin, Cp);
-                else vad_dot_steps<SW, V, VAD_MAXH>(pre, v.wT1, H4, tid, h0s, Hp);
+                if (layer == 0) lstm_dot_steps<SW, V, VAD_MAXC, VAD_TP>(pre, v.wT0, H4, tid, xin, Cp);
+                else lstm_dot_steps<SW, V, VAD_MAXH, VAD_TP>(pre, v.wT1, H4, tid, h0s, Hp);
             }
 #pragma unroll
             for (int tt = 0; tt < VAD_TP; ++tt) {
@@ -75,28 +79,27 @@ vad_lstm_kernel(DssVadDev v, const FrameT *__restrict__ frames, int W, int *__re
                 // ---- gate pre-activations of this layer and frame: W_ih x + W_hh h + (b_ih + b_hh)
                 if (rowt) {
                     V acc = pre[tt];
-                    if (layer == 0) vad_dot<SW, V>(acc, v.wT0 + (size_t)Cp * H4, H4, tid, hs[0], Hp);
-                    else vad_dot<SW, V>(acc, v.wT1 + (size_t)Hp * H4, H4, tid, hs[1], Hp);
+                    if (layer == 0) lstm_dot<SW, V>(acc, v.wT0 + (size_t)Cp * H4, H4, tid, hs[0], Hp);
+                    else lstm_dot<SW, V>(acc, v.wT1 + (size_t)Hp * H4, H4, tid, hs[1], Hp);
 #pragma unroll
                     for (int s = 0; s < SW; ++s) acc[s] += layer == 0 ? bias0 : bias1;
                     gates[tid] = acc;
                 }
                 __syncthreads();
-                // ---- cell update of (stream cs, unit cu): c' = f c + i g, h' = o tanh(c')
+                // ---- cell update of (stream cs, unit cu)
                 if (tid < SW * H) {
-                    const float gi = reinterpret_cast<const float *>(&gates[cu])[cs];
-                    const float gf = reinterpret_cast<const float *>(&gates[H + cu])[cs];
-                    const float gg = reinterpret_cast<const float *>(&gates[2 * H + cu])[cs];
-                    const float go = reinterpret_cast<const float *>(&gates[3 * H + cu])[cs];
-                    float &c = layer == 0 ? c0 : c1;
-                    c = vad_sigmoid(gf) * c + vad_sigmoid(gi) * tanhf(gg);
-                    const float h = vad_sigmoid(go) * tanhf(c);
+                    float gi = reinterpret_cast<const float *>(&gates[cu])[cs];
+                    float gf = reinterpret_cast<const float *>(&gates[H + cu])[cs];
+                    float gg = reinterpret_cast<const float *>(&gates[2 * H + cu])[cs];
+                    float go = reinterpret_cast<const float *>(&gates[3 * H + cu])[cs];
+                    const float h = lstm_cell(gi, gf, gg, go, layer == 0 ? c0 : c1);
                     reinterpret_cast<float *>(&hs[layer][cu])[cs] = h;
                     if (layer == 0) reinterpret_cast<float *>(&h0s[tt][cu])[cs] = h;
                 }
                 __syncthreads();
                 if (layer == 1) {
-                    // ---- classifier (models.py:20,32) and the raw label (units.py:434: argmax, the first maximum wins)
+                    // ---- classifier (models.py:20,32) and the raw label (units.py:434: argmax, the first maximum wins: equal
+                    // logits are non-speech)
                     const int w = w0 + tt;
                     if (tid < SW * 2) {
                         const int sl = tid >> 1, cls = tid & 1;
@@ -112,13 +115,21 @@ vad_lstm_kernel(DssVadDev v, const FrameT *__restrict__ frames, int W, int *__re
             }
         }
     }
-    if (cell) {
+    if (CARRY && cell) {
         const size_t o = (size_t)(s0 + cs) * H + cu;
         v.h[o] = reinterpret_cast<const float *>(&hs[0][cu])[cs];
         v.h[(size_t)S * H + o] = reinterpret_cast<const float *>(&hs[1][cu])[cs];
         v.c[o] = c0;
         v.c[(size_t)S * H + o] = c1;
     }
+}
+
+// S streams advanced in lock-step by W frames from the handle's carried state: a workgroup owns SW of them.
+template <typename FrameT, int SW>
+__global__ void __launch_bounds__(VAD_THREADS)
+vad_lstm_kernel(DssVadDev v, const FrameT *__restrict__ frames, int W, int *__restrict__ labels, float *__restrict__ logits)
+{
+    vad_forward_body<FrameT, SW, true>(v, frames, W, labels, logits, blockIdx.x * SW, v.S);
 }
 
 int dss_launch_vad(const DssVadDev &v, const void *d_frames, int frames_f64, int W, int *d_labels, float *d_logits, hipStream_t st)
@@ -139,88 +150,21 @@ int dss_launch_vad(const DssVadDev &v, const void *d_frames, int frames_f64, int
 
 // ---- a trial list in one launch (dss_vad_forward_trials_dev; the reference's validation pass, train_unidirectional_vad.py:181-215) ----
 // Trial k is rows in_row .. in_row + len of one (N, C) array and starts from the zero state of both layers; its labels and logits go
-// to rows out_row .. of the concatenated outputs.  One workgroup per trial, one stream wide (SW = 1): the arithmetic of a trial is,
-// term for term, what vad_lstm_kernel<FrameT, 1> does for the only stream of a one-stream handle stepped through all len frames in
-// one call -- the same vad_dot / vad_dot_steps chains per gate row, the same cell update, the same classifier loop -- so the
-// results are the same bits.  The table comes sorted longest trial first: workgroups are dispatched in index order, so the long
-// trials start first and the short ones fill the CUs they leave (a trial is a serial chain of len steps; nothing else balances
-// it).  The handle's persistent (h, c) are not touched: h lives in LDS and c in registers for the length of the trial.
+// to rows out_row .. of the concatenated outputs.  One workgroup per trial, one stream wide: vad_forward_body<FrameT, 1> for the
+// only stream of a call of len frames, so a trial's results are the bits vad_lstm_kernel<FrameT, 1> gives a one-stream handle
+// stepped through all len frames in one call.  The table comes sorted longest trial first: workgroups are dispatched in index
+// order, so the long trials start first and the short ones fill the CUs they leave (a trial is a serial chain of len steps;
+// nothing else balances it).  The handle's persistent (h, c) are not touched: h lives in LDS and c in registers for the length of
+// the trial.
 
 template <typename FrameT>
 __global__ void __launch_bounds__(VAD_THREADS, 5)         // 5 waves per SIMD = two trials per CU: one hides the other's L2 and barrier waits
 vad_trials_kernel(DssVadDev v, const FrameT *__restrict__ frames, const DssVadTrialDesc *__restrict__ desc, int *__restrict__ labels,
                   float *__restrict__ logits)
 {
-    typedef typename VadVec<1>::type V;
-    __shared__ __attribute__((aligned(16))) V xin[VAD_TP][VAD_MAXC];
-    __shared__ __attribute__((aligned(16))) V h0s[VAD_TP][VAD_MAXH];
-    __shared__ __attribute__((aligned(16))) V hs[2][VAD_MAXH];
-    __shared__ __attribute__((aligned(16))) V gates[4 * VAD_MAXH];
-    __shared__ float lg[2];
     const DssVadTrialDesc d = desc[blockIdx.x];
-    const int tid = threadIdx.x, C = v.C, H = v.H, H4 = 4 * H, W = d.len;
-    const int Cp = (C + 3) & ~3, Hp = (H + 3) & ~3;
-    const FrameT *x = frames + (size_t)d.in_row * C;
-    int *lab = labels + d.out_row;
-    float *lgo = logits ? logits + (size_t)d.out_row * 2 : nullptr;
-    float c0 = 0.f, c1 = 0.f;                              // create_new_initial_state: zeros (models.py:22-24)
-    for (int k = tid; k < 2 * VAD_MAXH; k += VAD_THREADS) reinterpret_cast<float *>(hs)[k] = 0.f;
-    for (int k = tid; k < VAD_TP * VAD_MAXH; k += VAD_THREADS) reinterpret_cast<float *>(h0s)[k] = 0.f;
-    for (int k = tid; k < VAD_TP * VAD_MAXC; k += VAD_THREADS) reinterpret_cast<float *>(xin)[k] = 0.f;
-    __syncthreads();
-    const bool rowt = tid < H4;
-    const float bias0 = rowt ? v.b0[tid] : 0.f, bias1 = rowt ? v.b1[tid] : 0.f;
-    for (int w0 = 0; w0 < W; w0 += VAD_TP) {
-        const int nst = min(VAD_TP, W - w0);
-        for (int idx = tid; idx < nst * C; idx += VAD_THREADS) {
-            const int tt = idx / C, k = idx - tt * C;
-            xin[tt][k].v = (float)x[(size_t)(w0 + tt) * C + k];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int layer = 0; layer < 2; ++layer) {
-            V pre[VAD_TP];
-#pragma unroll
-            for (int tt = 0; tt < VAD_TP; ++tt) pre[tt].v = 0.f;
-            if (rowt) {
-                if (layer == 0) vad_dot_steps<1, V, VAD_MAXC>(pre, v.wT0, H4, tid, xin, Cp);
-                else vad_dot_steps<1, V, VAD_MAXH>(pre, v.wT1, H4, tid, h0s, Hp);
-            }
-#pragma unroll
-            for (int tt = 0; tt < VAD_TP; ++tt) {
-                if (tt >= nst) break;
-                if (rowt) {
-                    V acc = pre[tt];
-                    if (layer == 0) vad_dot<1, V>(acc, v.wT0 + (size_t)Cp * H4, H4, tid, hs[0], Hp);
-                    else vad_dot<1, V>(acc, v.wT1 + (size_t)Hp * H4, H4, tid, hs[1], Hp);
-                    acc.v += layer == 0 ? bias0 : bias1;
-                    gates[tid] = acc;
-                }
-                __syncthreads();
-                if (tid < H) {
-                    const float gi = gates[tid].v, gf = gates[H + tid].v, gg = gates[2 * H + tid].v, go = gates[3 * H + tid].v;
-                    float &c = layer == 0 ? c0 : c1;
-                    c = vad_sigmoid(gf) * c + vad_sigmoid(gi) * tanhf(gg);
-                    const float h = vad_sigmoid(go) * tanhf(c);
-                    hs[layer][tid].v = h;
-                    if (layer == 0) h0s[tt][tid].v = h;
-                }
-                __syncthreads();
-                if (layer == 1) {
-                    const int w = w0 + tt;
-                    if (tid < 2) {
-                        float a = 0.f;
-                        for (int k = 0; k < H; ++k) a = __builtin_fmaf(v.wc[tid * H + k], hs[1][k].v, a);
-                        a += v.bc[tid];
-                        lg[tid] = a;
-                        if (lgo) lgo[(size_t)w * 2 + tid] = a;
-                    }
-                    __syncthreads();
-                    if (tid == 0) lab[w] = lg[1] > lg[0] ? 1 : 0;      // the step kernel's tie rule: equal logits are non-speech
-                }
-            }
-        }
-    }
+    vad_forward_body<FrameT, 1, false>(v, frames + (size_t)d.in_row * v.C, d.len, labels + d.out_row,
+                                       logits ? logits + (size_t)d.out_row * 2 : nullptr, 0, 1);
 }
 
 int dss_launch_vad_trials(const DssVadDev &v, const void *d_frames, int frames_f64, const DssVadTrialDesc *desc, int n_trials, int *d_labels,

@@ -9,8 +9,8 @@
 //   nn.LSTM(dropout = p), train mode      layer 0's output, as layer 1 reads it, times a mask of 0 or 1 / (1 - p); the mask is an
 //                                         INPUT here, (T, H) multipliers or NULL -- the kernels hold no generator
 // Two launches per window ("Training the detector"):
-//   vad_train_window_kernel  one workgroup of 640 threads, everything that is serial in time: the forward pass (the chains of
-//                            vad_lstm.hip's kernels, vad_lstm_dot.h) with the stash the backward pass needs, the loss, dlogits,
+//   vad_train_window_kernel  one workgroup of 640 threads, everything that is serial in time: the forward pass (lstm_blocks.h: the
+//                            blocks of vad_lstm.hip's forward body) with the stash the backward pass needs, the loss, dlogits,
 //                            and backward through time for layer 1, then layer 0 -- the gate gradients dG1[T][4H], dG0[T][4H]
 //   vad_train_step_kernel    one workgroup per gate row (and per class of the head): the weight gradients dG^T . inputs as sums
 //                            over t in frame order, the bias gradients, and, fused, the RMSprop update of the master parameters
@@ -23,8 +23,7 @@
 // The arithmetic is stated once, so a model's bits do not depend on which of the two ran it.  Every pointer read from the
 // descriptor goes through dss_gp (dss_global_ptr.h): the group kernels load them from a table, and must still address global
 // memory, not the flat aperture.
-#include "vad_lstm_dot.h"
-#include "dss_global_ptr.h"
+#include "lstm_blocks.h"
 
 // offsets of the ten tensors in the flat parameter array (state_dict order; also of the gradients and the square averages)
 struct VadTrainOff { int wih0, whh0, bih0, bhh0, wih1, whh1, bih1, bhh1, wc, bc, total; };
@@ -113,7 +112,7 @@ __device__ __forceinline__ void vad_train_window_body(const DssVadTrainDev &d, c
                                                       const unsigned char *__restrict__ targets, const float *__restrict__ mask,
                                                       double *__restrict__ loss)
 {
-    typedef typename VadVec<1>::type V;
+    typedef typename LstmVec<1>::type V;
     __shared__ __attribute__((aligned(16))) V xin[VAD_TP][VAD_MAXC];
     __shared__ __attribute__((aligned(16))) V h0s[VAD_TP][VAD_MAXH];      // layer 0's MASKED h of the chunk's frames (layer 1's inputs)
     __shared__ __attribute__((aligned(16))) V hs[2][VAD_MAXH];            // the h each layer carries to its own next step (never masked)
@@ -134,7 +133,7 @@ __device__ __forceinline__ void vad_train_window_body(const DssVadTrainDev &d, c
     double *lossf = dss_gp(d.lossf);
     const float *dg1 = dss_gp(d.dg1);
 
-    // ---- forward: vad_trials_kernel's chains from the carried state, with the stash ------------------------------------------
+    // ---- forward: vad_forward_body's steps (vad_lstm.hip) for one stream from the carried state, the stash writes between them --
     float c0 = 0.f, c1 = 0.f;
     for (int k = tid; k < 2 * VAD_MAXH; k += VAD_THREADS) reinterpret_cast<float *>(hs)[k] = 0.f;
     for (int k = tid; k < VAD_TP * VAD_MAXH; k += VAD_THREADS) reinterpret_cast<float *>(h0s)[k] = 0.f;
@@ -162,8 +161,8 @@ __device__ __forceinline__ void vad_train_window_body(const DssVadTrainDev &d, c
 #pragma unroll
             for (int tt = 0; tt < VAD_TP; ++tt) pre[tt].v = 0.f;
             if (rowt) {
-                if (layer == 0) vad_dot_steps<1, V, VAD_MAXC>(pre, wT0, H4, tid, xin, Cp);
-                else vad_dot_steps<1, V, VAD_MAXH>(pre, wT1, H4, tid, h0s, Hp);
+                if (layer == 0) lstm_dot_steps<1, V, VAD_MAXC, VAD_TP>(pre, wT0, H4, tid, xin, Cp);
+                else lstm_dot_steps<1, V, VAD_MAXH, VAD_TP>(pre, wT1, H4, tid, h0s, Hp);
             }
 #pragma unroll
             for (int tt = 0; tt < VAD_TP; ++tt) {
@@ -171,18 +170,16 @@ __device__ __forceinline__ void vad_train_window_body(const DssVadTrainDev &d, c
                 const int t = w0 + tt;
                 if (rowt) {
                     V acc = pre[tt];
-                    if (layer == 0) vad_dot<1, V>(acc, wT0 + (size_t)Cp * H4, H4, tid, hs[0], Hp);
-                    else vad_dot<1, V>(acc, wT1 + (size_t)Hp * H4, H4, tid, hs[1], Hp);
+                    if (layer == 0) lstm_dot<1, V>(acc, wT0 + (size_t)Cp * H4, H4, tid, hs[0], Hp);
+                    else lstm_dot<1, V>(acc, wT1 + (size_t)Hp * H4, H4, tid, hs[1], Hp);
                     acc.v += layer == 0 ? bias0 : bias1;
                     gates[tid] = acc;
                 }
                 __syncthreads();
                 if (own) {
-                    const float gi = vad_sigmoid(gates[tid].v), gf = vad_sigmoid(gates[H + tid].v), gg = tanhf(gates[2 * H + tid].v),
-                                go = vad_sigmoid(gates[3 * H + tid].v);
+                    float gi = gates[tid].v, gf = gates[H + tid].v, gg = gates[2 * H + tid].v, go = gates[3 * H + tid].v;
                     float &c = layer == 0 ? c0 : c1;
-                    c = gf * c + gi * gg;
-                    const float h = go * tanhf(c);
+                    const float h = lstm_cell(gi, gf, gg, go, c);
                     hs[layer][tid].v = h;
                     float *a = dss_uniform((layer == 0 ? act0 : act1) + (size_t)t * H4);
                     a[tid] = gi; a[H + tid] = gf; a[2 * H + tid] = gg; a[3 * H + tid] = go;
@@ -240,7 +237,7 @@ __device__ __forceinline__ void vad_train_window_body(const DssVadTrainDev &d, c
             __syncthreads();
             if (j < H) {
                 const float *W = Wih1 + (size_t)q * H * H;
-                vf4 acc = {0.f, 0.f, 0.f, 0.f};
+                f4 acc = {0.f, 0.f, 0.f, 0.f};
                 int r = 0;
                 for (; r + 4 <= H; r += 4) {
                     float w[4];
@@ -248,18 +245,18 @@ __device__ __forceinline__ void vad_train_window_body(const DssVadTrainDev &d, c
                     for (int u = 0; u < 4; ++u) w[u] = W[(size_t)(r + u) * H + j];
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
-                        const vf4 g = *reinterpret_cast<const vf4 *>(dg4[q * H + r + u]);
+                        const f4 g = *reinterpret_cast<const f4 *>(dg4[q * H + r + u]);
                         acc.x = __builtin_fmaf(w[u], g.x, acc.x); acc.y = __builtin_fmaf(w[u], g.y, acc.y);
                         acc.z = __builtin_fmaf(w[u], g.z, acc.z); acc.w = __builtin_fmaf(w[u], g.w, acc.w);
                     }
                 }
                 for (; r < H; ++r) {
                     const float w = W[(size_t)r * H + j];
-                    const vf4 g = *reinterpret_cast<const vf4 *>(dg4[q * H + r]);
+                    const f4 g = *reinterpret_cast<const f4 *>(dg4[q * H + r]);
                     acc.x = __builtin_fmaf(w, g.x, acc.x); acc.y = __builtin_fmaf(w, g.y, acc.y);
                     acc.z = __builtin_fmaf(w, g.z, acc.z); acc.w = __builtin_fmaf(w, g.w, acc.w);
                 }
-                *reinterpret_cast<vf4 *>(part4[q][j]) = acc;
+                *reinterpret_cast<f4 *>(part4[q][j]) = acc;
             }
             __syncthreads();
             if (own) {
@@ -294,79 +291,29 @@ vad_train_window_kernel(DssVadTrainDev d, const FrameT *__restrict__ frames, int
 // square average; the packed bias is their float32 sum.
 #define VTS_THREADS 256
 
-__device__ __forceinline__ float vad_rmsprop(const DssVadTrainDev &d, int k, float g, int apply, double lr, double alpha, double eps)
-{
-    float *dp = dss_gp(d.p), *dsq = dss_gp(d.sq);
-    dss_gp(d.g)[k] = g;
-    if (!apply) return dp[k];
-    const float sq = (float)(alpha * (double)dsq[k] + (1.0 - alpha) * ((double)g * (double)g));
-    dsq[k] = sq;
-    const float p = (float)((double)dp[k] - lr * (double)g / (sqrt((double)sq) + eps));
-    dp[k] = p;
-    return p;
-}
-
 __device__ __forceinline__ void vad_train_step_body(const DssVadTrainDev &d, const int b, const int T, const int apply, const double lr,
                                                     const double alpha, const double eps)
 {
-    __shared__ float dgt[VTS_THREADS];
-    const int tid = threadIdx.x, C = d.v.C, H = d.v.H, H4 = 4 * H;
-    const int Cp = (C + 3) & ~3, Hp = (H + 3) & ~3;
+    const int C = d.v.C, H = d.v.H, H4 = 4 * H;
     const VadTrainOff o = vad_train_off(C, H);
     const bool head = b >= 2 * H4;
     const int L = head ? 2 : b / H4, r = head ? b - 2 * H4 : b - L * H4;
-    const float *dg = dss_gp(head ? d.dl : (L ? d.dg1 : d.dg0)) + r;
-    const int dgs = head ? 2 : H4;
-    const float *inA = dss_gp(head ? d.h1 + H : (L ? d.h0m : d.xs)), *inB = dss_gp(L ? d.h1 : d.h0);
-    const int nA = head || L ? H : C, nB = head ? 0 : H, ncol = nA + nB + 1;
-    // two columns per thread: ncol <= 128 + 160 + 1
-    const float *src[2];
-    int stride[2], col[2];
-    bool live[2], bias[2];
-    float acc[2] = {0.f, 0.f};
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        col[u] = tid + u * VTS_THREADS;
-        live[u] = col[u] < ncol;
-        bias[u] = col[u] == ncol - 1;
-        const bool a = col[u] < nA;
-        src[u] = a ? inA + col[u] : inB + (col[u] - nA);
-        stride[u] = a ? nA : H;
-        if (!live[u] || bias[u]) { src[u] = inA; stride[u] = 0; }
-    }
-    for (int t0 = 0; t0 < T; t0 += VTS_THREADS) {
-        const int n = min(VTS_THREADS, T - t0);
-        if (tid < n) dgt[tid] = dg[(size_t)(t0 + tid) * dgs];
-        __syncthreads();
-        for (int tt = 0; tt < n; ++tt) {
-            const float g = dgt[tt];
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const float x = bias[u] ? 1.f : dss_gp(src[u])[(size_t)(t0 + tt) * stride[u]];
-                acc[u] = __builtin_fmaf(g, x, acc[u]);
-            }
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        if (!live[u]) continue;
-        const int k = col[u];
-        if (head) {
-            vad_rmsprop(d, bias[u] ? o.bc + r : o.wc + r * H + k, acc[u], apply, lr, alpha, eps);
-        } else if (bias[u]) {
-            const float bi = vad_rmsprop(d, (L ? o.bih1 : o.bih0) + r, acc[u], apply, lr, alpha, eps);
-            const float bh = vad_rmsprop(d, (L ? o.bhh1 : o.bhh0) + r, acc[u], apply, lr, alpha, eps);
-            if (apply) dss_gp(L ? d.b1 : d.b0)[r] = bi + bh;
-        } else {
-            const bool a = k < nA;
-            const int pk = a ? (L ? o.wih1 : o.wih0) + r * nA + k : (L ? o.whh1 : o.whh0) + r * H + (k - nA);
-            const float p = vad_rmsprop(d, pk, acc[u], apply, lr, alpha, eps);
-            // the packed copy: [inputs / 4][4H rows][4 consecutive inputs], W_hh behind W_ih's padded inputs
-            const int ki = a ? k : (L ? Hp : Cp) + (k - nA);
-            if (apply) dss_gp(L ? d.wT1 : d.wT0)[((size_t)(ki >> 2) * H4 + r) * 4 + (ki & 3)] = p;
-        }
-    }
+    LstmStepRow w;
+    w.dg = dss_gp(head ? d.dl : (L ? d.dg1 : d.dg0)) + r;
+    w.dgs = head ? 2 : H4;
+    w.inA = dss_gp(head ? d.h1 + H : (L ? d.h0m : d.xs));
+    w.nA = head || L ? H : C;              // (two columns per thread: at most 128 + 160 + 1 columns)
+    w.inB = dss_gp(L ? d.h1 : d.h0);
+    w.nB = head ? 0 : H;
+    w.strideB = H;
+    w.o_A = (head ? o.wc : (L ? o.wih1 : o.wih0)) + r * w.nA;
+    w.o_B = (L ? o.whh1 : o.whh0) + r * H;
+    w.o_bias = head ? o.bc + r : (L ? o.bih1 : o.bih0) + r;
+    w.o_bias2 = (L ? o.bhh1 : o.bhh0) + r;
+    w.wpk = head ? nullptr : dss_gp(L ? d.wT1 : d.wT0);
+    w.bpk = dss_gp(L ? d.b1 : d.b0) + r;
+    w.r = r; w.H4 = H4; w.kB = (w.nA + 3) & ~3;
+    lstm_train_step_row<VTS_THREADS>(w, dss_gp(d.p), dss_gp(d.sq), dss_gp(d.g), T, apply, lr, alpha, eps);
 }
 
 __global__ void __launch_bounds__(VTS_THREADS)

@@ -153,7 +153,7 @@ def _define(header, name):
 
 
 def test_the_restated_constants_are_the_kernels():
-    assert TC.DEC_THREADS == _define("dec_lstm_dot.h", "DEC_THREADS") and TC.VAD_THREADS == _define("vad_lstm_dot.h", "VAD_THREADS")
+    assert TC.DEC_THREADS == _define("lstm_blocks.h", "DEC_THREADS") and TC.VAD_THREADS == _define("lstm_blocks.h", "VAD_THREADS")
     assert TC.STEP_TILE == _define("dec_train.hip", "DTS_THREADS") == _define("vad_train.hip", "VTS_THREADS")
     assert TC.FRAME_TILE == _define("dec_train.hip", "DTH_ROWS") == _define("dec_train.hip", "DTM_FR")
     assert TC.DEC_MAXO == _define("dss_common.h", "DSS_DEC_MAXO")

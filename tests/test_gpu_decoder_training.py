@@ -139,7 +139,7 @@ def test_the_same_trial_twice_gives_the_same_bits(T, H, C, n):
 @pytest.mark.parametrize("case", D.GRAD_CASES, ids=str)
 def test_forward_half_is_the_inference_kernel(T, case):
     """Without a mask the features of the trainer's forward pass are the bits of BiLstmDecoderGPU.forward_torch on the same weights
-    and frames: both run dec_lstm_dot.h's dot products, the same recurrent half, cell update and head, term for term."""
+    and frames: both run lstm_blocks.h's dot products, recurrent half and cell update, and the same head, term for term."""
     import torch
     from dss_amd.decoder import BiLstmDecoderGPU
     sd, x, y, _ = D.case_inputs(case, None)
