@@ -330,22 +330,19 @@ static inline DssHgaRing dss_hga_ring(int frame_length, int overlap)
     r.fused = r.bytes <= DSS_HGA_RING_LIMIT;
     return r;
 }
-// the front end of a call (local/common.py:16-58,308-345): raw amplifier rows (S, n, c_raw) instead of (S, n, C)
-struct DssHgaFrontDev {
-    const double *raw;
-    int c_raw, n_grids;
-    const int *src_col, *grid_of, *comp_cols, *comp_off;
-};
-// d_data is (S, n, C); fe must be nullptr (raw amplifier rows go through dss_launch_hga_frontend first)
-int dss_launch_hga(const DssHgaDev &h, const double *d_data, const DssHgaFrontDev *fe, int n, int row0, int zero_rows, int rows,
-                   int W, double *d_out, int apply_log, hipStream_t s);
+// d_data is (S, n, C)
+int dss_launch_hga(const DssHgaDev &h, const double *d_data, int n, int row0, int zero_rows, int rows, int W, double *d_out,
+                   int apply_log, hipStream_t s);
 int dss_launch_hga_frontend(const double *d_raw, double *d_pre, int S, int n, int c_raw, int C, const int *src_col,
                             const int *grid_of, int n_grids, const int *comp_cols, const int *comp_off, hipStream_t s);
 int dss_launch_hga_wire(const float *d_payload, double *d_rows, int S, int C, int n, hipStream_t s);
 int dss_launch_hga_reset(const DssHgaDev &h, const double *d_zi_hg, const double *d_zi_fh, hipStream_t s);
 // one launch for n_trials fresh-extractor trials that are row ranges of one (rows, C) device array; d_desc is the device copy of
-// the descriptor table {int64 in_row, out_row; int32 n, W, zero_rows, pad} (csrc/hga_kernels.hip, HgaTrialDesc)
-int dss_launch_hga_trials(const DssHgaDev &h, const double *d_data, const void *d_desc, int n_trials, const double *d_zi_hg,
+// the descriptor table: trial i reads rows in_row .. in_row + n - 1, left-padded with zero_rows rows of zeros, and writes frames
+// out_row .. out_row + W - 1
+struct DssHgaTrialDesc { long long in_row, out_row; int n, W, zero_rows, pad; };
+static_assert(sizeof(DssHgaTrialDesc) == 32, "the descriptor table is copied to the device as it stands");
+int dss_launch_hga_trials(const DssHgaDev &h, const double *d_data, const DssHgaTrialDesc *d_desc, int n_trials, const double *d_zi_hg,
                           const double *d_zi_fh, double *d_out, int apply_log, int with_zscore, hipStream_t s);
 // in place on (N, C) frames: the bad-channel patch (n_patches may be 0; d_single_rows: the frames of trials that emit one
 // frame, which numpy sums as a contiguous row), then the z-score when zs_mean is not NULL

@@ -64,8 +64,6 @@ extern "C" int dss_hga_plan(int fs, float window_length, float window_shift, int
     return DSS_OK;
 }
 
-struct DssHgaTrialDesc { long long in_row, out_row; int n, W, zero_rows, pad; };       // HgaTrialDesc of csrc/hga_kernels.hip
-
 struct dss_hga {
     int device;
     DssHgaDev d;
@@ -86,7 +84,7 @@ struct dss_hga {
     std::vector<int> patch_dst, patch_cols, patch_off;     // empty = no patch
     int *d_patch_dst = nullptr, *d_patch_cols = nullptr, *d_patch_off = nullptr;
     std::vector<DssHgaTrialDesc> desc;
-    void *d_desc = nullptr;
+    DssHgaTrialDesc *d_desc = nullptr;
     std::vector<long long> single_rows;                    // output frames of the trials that emit one frame
     long long *d_single = nullptr;
     double *d_trec = nullptr, *d_tout = nullptr;
@@ -177,8 +175,8 @@ extern "C" int dss_hga_frames_for(const dss_hga *h, int n)
     return W < 0 ? 0 : W;
 }
 
-// one call of the extractor on device-resident input: (S, n, C) rows, or with `fe` the raw amplifier rows
-static int hga_run(dss_hga *h, const double *d_data, const DssHgaFrontDev *fe, int n, double *d_out, int apply_log, hipStream_t s)
+// one call of the extractor on device-resident input: (S, n, C) rows
+static int hga_run(dss_hga *h, const double *d_data, int n, double *d_out, int apply_log, hipStream_t s)
 {
     int row0, zr, rows;
     hga_plan(h, n, &row0, &zr, &rows);
@@ -186,7 +184,7 @@ static int hga_run(dss_hga *h, const double *d_data, const DssHgaFrontDev *fe, i
     if (rc) return rc;
     int W = dss_hga_num_windows(rows, h->d.fs, h->d.wl, h->d.ws);
     if (W < 0) W = 0;
-    rc = dss_launch_hga(h->d, d_data, fe, n, row0, zr, rows, W, d_out, apply_log, s);
+    rc = dss_launch_hga(h->d, d_data, n, row0, zr, rows, W, d_out, apply_log, s);
     if (rc) return rc;
     h->first_frame = 0;
     return W;
@@ -196,7 +194,7 @@ extern "C" int dss_hga_extract_dev(dss_hga *h, const double *d_data, int n, doub
 {
     if (!h || !d_data || !d_out || n <= 0) { dss_set_error("bad arguments"); return DSS_EINVAL; }
     DSS_HIP_CHECK(hipSetDevice(h->device));
-    return hga_run(h, d_data, nullptr, n, d_out, apply_log, (hipStream_t)hip_stream);
+    return hga_run(h, d_data, n, d_out, apply_log, (hipStream_t)hip_stream);
 }
 
 /* Optional z-score of the frames, (x - mean[c]) / std[c] (ZScoreNormalization, local/common.py:367-376; the last step of
@@ -563,18 +561,14 @@ static int hga_trials_run(dss_hga *h, const double *d_rows, long long row_base, 
         t.zero_rows = len[i] >= d.frame_length ? 0 : d.frame_length - len[i];
         t.pad = 0;
     }
-    {
-        DssHgaTrialDesc *dd = static_cast<DssHgaTrialDesc *>(h->d_desc);
-        int rc = h->blocks.grow(&dd, &h->desc_cap, (size_t)n_trials);
-        h->d_desc = dd;
-        if (rc) return rc;
-    }
+    int rc = h->blocks.grow(&h->d_desc, &h->desc_cap, (size_t)n_trials);
+    if (rc) return rc;
     DSS_HIP_CHECK(hipMemcpyAsync(h->d_desc, h->desc.data(), sizeof(DssHgaTrialDesc) * (size_t)n_trials, hipMemcpyHostToDevice, st));
     const bool patched = finish && !h->patch_dst.empty();
     const bool zs = finish && d.zs_mean;
     // the patch stands between the log and the z-score (prepare_corpus.py:166-170), so with patches the z-score leaves the
     // trial kernel's epilogue and follows the patch kernel
-    int rc = dss_launch_hga_trials(d, d_data, h->d_desc, n_trials, h->d_zi0[0], h->d_zi0[1], d_out, finish ? apply_log : 0,
+    rc = dss_launch_hga_trials(d, d_data, h->d_desc, n_trials, h->d_zi0[0], h->d_zi0[1], d_out, finish ? apply_log : 0,
                                    zs && !patched, st);
     if (rc) return rc;
     if (patched) {

@@ -33,16 +33,62 @@ __device__ __forceinline__ int hga_win_stop(int start, float wl, int sr)
     return (int)round((double)(start + wl * sr));
 }
 
+// pyx:45-46 and local/common.py:367-376: a window's mean power over its rows, + 0.01, the log, ZScoreNormalization of channel c
+__device__ __forceinline__ double hga_finish(double sum, int rows, int apply_log, const double *__restrict__ zs_mean,
+                                             const double *__restrict__ zs_std, int c)
+{
+    const double pw = sum / (double)rows + 0.01;
+    double o = apply_log ? log(pw) : pw;
+    if (zs_mean) o = (o - zs_mean[c]) / zs_std[c];
+    return o;
+}
+
 // ---- stage 1: the two IIR cascades, pipelined over their sections --------------------------------------------
 // The 2*nsec (<= 16) second-order sections of one (stream, channel) column occupy the 16 lanes of one DPP row: at
 // step k lane r filters sample k - r, taking its input from lane r-1's output of the previous step (row_shr:1), so
 // the column advances one sample per step instead of one per 16 biquads.  Each section's arithmetic is exactly
-// scipy's sosfilt inner loop (one product, one sum at a time).  A 256-thread block handles 16 consecutive columns
-// (same stream, consecutive channels), whose input samples are staged through LDS in tiles of HGA_TT rows with
-// 128-byte row segments; lane 2*nsec-1 writes the filtered sample to the column's row buffer at row0 + t.
+// scipy's sosfilt inner loop (one product, one sum at a time).  A 256-thread block handles 16 consecutive columns,
+// whose input samples are staged through LDS in tiles of HGA_TT rows with 128-byte row segments (xs, one row per step);
+// lane 2*nsec-1 leaves the filtered sample of step k, sample k - (2*nsec-1), in ys.  Thread tid is section lane tid & 15
+// of column tid >> 4 while it filters, and moves column tid & 15 whenever the block copies rows (16 * 8 bytes side by side).
 #define HGA_TT 64
-#define HGA_WTAB 256          // windows whose row ranges the fused kernel tabulates in LDS (2 KB)
 static_assert(HGA_TT == DSS_HGA_TT, "the ring of dss_hga_ring (dss_common.h) is sized for this tile");
+
+// a thread as one lane of the section pipeline: where it sits, the section it holds and that section's state
+struct HgaLane {
+    int r, pib;                // section lane in the DPP row, column in the block
+    int nsec2, f, q;           // sections of both cascades; this lane's cascade and section within it (0, 0 without one)
+    bool has_sec, is_last;
+    double b0, b1, b2, a1, a2;
+    double z0, z1, y;
+};
+
+// before the kernel's first barrier: the lane's place, and the section coefficients by lane into coef (a kernel argument
+// cannot be indexed per lane).  The kernel loads z0 / z1 from wherever its state lives.
+__device__ __forceinline__ HgaLane hga_lane_setup(const HgaSos &sos, int nsec, double (*coef)[5])
+{
+    HgaLane l;
+    const int tid = threadIdx.x;
+    l.r = tid & 15;
+    l.pib = tid >> 4;
+    l.nsec2 = 2 * nsec;
+    l.has_sec = l.r < l.nsec2;
+    l.is_last = l.r == l.nsec2 - 1;
+    l.f = l.has_sec ? l.r / nsec : 0;
+    l.q = l.has_sec ? l.r - l.f * nsec : 0;
+    if (tid < 16) {
+        const int ff = tid < l.nsec2 ? tid / nsec : 0, qq = tid < l.nsec2 ? tid - ff * nsec : 0;
+        coef[tid][0] = sos.k[ff][qq][0]; coef[tid][1] = sos.k[ff][qq][1]; coef[tid][2] = sos.k[ff][qq][2];
+        coef[tid][3] = sos.k[ff][qq][4]; coef[tid][4] = sos.k[ff][qq][5];
+    }
+    l.y = 0.0;
+    return l;
+}
+// behind that barrier
+__device__ __forceinline__ void hga_lane_coef(HgaLane &l, const double (*coef)[5])
+{
+    l.b0 = coef[l.r][0]; l.b1 = coef[l.r][1]; l.b2 = coef[l.r][2]; l.a1 = coef[l.r][3]; l.a2 = coef[l.r][4];
+}
 
 // lanes 1..15 of every row receive their left neighbour's `y`; lane 0 (no neighbour) keeps `x`: the column's input
 __device__ __forceinline__ double hga_shift_in(double x, double y)
@@ -54,52 +100,84 @@ __device__ __forceinline__ double hga_shift_in(double x, double y)
 }
 
 // one step of one section: scipy _sosfilt's inner statement order
-#define HGA_BIQUAD(IN)                                                                           \
-    {                                                                                            \
-        y = b0 * (IN) + z0;                        /* x_c = b0*x_n + zi0        */               \
-        z0 = b1 * (IN) - a1 * y + z1;              /* zi0 = b1*x_n - a1*x_c + zi1 */             \
-        z1 = b2 * (IN) - a2 * y;                   /* zi1 = b2*x_n - a2*x_c     */               \
+__device__ __forceinline__ void hga_biquad(HgaLane &l, double in)
+{
+    l.y = l.b0 * in + l.z0;                        // x_c = b0*x_n + zi0
+    l.z0 = l.b1 * in - l.a1 * l.y + l.z1;          // zi0 = b1*x_n - a1*x_c + zi1
+    l.z1 = l.b2 * in - l.a2 * l.y;                 // zi1 = b2*x_n - a2*x_c
+}
+
+// a step on which some lanes have no sample yet (pipeline filling) or no more (draining): predicated
+__device__ __forceinline__ void hga_edge_step(HgaLane &l, const double (*xs)[16], double (*ys)[16], int k, int base, int n)
+{
+    const double in = hga_shift_in(xs[k - base][l.pib], l.y);
+    const int t = k - l.r;
+    if (l.has_sec && t >= 0 && t < n) {
+        hga_biquad(l, in);
+        if (l.is_last) ys[k - base][l.pib] = l.y;
     }
+}
+
+// steps base .. kend - 1 of a column of n samples, over the tile staged in xs
+__device__ __forceinline__ void hga_tile_steps(HgaLane &l, const double (*xs)[16], double (*ys)[16], int base, int kend, int n)
+{
+    int k = base;
+    for (; k < kend && (k < l.nsec2 - 1 || k >= n); ++k) hga_edge_step(l, xs, ys, k, base, n);
+    // steady state: every section has a sample
+    const int ksteady = min(kend, n);
+    {
+        const double *xp = &xs[k - base][l.pib];
+        double xcur = *xp;
+        // four steps per trip with constant LDS offsets (a DPP move is convergent: the compiler will not unroll a loop of
+        // unknown length around it): per step 9 fp64 operations, 2 DPP moves, one LDS read, one LDS write.  The next
+        // step's input is read a step ahead: its LDS latency hides under this step.
+        double *const yl = &ys[k - base][l.pib];
+        int kk = 0;
+        for (; k + 4 <= ksteady; k += 4, kk += 4) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const double xnext = xp[16 * (kk + u + 1)];
+                hga_biquad(l, hga_shift_in(xcur, l.y));
+                if (l.is_last) yl[16 * (kk + u)] = l.y;
+                xcur = xnext;
+            }
+        }
+        for (; k < ksteady; ++k, ++kk) {
+            const double xnext = xp[16 * (kk + 1)];
+            hga_biquad(l, hga_shift_in(xcur, l.y));
+            if (l.is_last) yl[16 * kk] = l.y;
+            xcur = xnext;
+        }
+    }
+    for (; k < kend; ++k) hga_edge_step(l, xs, ys, k, base, n);      // draining steps at the end of the last tile(s)
+}
 
 __global__ void __launch_bounds__(256)
 hga_filter_kernel(const double *__restrict__ data, double *__restrict__ zi, double *__restrict__ rowbuf,
                   HgaSos sos, int S, int C, int n, int nsec, int row0, int cap_rows, int zero_rows)
 {
-    __shared__ double xs[HGA_TT + 1][16];      // inputs of the tile's steps, one row segment of 16 columns per step (+1: prefetch)
+    __shared__ double xs[HGA_TT + 1][16];      // inputs of the tile's steps, one row segment of 16 columns per step (+1: read ahead)
     __shared__ double ys[HGA_TT][16];          // outputs produced at the tile's steps (sample k - (2*nsec-1) at step k)
     __shared__ double coef[16][5];
-    __shared__ double dump[256];               // where the lanes that do not hold the last section "store" their y
-    const int tid = threadIdx.x, r = tid & 15, pib = tid >> 4;
+    const int tid = threadIdx.x;
     const long total = (long)S * C;
     const long pair0 = (long)blockIdx.x * 16;
-    long pair = pair0 + pib;
+    HgaLane l = hga_lane_setup(sos, nsec, coef);
+    long pair = pair0 + l.pib;
     const bool valid = pair < total;
     if (!valid) pair = total - 1;
     const int s = (int)(pair / C), c = (int)(pair - (long)s * C);
-    const int nsec2 = 2 * nsec;
-    const bool has_sec = r < nsec2;
-    const bool is_last = r == nsec2 - 1;
-    // branch-free output store of the steady-state loop: the last section's lane walks down its ys column, every other
-    // lane rewrites its own dump word
-    char *const ybase = is_last ? reinterpret_cast<char *>(&ys[0][pib]) : reinterpret_cast<char *>(&dump[tid]);
-    const int ystride = is_last ? 16 * (int)sizeof(double) : 0;
-    const int f = has_sec ? r / nsec : 0, q = has_sec ? r - f * nsec : 0;
-    if (tid < 16) {           // section coefficients by lane (a kernel argument cannot be indexed per lane)
-        const int ff = tid < nsec2 ? tid / nsec : 0, qq = tid < nsec2 ? tid - ff * nsec : 0;
-        coef[tid][0] = sos.k[ff][qq][0]; coef[tid][1] = sos.k[ff][qq][1]; coef[tid][2] = sos.k[ff][qq][2];
-        coef[tid][3] = sos.k[ff][qq][4]; coef[tid][4] = sos.k[ff][qq][5];
-    }
     double *zp = zi + (size_t)s * 2 * 8 * 2 * C + c;
-    double z0 = zp[((f * 8 + q) * 2 + 0) * (size_t)C], z1 = zp[((f * 8 + q) * 2 + 1) * (size_t)C];
+    l.z0 = zp[((l.f * 8 + l.q) * 2 + 0) * (size_t)C];
+    l.z1 = zp[((l.f * 8 + l.q) * 2 + 1) * (size_t)C];
     // CASE 2 of the frame buffer (first chunk shorter than a frame): left zero padding, pyx:116
     if (valid) {
         double *col = rowbuf + (size_t)s * cap_rows * C + c;
-        for (int k = r; k < zero_rows; k += 16) col[(size_t)k * C] = 0.0;
+        for (int k = l.r; k < zero_rows; k += 16) col[(size_t)k * C] = 0.0;
     }
     __syncthreads();
-    const double b0 = coef[r][0], b1 = coef[r][1], b2 = coef[r][2], a1 = coef[r][3], a2 = coef[r][4];
-    const int steps = n + nsec2 - 1;
-    double y = 0.0;
+    hga_lane_coef(l, coef);
+    const int steps = n + l.nsec2 - 1;
     for (int base = 0; base < steps; base += HGA_TT) {
         __syncthreads();                                   // previous tile fully consumed and written out
         for (int idx = tid; idx < HGA_TT * 16; idx += 256) {
@@ -115,66 +193,163 @@ hga_filter_kernel(const double *__restrict__ data, double *__restrict__ zi, doub
         }
         __syncthreads();
         const int kend = min(base + HGA_TT, steps);
-        int k = base;
-        // steps on which some lanes have no sample yet (pipeline filling) or no more (draining): predicated
-        for (; k < kend && (k < nsec2 - 1 || k >= n); ++k) {
-            const double in = hga_shift_in(xs[k - base][pib], y);
-            const int t = k - r;
-            if (has_sec && t >= 0 && t < n) {
-                HGA_BIQUAD(in)
-                if (is_last) ys[k - base][pib] = y;
-            }
-        }
-        // steady state: every section has a sample
-        const int ksteady = min(kend, n);
-        {
-            char *yp = ybase + (k - base) * ystride;
-            const double *xp = &xs[k - base][pib];
-            double xcur = *xp;
-            for (; k < ksteady; ++k) {
-                xp += 16;
-                const double xnext = *xp;                  // next step's input: its LDS latency hides under this step
-                const double in = hga_shift_in(xcur, y);
-                HGA_BIQUAD(in)
-                *reinterpret_cast<double *>(yp) = y;
-                yp += ystride;
-                xcur = xnext;
-            }
-        }
-        for (; k < kend; ++k) {                            // draining steps at the end of the last tile(s)
-            const double in = hga_shift_in(xs[k - base][pib], y);
-            const int t = k - r;
-            if (has_sec && t >= 0 && t < n) {
-                HGA_BIQUAD(in)
-                if (is_last) ys[k - base][pib] = y;
-            }
-        }
+        hga_tile_steps(l, xs, ys, base, kend, n);
         __syncthreads();
         // the tile's finished samples go out as 128-byte row segments
         for (int idx = tid; idx < HGA_TT * 16; idx += 256) {
             const int tt = idx >> 4, p = idx & 15;
             const long pp = pair0 + p;
-            const int t = base + tt - (nsec2 - 1);
+            const int t = base + tt - (l.nsec2 - 1);
             if (base + tt < kend && t >= 0 && t < n && pp < total) {
                 const int sp = (int)(pp / C), cp = (int)(pp - (long)sp * C);
                 rowbuf[((size_t)sp * cap_rows + row0 + t) * C + cp] = ys[tt][p];
             }
         }
     }
-    if (valid && has_sec) {
-        zp[((f * 8 + q) * 2 + 0) * (size_t)C] = z0;
-        zp[((f * 8 + q) * 2 + 1) * (size_t)C] = z1;
+    if (valid && l.has_sec) {
+        zp[((l.f * 8 + l.q) * 2 + 0) * (size_t)C] = l.z0;
+        zp[((l.f * 8 + l.q) * 2 + 1) * (size_t)C] = l.z1;
     }
 }
 
-// ---- fused form: filter tile -> LDS ring -> completed windows -> overlap rows -------------------------------------------
+// ---- one-launch forms: filter tile -> LDS ring -> completed windows ---------------------------------------------------
 // Same block shape and the same per-step code as hga_filter_kernel (16 columns x 16 section lanes).  `ring` holds the last
 // R rows of the block's 16 columns (overlap / zero rows first, then the new samples at row0 + t), row i at position i mod R;
 // R >= frame_length + window shift + TT + 2 so that no row a pending window still needs is overwritten by the next tile.
-// Round 3: R carries no power-of-two padding and the lanes that do not hold the last section have no dummy store targets
-// any more (18 KB of static LDS + 16 KB of ring instead of 37 KB).  (A 32-step-tile instantiation -- 22 KB, 7 blocks per CU
-// instead of 5 -- was no faster at 1024 streams and slower on small calls, profiles/r3_hga_tile_ab_timing.txt, and is gone.)
+// Round 3: R carries no power-of-two padding (18 KB of static LDS + 16 KB of ring instead of 37 KB).  (A 32-step-tile
+// instantiation -- 22 KB, 7 blocks per CU instead of 5 -- was no faster at 1024 streams and slower on small calls,
+// profiles/r3_hga_tile_ab_timing.txt, and is gone.)
 #define HGF_WTAB 128
+
+// the frames a block emits: W windows over its columns, the window rule of pyx:43-44 and the finish
+struct HgaFrames {
+    int W, sr;
+    float wl, ws;
+    int apply_log;
+    const double *zs_mean, *zs_std;
+};
+
+// first and one-past-last row of the first HGF_WTAB windows (the float32 / round() arithmetic once per block instead of
+// once per tile); a window past the table takes its rows from that arithmetic directly
+__device__ __forceinline__ void hga_window_table(int (*wtab)[HGF_WTAB], const HgaFrames &fr)
+{
+    for (int w = threadIdx.x; w < fr.W && w < HGF_WTAB; w += 256) {
+        const int st = hga_win_start(w, fr.ws, fr.sr);
+        wtab[0][w] = st;
+        wtab[1][w] = hga_win_stop(st, fr.wl, fr.sr);
+    }
+}
+__device__ __forceinline__ void hga_window_range(const int (*wtab)[HGF_WTAB], const HgaFrames &fr, int w, int &start, int &stop)
+{
+    if (w < HGF_WTAB) {            // one branch for both: a caller that wants the stop alone then reads one entry, not two in turn
+        start = wtab[0][w];
+        stop = wtab[1][w];
+    } else {
+        start = hga_win_start(w, fr.ws, fr.sr);
+        stop = hga_win_stop(start, fr.wl, fr.sr);
+    }
+}
+
+// Input tiles: thread (tt0, p) owns column p of rows tt0, tt0 + 16, ... of every tile; lcol is its column's sample 0 (null: a
+// column past the edge, zeros).  Samples base + tt0 + 16 j of a column of n, C doubles apart, into registers.
+__device__ __forceinline__ void hga_tile_fetch(double (&pre)[HGA_TT / 16], const double *__restrict__ lcol, int base, int n, int C)
+{
+    const int ltt = threadIdx.x >> 4;
+#pragma unroll
+    for (int j = 0; j < HGA_TT / 16; ++j) {
+        const int t = base + ltt + 16 * j;
+        pre[j] = (lcol && t < n) ? lcol[(size_t)t * C] : 0.0;
+    }
+}
+
+// the tile's finished samples join the ring at their row: the output of step base + tt at position tile_pos + tt (mod R)
+__device__ __forceinline__ void hga_ring_join(double *ring, int R, int tile_pos, const double (*ys)[16], int base, int kend,
+                                              int nsec2, int n)
+{
+    for (int idx = threadIdx.x; idx < HGA_TT * 16; idx += 256) {
+        const int tt = idx >> 4, p = idx & 15;
+        const int t = base + tt - (nsec2 - 1);
+        int pos = tile_pos + tt;
+        if (pos >= R) pos -= R;
+        if (base + tt < kend && t >= 0 && t < n) ring[pos * 16 + p] = ys[tt][p];
+    }
+}
+
+// every window from w_next on whose rows are all among the first rows_done: lane = (window, column), a sequential sum over
+// its rows (pyx:9-22, 42-46); then w_next moves past them (block-uniform).  ocol is the lane's output column, frame w at
+// ocol[w * C] (null: a column past the edge), oc its channel for the z-score.
+__device__ __forceinline__ void hga_ring_windows(const double *ring, int R, const int (*wtab)[HGF_WTAB], const HgaFrames &fr,
+                                                 int &w_next, int rows_done, double *__restrict__ ocol, int C, int oc)
+{
+    const int p = threadIdx.x & 15, wi = threadIdx.x >> 4;
+    int start, stop;
+    for (int w = w_next + wi; w < fr.W; w += 16) {
+        hga_window_range(wtab, fr, w, start, stop);
+        if (stop > rows_done) break;
+        double sum = 0.0;
+        // the window's rows sit at positions start mod R ... (wrapping once at most: stop - start <= R)
+        int pos = start % R, left = stop - start;
+        while (left > 0) {
+            const int run = min(left, R - pos);
+            const double *rp = ring + pos * 16 + p;
+            int i = 0;
+            for (; i + 8 <= run; i += 8) {             // eight ring reads in flight, then their terms in row order
+                double v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) v[u] = rp[(i + u) * 16];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) sum += v[u] * v[u];
+            }
+            for (; i < run; ++i) {
+                const double v = rp[i * 16];
+                sum += v * v;
+            }
+            left -= run;
+            pos = 0;
+        }
+        if (ocol) ocol[(size_t)w * C] = hga_finish(sum, stop - start, fr.apply_log, fr.zs_mean, fr.zs_std, oc);
+    }
+    for (; w_next < fr.W; ++w_next) {
+        hga_window_range(wtab, fr, w_next, start, stop);
+        if (stop > rows_done) break;
+    }
+}
+
+// All tiles of a block whose ring already holds rows [0, row0): the n samples of each column are filtered and join the ring at
+// rows row0 .. row0 + n - 1, and every window goes out once its rows are there.  The next tile's samples are fetched into
+// registers before the current tile's steps run and go to LDS after them: the HBM latency hides under the filter
+// arithmetic instead of standing between two barriers.  lcol: hga_tile_fetch; ocol, oc: hga_ring_windows.
+__device__ __forceinline__ void hga_ring_tiles(HgaLane &l, double (*xs)[16], double (*ys)[16], const int (*wtab)[HGF_WTAB],
+                                               double *ring, int R, const HgaFrames &fr, const double *__restrict__ lcol, int n,
+                                               int row0, double *__restrict__ ocol, int C, int oc)
+{
+    const int lp = threadIdx.x & 15, ltt = threadIdx.x >> 4;
+    const int steps = n + l.nsec2 - 1;
+    int w_next = 0;                                        // first window not yet written (block-uniform)
+    double pre[HGA_TT / 16];
+    hga_tile_fetch(pre, lcol, 0, n, C);
+    // ring position of row (row0 + t) for the first output of the current tile, kept modulo R (block-uniform)
+    int tile_pos = (row0 + R * 16 - (l.nsec2 - 1)) % R;    // row0 + t for t = 0 - (nsec2 - 1): the row "before" the first output
+    for (int base = 0; base < steps; base += HGA_TT) {
+        __syncthreads();                                   // previous tile fully consumed
+#pragma unroll
+        for (int j = 0; j < HGA_TT / 16; ++j) xs[ltt + 16 * j][lp] = pre[j];
+        if (base + HGA_TT < steps) hga_tile_fetch(pre, lcol, base + HGA_TT, n, C);
+        __syncthreads();
+        const int kend = min(base + HGA_TT, steps);
+        hga_tile_steps(l, xs, ys, base, kend, n);
+        __syncthreads();
+        hga_ring_join(ring, R, tile_pos, ys, base, kend, l.nsec2, n);
+        tile_pos += HGA_TT;
+        if (tile_pos >= R) tile_pos -= R;
+        __syncthreads();
+        int t_done = kend - (l.nsec2 - 1);
+        t_done = t_done < 0 ? 0 : (t_done > n ? n : t_done);
+        hga_ring_windows(ring, R, wtab, fr, w_next, row0 + t_done, ocol, C, oc);
+    }
+}
+
+// ---- streaming form: every stream advances by one chunk of n samples; the last `overlap` rows stay for the next call ----
 __global__ void __launch_bounds__(256, 4)
 hga_fused_kernel(const double *__restrict__ data, double *__restrict__ zi, double *__restrict__ rowbuf, double *__restrict__ out,
                  HgaSos sos, int S, int C, int n, int nsec, int row0, int cap_rows, int zero_rows, int rows, int W, int overlap,
@@ -184,186 +359,45 @@ hga_fused_kernel(const double *__restrict__ data, double *__restrict__ zi, doubl
     __shared__ double xs[HGA_TT + 1][16];
     __shared__ double ys[HGA_TT][16];
     __shared__ double coef[16][5];
-    __shared__ int wtab[2][HGF_WTAB];          // first and one-past-last row of the first HGF_WTAB windows (the float32 /
-                                               //   round() arithmetic of pyx:43-44 once per block instead of once per tile)
+    __shared__ int wtab[2][HGF_WTAB];
     extern __shared__ __attribute__((aligned(16))) double ring[];         // [R][16]
-    const int tid = threadIdx.x, r = tid & 15, pib = tid >> 4;
+    const int tid = threadIdx.x;
     const long total = (long)S * C;
     const long pair0 = (long)blockIdx.x * 16;
-    long pair = pair0 + pib;
+    const HgaFrames fr = {W, sr, wl, ws, apply_log, zs_mean, zs_std};
+    HgaLane l = hga_lane_setup(sos, nsec, coef);
+    // the column this thread filters, and its state
+    long pair = pair0 + l.pib;
     const bool valid = pair < total;
     if (!valid) pair = total - 1;
     const int s = (int)(pair / C), c = (int)(pair - (long)s * C);
-    const int nsec2 = 2 * nsec;
-    const bool has_sec = r < nsec2;
-    const bool is_last = r == nsec2 - 1;
-    const int f = has_sec ? r / nsec : 0, q = has_sec ? r - f * nsec : 0;
-    if (tid < 16) {
-        const int ff = tid < nsec2 ? tid / nsec : 0, qq = tid < nsec2 ? tid - ff * nsec : 0;
-        coef[tid][0] = sos.k[ff][qq][0]; coef[tid][1] = sos.k[ff][qq][1]; coef[tid][2] = sos.k[ff][qq][2];
-        coef[tid][3] = sos.k[ff][qq][4]; coef[tid][4] = sos.k[ff][qq][5];
-    }
     double *zp = zi + (size_t)s * 2 * 8 * 2 * C + c;
-    double z0 = zp[((f * 8 + q) * 2 + 0) * (size_t)C], z1 = zp[((f * 8 + q) * 2 + 1) * (size_t)C];
-    for (int w = tid; w < W && w < HGF_WTAB; w += 256) {
-        const int st = hga_win_start(w, ws, sr);
-        wtab[0][w] = st;
-        wtab[1][w] = hga_win_stop(st, wl, sr);
-    }
+    l.z0 = zp[((l.f * 8 + l.q) * 2 + 0) * (size_t)C];
+    l.z1 = zp[((l.f * 8 + l.q) * 2 + 1) * (size_t)C];
+    // the column this thread moves: input, overlap rows and frames (a block's 16 columns may span two streams)
+    const int p = tid & 15;
+    const long pp = pair0 + p;
+    const bool pvalid = pp < total;
+    const int sp = pvalid ? (int)(pp / C) : 0, cp = pvalid ? (int)(pp - (long)sp * C) : 0;
+    double *const rcol = rowbuf + (size_t)sp * cap_rows * C + cp;
+    // (formed here and selected against null below: formed inside the selection, the row stride C ends up in vector registers)
+    const double *const lcol = data + (size_t)sp * n * C + cp;
+    double *const ocol = out + (size_t)sp * W * C + cp;
+    hga_window_table(wtab, fr);
     // rows [0, row0) of the ring: zeros (CASE 2, pyx:116) or the overlap the previous call left (CASE 3, pyx:123-131)
-    for (int idx = tid; idx < row0 * 16; idx += 256) {
-        const int rr = idx >> 4, p = idx & 15;
-        const long pp = pair0 + p;
-        double v = 0.0;
-        if (rr >= zero_rows && pp < total) {
-            const int sp = (int)(pp / C), cp = (int)(pp - (long)sp * C);
-            v = rowbuf[((size_t)sp * cap_rows + rr) * C + cp];
-        }
-        ring[(rr % R) * 16 + p] = v;
-    }
+    for (int rr = tid >> 4; rr < row0; rr += 16)
+        ring[(rr % R) * 16 + p] = (rr >= zero_rows && pvalid) ? rcol[(size_t)rr * C] : 0.0;
     __syncthreads();
-    const double b0 = coef[r][0], b1 = coef[r][1], b2 = coef[r][2], a1 = coef[r][3], a2 = coef[r][4];
-    const int steps = n + nsec2 - 1;
-    double y = 0.0;
-    int w_next = 0;                                        // first window not yet written (block-uniform)
-    // Input tiles: thread (tt0, p) owns column p of rows tt0, tt0 + 16, ... of every tile.  The next tile's samples are
-    // fetched into registers before the current tile's steps run and go to LDS after them: the HBM latency hides under
-    // the filter arithmetic instead of standing between two barriers.
-    const int lp = tid & 15, ltt = tid >> 4;
-    const long lpp = pair0 + lp;
-    const bool lvalid = lpp < total;
-    const double *lcol = data;
-    if (lvalid) { const int sp = (int)(lpp / C), cp = (int)(lpp - (long)sp * C); lcol = data + (size_t)sp * n * C + cp; }
-    double pre[HGA_TT / 16];
-#define HGF_FETCH(BASE)                                                                          \
-    _Pragma("unroll") for (int j = 0; j < HGA_TT / 16; ++j) {                                        \
-        const int t = (BASE) + ltt + 16 * j;                                                     \
-        pre[j] = (lvalid && t < n) ? lcol[(size_t)t * C] : 0.0;                                  \
-    }
-    HGF_FETCH(0)
-    // ring position of row (row0 + t) for the first output of the current tile, kept modulo R (block-uniform)
-    int tile_pos = (row0 + R * 16 - (nsec2 - 1)) % R;      // row0 + t for t = 0 - (nsec2 - 1): the row "before" the first output
-    for (int base = 0; base < steps; base += HGA_TT) {
-        __syncthreads();                                   // previous tile fully consumed
-#pragma unroll
-        for (int j = 0; j < HGA_TT / 16; ++j) xs[ltt + 16 * j][lp] = pre[j];
-        if (base + HGA_TT < steps) { HGF_FETCH(base + HGA_TT) }
-        __syncthreads();
-        const int kend = min(base + HGA_TT, steps);
-        int k = base;
-        for (; k < kend && (k < nsec2 - 1 || k >= n); ++k) {
-            const double in = hga_shift_in(xs[k - base][pib], y);
-            const int t = k - r;
-            if (has_sec && t >= 0 && t < n) {
-                HGA_BIQUAD(in)
-                if (is_last) ys[k - base][pib] = y;
-            }
-        }
-        const int ksteady = min(kend, n);
-        {
-            const double *xp = &xs[k - base][pib];
-            double xcur = *xp;
-            // four steps per trip with constant LDS offsets (a DPP move is convergent: the compiler will not unroll a loop of
-            // unknown length around it): per step 9 fp64 operations, 2 DPP moves, one LDS read, one LDS write
-            double *const yl = &ys[k - base][pib];
-            int kk = 0;
-            for (; k + 4 <= ksteady; k += 4, kk += 4) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const double xnext = xp[16 * (kk + u + 1)];
-                    const double in = hga_shift_in(xcur, y);
-                    HGA_BIQUAD(in)
-                    if (is_last) yl[16 * (kk + u)] = y;
-                    xcur = xnext;
-                }
-            }
-            for (; k < ksteady; ++k, ++kk) {
-                const double xnext = xp[16 * (kk + 1)];
-                const double in = hga_shift_in(xcur, y);
-                HGA_BIQUAD(in)
-                if (is_last) yl[16 * kk] = y;
-                xcur = xnext;
-            }
-        }
-        for (; k < kend; ++k) {
-            const double in = hga_shift_in(xs[k - base][pib], y);
-            const int t = k - r;
-            if (has_sec && t >= 0 && t < n) {
-                HGA_BIQUAD(in)
-                if (is_last) ys[k - base][pib] = y;
-            }
-        }
-        __syncthreads();
-        // the tile's finished samples join the ring at their row (position row mod R, advanced from tile to tile)
-        for (int idx = tid; idx < HGA_TT * 16; idx += 256) {
-            const int tt = idx >> 4, p = idx & 15;
-            const int t = base + tt - (nsec2 - 1);
-            int pos = tile_pos + tt;
-            if (pos >= R) pos -= R;
-            if (base + tt < kend && t >= 0 && t < n) ring[pos * 16 + p] = ys[tt][p];
-        }
-        tile_pos += HGA_TT;
-        if (tile_pos >= R) tile_pos -= R;
-        __syncthreads();
-        // every window that is complete now: lane = (window, column), a sequential sum over its rows (pyx:9-22, 42-46)
-        int t_done = kend - (nsec2 - 1);
-        t_done = t_done < 0 ? 0 : (t_done > n ? n : t_done);
-        const int rows_done = row0 + t_done;
-        {
-            const int p = tid & 15, wi = tid >> 4;
-            const long pp = pair0 + p;
-            for (int w = w_next + wi; w < W; w += 16) {
-                const int start = w < HGF_WTAB ? wtab[0][w] : hga_win_start(w, ws, sr);
-                const int stop = w < HGF_WTAB ? wtab[1][w] : hga_win_stop(start, wl, sr);
-                if (stop > rows_done) break;
-                double sum = 0.0;
-                // the window's rows sit at positions start mod R ... (wrapping once at most: stop - start <= R)
-                int pos = start % R, left = stop - start;
-                while (left > 0) {
-                    const int run = min(left, R - pos);
-                    const double *rp = ring + pos * 16 + p;
-                    int i = 0;
-                    for (; i + 8 <= run; i += 8) {             // eight ring reads in flight, then their terms in row order
-                        double v[8];
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) v[u] = rp[(i + u) * 16];
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) sum += v[u] * v[u];
-                    }
-                    for (; i < run; ++i) {
-                        const double v = rp[i * 16];
-                        sum += v * v;
-                    }
-                    left -= run;
-                    pos = 0;
-                }
-                if (pp < total) {
-                    const int sp = (int)(pp / C), cp = (int)(pp - (long)sp * C);
-                    const double pw = sum / (double)(stop - start) + 0.01;
-                    double o = apply_log ? log(pw) : pw;
-                    if (zs_mean) o = (o - zs_mean[cp]) / zs_std[cp];          // ZScoreNormalization (local/common.py:367-376)
-                    out[((size_t)sp * W + w) * C + cp] = o;
-                }
-            }
-            while (w_next < W && (w_next < HGF_WTAB ? wtab[1][w_next] : hga_win_stop(hga_win_start(w_next, ws, sr), wl, sr)) <= rows_done)
-                ++w_next;
-        }
-    }
+    hga_lane_coef(l, coef);
+    hga_ring_tiles(l, xs, ys, wtab, ring, R, fr, pvalid ? lcol : nullptr, n, row0, pvalid ? ocol : nullptr, C, cp);
     __syncthreads();
     // the last `overlap` rows become rows 0..overlap-1 of the next call (WarmStartFrameBuffer.remainder_data)
-    for (int idx = tid; idx < overlap * 16; idx += 256) {
-        const int kk = idx >> 4, p = idx & 15;
-        const long pp = pair0 + p;
-        if (pp < total) {
-            const int sp = (int)(pp / C), cp = (int)(pp - (long)sp * C);
-            rowbuf[((size_t)sp * cap_rows + kk) * C + cp] = ring[((rows - overlap + kk) % R) * 16 + p];
-        }
+    if (pvalid)
+        for (int kk = tid >> 4; kk < overlap; kk += 16) rcol[(size_t)kk * C] = ring[((rows - overlap + kk) % R) * 16 + p];
+    if (valid && l.has_sec) {
+        zp[((l.f * 8 + l.q) * 2 + 0) * (size_t)C] = l.z0;
+        zp[((l.f * 8 + l.q) * 2 + 1) * (size_t)C] = l.z1;
     }
-    if (valid && has_sec) {
-        zp[((f * 8 + q) * 2 + 0) * (size_t)C] = z0;
-        zp[((f * 8 + q) * 2 + 1) * (size_t)C] = z1;
-    }
-#undef HGF_FETCH
 }
 
 // ---- trial form: one launch for a list of trials of unequal length ----------------------------------------------------
@@ -371,15 +405,11 @@ hga_fused_kernel(const double *__restrict__ data, double *__restrict__ zi, doubl
 // windows of unequal length into ONE recording, each fed to a FRESH HighGammaExtractor as a single chunk.  Here a block takes
 // (trial, 16-column group): its n, W, zero rows, first input row and first output frame come from a descriptor table, the
 // filter state starts at the unit-step state of sosfilt_zi (units.py:128-132) and nothing is written back -- no per-stream
-// zi / rowbuf is touched.  The per-step code, the ring, the window tables and the sequential window sum are those of
-// hga_fused_kernel, statement for statement (the body is repeated rather than shared so that the streaming kernel's code
-// generation cannot move); windows past HGF_WTAB take their row range from the float32 arithmetic directly, as there.
+// zi / rowbuf is touched.  Everything between is hga_ring_tiles, as in hga_fused_kernel.
 // `data` is the recording (or its front-end output), (rows, C) row-major; trial i reads rows in_row .. in_row + n - 1 and
 // writes frames out_row .. out_row + W - 1 of the concatenated (sum W, C) output.  Every range is checked on the host.
-struct HgaTrialDesc { long long in_row, out_row; int n, W, zero_rows, pad; };
-
 __global__ void __launch_bounds__(256, 4)
-hga_trials_kernel(const double *__restrict__ data, const HgaTrialDesc *__restrict__ desc, double *__restrict__ out,
+hga_trials_kernel(const double *__restrict__ data, const DssHgaTrialDesc *__restrict__ desc, double *__restrict__ out,
                   const double *__restrict__ zi_hg, const double *__restrict__ zi_fh, HgaSos sos, int C, int cgroups, int nsec,
                   int sr, float wl, float ws, int apply_log, int R, const double *__restrict__ zs_mean,
                   const double *__restrict__ zs_std)
@@ -389,157 +419,34 @@ hga_trials_kernel(const double *__restrict__ data, const HgaTrialDesc *__restric
     __shared__ double coef[16][5];
     __shared__ int wtab[2][HGF_WTAB];
     extern __shared__ __attribute__((aligned(16))) double ring[];         // [R][16]
-    const int tid = threadIdx.x, r = tid & 15, pib = tid >> 4;
+    const int tid = threadIdx.x;
     const int trial = blockIdx.x / cgroups, cg = blockIdx.x - trial * cgroups;
-    const HgaTrialDesc d = desc[trial];
-    const int n = d.n, W = d.W, row0 = d.zero_rows;       // a fresh frame buffer: CASE 1 (row0 = 0) or CASE 2 (left zero pad)
-    const int col0 = cg * 16;
-    const int nsec2 = 2 * nsec;
-    const bool has_sec = r < nsec2;
-    const bool is_last = r == nsec2 - 1;
-    const int f = has_sec ? r / nsec : 0, q = has_sec ? r - f * nsec : 0;
-    if (tid < 16) {
-        const int ff = tid < nsec2 ? tid / nsec : 0, qq = tid < nsec2 ? tid - ff * nsec : 0;
-        coef[tid][0] = sos.k[ff][qq][0]; coef[tid][1] = sos.k[ff][qq][1]; coef[tid][2] = sos.k[ff][qq][2];
-        coef[tid][3] = sos.k[ff][qq][4]; coef[tid][4] = sos.k[ff][qq][5];
-    }
+    const DssHgaTrialDesc d = desc[trial];
+    const int row0 = d.zero_rows;                         // a fresh frame buffer: CASE 1 (row0 = 0) or CASE 2 (left zero pad)
+    const HgaFrames fr = {d.W, sr, wl, ws, apply_log, zs_mean, zs_std};
+    HgaLane l = hga_lane_setup(sos, nsec, coef);
     // units.py:128-132: every column starts at sosfilt_zi(sos), not scaled by the first sample
-    const double *z_src = f ? zi_fh : zi_hg;
-    double z0 = has_sec ? z_src[q * 2 + 0] : 0.0, z1 = has_sec ? z_src[q * 2 + 1] : 0.0;
-    for (int w = tid; w < W && w < HGF_WTAB; w += 256) {
-        const int st = hga_win_start(w, ws, sr);
-        wtab[0][w] = st;
-        wtab[1][w] = hga_win_stop(st, wl, sr);
-    }
+    const double *z_src = l.f ? zi_fh : zi_hg;
+    l.z0 = l.has_sec ? z_src[l.q * 2 + 0] : 0.0;
+    l.z1 = l.has_sec ? z_src[l.q * 2 + 1] : 0.0;
+    hga_window_table(wtab, fr);
     for (int idx = tid; idx < row0 * 16; idx += 256) ring[idx] = 0.0;     // CASE 2, pyx:116 (row0 <= frame length <= R)
     __syncthreads();
-    const double b0 = coef[r][0], b1 = coef[r][1], b2 = coef[r][2], a1 = coef[r][3], a2 = coef[r][4];
-    const int steps = n + nsec2 - 1;
-    double y = 0.0;
-    int w_next = 0;
-    const int lp = tid & 15, ltt = tid >> 4;
-    const bool lvalid = col0 + lp < C;
-    const double *lcol = data + (size_t)d.in_row * C + (lvalid ? col0 + lp : 0);
-    double pre[HGA_TT / 16];
-#define HGT_FETCH(BASE)                                                                          \
-    _Pragma("unroll") for (int j = 0; j < HGA_TT / 16; ++j) {                                        \
-        const int t = (BASE) + ltt + 16 * j;                                                     \
-        pre[j] = (lvalid && t < n) ? lcol[(size_t)t * C] : 0.0;                                  \
-    }
-    HGT_FETCH(0)
-    int tile_pos = (row0 + R * 16 - (nsec2 - 1)) % R;
-    for (int base = 0; base < steps; base += HGA_TT) {
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < HGA_TT / 16; ++j) xs[ltt + 16 * j][lp] = pre[j];
-        if (base + HGA_TT < steps) { HGT_FETCH(base + HGA_TT) }
-        __syncthreads();
-        const int kend = min(base + HGA_TT, steps);
-        int k = base;
-        for (; k < kend && (k < nsec2 - 1 || k >= n); ++k) {
-            const double in = hga_shift_in(xs[k - base][pib], y);
-            const int t = k - r;
-            if (has_sec && t >= 0 && t < n) {
-                HGA_BIQUAD(in)
-                if (is_last) ys[k - base][pib] = y;
-            }
-        }
-        const int ksteady = min(kend, n);
-        {
-            const double *xp = &xs[k - base][pib];
-            double xcur = *xp;
-            double *const yl = &ys[k - base][pib];
-            int kk = 0;
-            for (; k + 4 <= ksteady; k += 4, kk += 4) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const double xnext = xp[16 * (kk + u + 1)];
-                    const double in = hga_shift_in(xcur, y);
-                    HGA_BIQUAD(in)
-                    if (is_last) yl[16 * (kk + u)] = y;
-                    xcur = xnext;
-                }
-            }
-            for (; k < ksteady; ++k, ++kk) {
-                const double xnext = xp[16 * (kk + 1)];
-                const double in = hga_shift_in(xcur, y);
-                HGA_BIQUAD(in)
-                if (is_last) yl[16 * kk] = y;
-                xcur = xnext;
-            }
-        }
-        for (; k < kend; ++k) {
-            const double in = hga_shift_in(xs[k - base][pib], y);
-            const int t = k - r;
-            if (has_sec && t >= 0 && t < n) {
-                HGA_BIQUAD(in)
-                if (is_last) ys[k - base][pib] = y;
-            }
-        }
-        __syncthreads();
-        for (int idx = tid; idx < HGA_TT * 16; idx += 256) {
-            const int tt = idx >> 4, p = idx & 15;
-            const int t = base + tt - (nsec2 - 1);
-            int pos = tile_pos + tt;
-            if (pos >= R) pos -= R;
-            if (base + tt < kend && t >= 0 && t < n) ring[pos * 16 + p] = ys[tt][p];
-        }
-        tile_pos += HGA_TT;
-        if (tile_pos >= R) tile_pos -= R;
-        __syncthreads();
-        int t_done = kend - (nsec2 - 1);
-        t_done = t_done < 0 ? 0 : (t_done > n ? n : t_done);
-        const int rows_done = row0 + t_done;
-        {
-            const int p = tid & 15, wi = tid >> 4;
-            const int c = col0 + p;
-            for (int w = w_next + wi; w < W; w += 16) {
-                const int start = w < HGF_WTAB ? wtab[0][w] : hga_win_start(w, ws, sr);
-                const int stop = w < HGF_WTAB ? wtab[1][w] : hga_win_stop(start, wl, sr);
-                if (stop > rows_done) break;
-                double sum = 0.0;
-                int pos = start % R, left = stop - start;
-                while (left > 0) {
-                    const int run = min(left, R - pos);
-                    const double *rp = ring + pos * 16 + p;
-                    int i = 0;
-                    for (; i + 8 <= run; i += 8) {
-                        double v[8];
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) v[u] = rp[(i + u) * 16];
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) sum += v[u] * v[u];
-                    }
-                    for (; i < run; ++i) {
-                        const double v = rp[i * 16];
-                        sum += v * v;
-                    }
-                    left -= run;
-                    pos = 0;
-                }
-                if (c < C) {
-                    const double pw = sum / (double)(stop - start) + 0.01;
-                    double o = apply_log ? log(pw) : pw;
-                    if (zs_mean) o = (o - zs_mean[c]) / zs_std[c];
-                    out[((size_t)d.out_row + w) * C + c] = o;
-                }
-            }
-            while (w_next < W && (w_next < HGF_WTAB ? wtab[1][w_next] : hga_win_stop(hga_win_start(w_next, ws, sr), wl, sr)) <= rows_done)
-                ++w_next;
-        }
-    }
-#undef HGT_FETCH
+    hga_lane_coef(l, coef);
+    const int c = cg * 16 + (tid & 15);                   // the column this thread moves: input and frames
+    const bool cvalid = c < C;
+    const double *const lcol = data + (size_t)d.in_row * C + (cvalid ? c : 0);
+    double *const ocol = out + (size_t)d.out_row * C + (cvalid ? c : 0);
+    hga_ring_tiles(l, xs, ys, wtab, ring, R, fr, cvalid ? lcol : nullptr, d.n, row0, cvalid ? ocol : nullptr, C, c);
 }
 
-int dss_launch_hga_trials(const DssHgaDev &h, const double *d_data, const void *d_desc, int n_trials, const double *d_zi_hg,
+int dss_launch_hga_trials(const DssHgaDev &h, const double *d_data, const DssHgaTrialDesc *d_desc, int n_trials, const double *d_zi_hg,
                           const double *d_zi_fh, double *d_out, int apply_log, int with_zscore, hipStream_t st)
 {
     if (n_trials <= 0) return DSS_OK;
     HgaSos sos;
     memcpy(&sos, h.sos, sizeof(sos));
     const DssHgaRing ring = dss_hga_ring(h.frame_length, h.overlap);
-    const int ring_rows = ring.rows;
-    const size_t ring_bytes = ring.bytes;
     if (!ring.fused) {
         dss_set_error("HGA trials: a frame of %d rows does not fit the kernel's ring", h.frame_length);
         return DSS_EINVAL;
@@ -547,9 +454,9 @@ int dss_launch_hga_trials(const DssHgaDev &h, const double *d_data, const void *
     const int cgroups = (h.C + 15) / 16;
     const long blocks = (long)n_trials * cgroups;
     if (blocks > 0x7fffffffL) { dss_set_error("HGA trials: too many blocks"); return DSS_EINVAL; }
-    hipLaunchKernelGGL(hga_trials_kernel, dim3((unsigned)blocks), dim3(256), ring_bytes, st, d_data,
-                       static_cast<const HgaTrialDesc *>(d_desc), d_out, d_zi_hg, d_zi_fh, sos, h.C, cgroups, h.nsec, h.fs, h.wl, h.ws,
-                       apply_log, ring_rows, with_zscore ? h.zs_mean : nullptr, with_zscore ? h.zs_std : nullptr);
+    hipLaunchKernelGGL(hga_trials_kernel, dim3((unsigned)blocks), dim3(256), ring.bytes, st, d_data, d_desc, d_out, d_zi_hg, d_zi_fh,
+                       sos, h.C, cgroups, h.nsec, h.fs, h.wl, h.ws, apply_log, ring.rows, with_zscore ? h.zs_mean : nullptr,
+                       with_zscore ? h.zs_std : nullptr);
     DSS_HIP_CHECK(hipGetLastError());
     return DSS_OK;
 }
@@ -793,10 +700,7 @@ hga_window_kernel(const double *__restrict__ rowbuf, double *__restrict__ out, i
             sum += v * v;
         }
     }
-    const double p = sum / (double)(stop - start) + 0.01;
-    double o = apply_log ? log(p) : p;
-    if (zs_mean) o = (o - zs_mean[c]) / zs_std[c];                    // ZScoreNormalization (local/common.py:367-376)
-    out[((size_t)s * W + win) * C + c] = o;
+    out[((size_t)s * W + win) * C + c] = hga_finish(sum, stop - start, apply_log, zs_mean, zs_std, c);
 }
 
 // ---- stage 3: keep the last `overlap` rows (ascending copy: a source row is always ahead of its destination) ------
@@ -810,22 +714,18 @@ hga_overlap_kernel(double *__restrict__ rowbuf, int S, int C, int cap_rows, int 
     for (int k = 0; k < overlap; ++k) col[(size_t)k * C] = col[(size_t)(rows - overlap + k) * C];
 }
 
-int dss_launch_hga(const DssHgaDev &h, const double *d_data, const DssHgaFrontDev *fe, int n, int row0, int zero_rows, int rows,
-                   int W, double *d_out, int apply_log, hipStream_t st)
+int dss_launch_hga(const DssHgaDev &h, const double *d_data, int n, int row0, int zero_rows, int rows, int W, double *d_out,
+                   int apply_log, hipStream_t st)
 {
     HgaSos sos;
     memcpy(&sos, h.sos, sizeof(sos));
     const long pairs = (long)h.S * h.C;
-    if (fe) { dss_set_error("HGA: raw amplifier rows go through dss_launch_hga_frontend first"); return DSS_EINVAL; }
     if (h.force_path != 2) {   // fused form when the ring (frame + shift + one tile of rows) fits beside the tiles
-        const int TT = HGA_TT;
         const DssHgaRing ring = dss_hga_ring(h.frame_length, h.overlap);
-        const int ring_rows = ring.rows;
-        const size_t ring_bytes = ring.bytes;
-        if (ring.fused && rows - h.overlap + TT <= (1 << 30) && h.overlap <= ring_rows && row0 <= ring_rows) {
-            hipLaunchKernelGGL(hga_fused_kernel, dim3((unsigned)((pairs + 15) / 16)), dim3(256), ring_bytes, st, d_data, h.zi,
-                                   h.rows, d_out, sos, h.S, h.C, n, h.nsec, row0, h.cap_rows, zero_rows, rows, W, h.overlap, h.fs, h.wl,
-                                   h.ws, apply_log, ring_rows, h.zs_mean, h.zs_std);
+        if (ring.fused && rows - h.overlap + HGA_TT <= (1 << 30) && h.overlap <= ring.rows && row0 <= ring.rows) {
+            hipLaunchKernelGGL(hga_fused_kernel, dim3((unsigned)((pairs + 15) / 16)), dim3(256), ring.bytes, st, d_data, h.zi,
+                               h.rows, d_out, sos, h.S, h.C, n, h.nsec, row0, h.cap_rows, zero_rows, rows, W, h.overlap, h.fs, h.wl,
+                               h.ws, apply_log, ring.rows, h.zs_mean, h.zs_std);
             DSS_HIP_CHECK(hipGetLastError());
             return DSS_OK;
         }
@@ -887,8 +787,7 @@ hga_log_power_kernel(const double *__restrict__ data, double *__restrict__ out, 
         const double q = data[(size_t)r * C + c];
         sum += q * q;
     }
-    const double p = sum / (double)(stop - start) + 0.01;
-    out[gid] = apply_log ? log(p) : p;
+    out[gid] = hga_finish(sum, stop - start, apply_log, nullptr, nullptr, c);
 }
 
 int dss_launch_log_power(const double *d_data, int T, int C, int sr, float wl, float ws, int W, double *d_out,
