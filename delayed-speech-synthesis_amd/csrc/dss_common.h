@@ -66,7 +66,7 @@ struct DssModelDev {
     const float *gru_b_w_in;                                // [384][48]
     const float *gru_b_w_rec;                               // [16][48]
     const float *fc_bias, *fc_w, *fc_factor;                // [512], [256][2][16], [512]
-    // derived tables (host libm, see dss_capi.cpp)
+    // derived tables (host libm, see dss_lpcnet_model.cpp)
     const float *tansig;          // [201] y = tanh(.04 i) as tansig_table.h rounds it; [DSS_TANSIG_Y + i]: 1 - y*y (see lpcnet_device.h)
     const float *logit_table;     // [256]
     const float *ulaw2lin;        // [256]
@@ -82,7 +82,7 @@ struct DssModelDev {
     int zr_cap;                   // register slots per gate of waves 4, 5: 10 or 12 (selects the instantiation)
     int hmax;                     // max h blocks over all row groups (reporting)
     int ext;                      // 1 when the model uses z/r tails or h slots beyond DSS_HC (latency kernel only)
-    int ext_tab;                  // float offset inside hblk of the tables the extended paths read (see dss_capi.cpp)
+    int ext_tab;                  // float offset inside hblk of the tables the extended paths read (see dss_lpcnet_model.cpp)
     int hblk_floats;              // size of hblk
     const int *unit_of;           // [384] lane of waves 0..5 -> GRU A unit whose z and r chains it runs
     const int *unit_h;            // [384] lane of waves 0..5 -> GRU A unit whose h-gate chain it runs
@@ -93,7 +93,7 @@ struct DssModelDev {
     const float *zr_w;            // [2*DSS_ZRC][4][384] z then r block weights per lane slot, zero padded
     const unsigned *zr_col;       // [2*DSS_ZRC/4][384]  four 8-bit block column ids (pos/4) per word
     const unsigned *h_col;        // [DSS_HCX/4][384]    same for the h-gate slots of the lane's row group
-    const float *hblk;            // LDS image: one list of [8 rows][4] records per row group, lists back to back (see dss_capi.cpp)
+    const float *hblk;            // LDS image: one list of [8 rows][4] records per row group, lists back to back (see dss_lpcnet_model.cpp)
     const float *gb_w_lane;       // [384][64] GRU B input weights, input-major, lane = row (rows 48..63 zero)
     const float *fc_w_pair;       // dual-FC weights as [k 8][node 256][4]: (layer 0, layer 1) weights of inputs 2k, 2k+1 (pair kernel)
     const float *gb_w_quad;       // the same weights as [384/4][64 lanes][4 inputs]: one 16-byte load per lane and block of four inputs

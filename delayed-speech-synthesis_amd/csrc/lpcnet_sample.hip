@@ -917,6 +917,23 @@ int dss_launch_tansig_selftest(const float *d_tab, int which, unsigned start, un
     return DSS_OK;
 }
 
+// Every compiled instantiation of lpcnet_sample_kernel, named here and nowhere else: the attribute pass walks the table, the launch
+// picks from it by the template arguments.
+struct SampleVariant { bool trace, stamp; int z; bool ragged, ext, progress; const void *fn; };
+#define DSS_VARIANT(T, S2, Z, R, E) {T, S2, Z, R, E, false, (const void *)lpcnet_sample_kernel<T, S2, Z, R, E>}
+#define DSS_VARIANT_PROGRESS(Z, E) {false, false, Z, true, E, true, (const void *)lpcnet_sample_kernel<false, false, Z, true, E, int *>}
+static const SampleVariant sample_variants[] = {
+    DSS_VARIANT(false, false, 10, false, false), DSS_VARIANT(false, false, 12, false, false),       // uniform
+    DSS_VARIANT(false, false, 10, true, false),  DSS_VARIANT(false, false, 12, true, false),        // ragged
+    DSS_VARIANT(true, false, 10, false, false),  DSS_VARIANT(true, false, 12, false, false),        // trace (honours the ragged lists)
+    DSS_VARIANT(false, true, 10, false, false),  DSS_VARIANT(false, true, 12, false, false),        // phase stamps
+    DSS_VARIANT(false, false, 10, false, true),  DSS_VARIANT(false, false, 10, true, true), DSS_VARIANT(true, false, 10, false, true),   // extended paths
+    DSS_VARIANT_PROGRESS(10, false), DSS_VARIANT_PROGRESS(12, false), DSS_VARIANT_PROGRESS(10, true),
+};
+#undef DSS_VARIANT
+#undef DSS_VARIANT_PROGRESS
+static DssLdsLimitOnce sample_lds_limit;
+
 // Number of CUs of the current device, asked once per device (the eager streaming tick launches this kernel every 40 ms).
 static int dss_cu_count()
 {
@@ -958,54 +975,21 @@ int dss_launch_sample_network(const DssModelDev &m, DssBatchDev &b, int n_utts, 
     }
     const int n_rows = n_utts - n_pair;          // rows of this launch
     const size_t dyn = ((size_t)m.hblk_floats * sizeof(float) + 15) & ~(size_t)15;
-    // two register-slot capacities are compiled: 10 per gate (no spills) and 12 (a few spilled registers)
-    const bool z10 = m.zr_cap <= 10;
-    static std::mutex attr_mu;                  // states on different devices may launch from different threads
-    static unsigned long long attr_set = 0;     // per device: the attribute belongs to the device's code object
-    int dev = 0;
-    DSS_HIP_CHECK(hipGetDevice(&dev));
-    {
-    std::lock_guard<std::mutex> attr_lk(attr_mu);
-    if (!(attr_set >> (dev & 63) & 1)) {      // one workgroup uses (almost) the whole 160 KB of the CU
-#define DSS_SET_ATTR(K) DSS_HIP_CHECK(hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, DSS_HBLK_BYTES))
-        DSS_SET_ATTR((lpcnet_sample_kernel<false, false, 10, false, false>)); DSS_SET_ATTR((lpcnet_sample_kernel<false, false, 12, false, false>));
-        DSS_SET_ATTR((lpcnet_sample_kernel<false, false, 10, true, false>));  DSS_SET_ATTR((lpcnet_sample_kernel<false, false, 12, true, false>));
-        DSS_SET_ATTR((lpcnet_sample_kernel<true, false, 10, false, false>));  DSS_SET_ATTR((lpcnet_sample_kernel<true, false, 12, false, false>));
-        DSS_SET_ATTR((lpcnet_sample_kernel<false, true, 10, false, false>));  DSS_SET_ATTR((lpcnet_sample_kernel<false, true, 12, false, false>));
-        // models with z/r tails or long h lists (m.ext): always on the 10-slot layout, which has registers to spare for them
-        DSS_SET_ATTR((lpcnet_sample_kernel<false, false, 10, false, true>));  DSS_SET_ATTR((lpcnet_sample_kernel<false, false, 10, true, true>));
-        DSS_SET_ATTR((lpcnet_sample_kernel<true, false, 10, false, true>));
-        DSS_SET_ATTR((lpcnet_sample_kernel<false, false, 10, true, false, int *>)); DSS_SET_ATTR((lpcnet_sample_kernel<false, false, 12, true, false, int *>));
-        DSS_SET_ATTR((lpcnet_sample_kernel<false, false, 10, true, true, int *>));
-#undef DSS_SET_ATTR
-        attr_set |= 1ull << (dev & 63);
-    }
-    }
     const bool ragged = b.slot_of || b.count_of;
     if (ragged && trace == 2) { dss_set_error("phase stamps are taken on uniform calls only"); return DSS_EINVAL; }
     if (m.ext && trace == 2) { dss_set_error("phase stamps are not built for models with z/r tails"); return DSS_EINVAL; }
-#define DSS_LAUNCH(T, S2, R)                                                                                           \
-    do {                                                                                                               \
-        if (z10) hipLaunchKernelGGL((lpcnet_sample_kernel<T, S2, 10, R, false>), dim3(n_rows), dim3(512), dyn, s, m, b, n_frames, d_pcm); \
-        else hipLaunchKernelGGL((lpcnet_sample_kernel<T, S2, 12, R, false>), dim3(n_rows), dim3(512), dyn, s, m, b, n_frames, d_pcm);     \
-    } while (0)
-#define DSS_LAUNCH_EXT(T, R) hipLaunchKernelGGL((lpcnet_sample_kernel<T, false, 10, R, true>), dim3(n_rows), dim3(512), dyn, s, m, b, n_frames, d_pcm)
-    if (frames_done) {                           // progressive (ragged) calls
-        if (m.ext) hipLaunchKernelGGL((lpcnet_sample_kernel<false, false, 10, true, true, int *>), dim3(n_rows), dim3(512), dyn, s, m, b, n_frames, d_pcm, frames_done);
-        else if (z10) hipLaunchKernelGGL((lpcnet_sample_kernel<false, false, 10, true, false, int *>), dim3(n_rows), dim3(512), dyn, s, m, b, n_frames, d_pcm, frames_done);
-        else hipLaunchKernelGGL((lpcnet_sample_kernel<false, false, 12, true, false, int *>), dim3(n_rows), dim3(512), dyn, s, m, b, n_frames, d_pcm, frames_done);
-    }
-    else if (m.ext) {
-        if (trace) DSS_LAUNCH_EXT(true, false);
-        else if (ragged) DSS_LAUNCH_EXT(false, true);
-        else DSS_LAUNCH_EXT(false, false);
-    }
-    else if (trace == 2) DSS_LAUNCH(false, true, false);   // diagnostic: phase stamps (never used for timing claims)
-    else if (trace) DSS_LAUNCH(true, false, false);
-    else if (ragged) DSS_LAUNCH(false, false, true);
-    else DSS_LAUNCH(false, false, false);
-#undef DSS_LAUNCH
-#undef DSS_LAUNCH_EXT
+    // two register-slot capacities are compiled: 10 per gate (no spills) and 12 (a few spilled registers); models with z/r tails or
+    // long h lists (m.ext) are always on the 10-slot layout, which has registers to spare for them
+    const bool stamp = trace == 2;               // diagnostic: phase stamps (never used for timing claims)
+    const bool progress = frames_done != nullptr, rows = !trace && (ragged || progress), ext = m.ext != 0;      // progressive calls are ragged
+    const int z = (ext || m.zr_cap <= 10) ? 10 : 12;
+    const void *fn = nullptr;
+    for (const SampleVariant &v : sample_variants)
+        if (v.trace == (trace && !stamp) && v.stamp == stamp && v.z == z && v.ragged == rows && v.ext == ext && v.progress == progress) fn = v.fn;
+    if (!fn) { dss_set_error("sample kernel: no instantiation for this call"); return DSS_EINVAL; }
+    if (const int rc = sample_lds_limit.raise(sample_variants, DSS_HBLK_BYTES)) return rc;      // one workgroup uses (almost) the whole 160 KB of the CU
+    void *args[] = {(void *)&m, (void *)&b, &n_frames, &d_pcm, &frames_done};       // the last one: the PROGRESS instantiations only
+    hipLaunchKernel(fn, dim3(n_rows), dim3(512), args, dyn, s);
     b.utt0 = 0;
     DSS_HIP_CHECK(hipGetLastError());
     return DSS_OK;

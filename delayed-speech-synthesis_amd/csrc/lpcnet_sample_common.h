@@ -3,6 +3,8 @@
 // workgroup as the halves of packed fp32 instructions, throughput-optimised).  Every macro keeps the summation order of xiph's
 // sparse_sgemv_accum8x4 / sgemv_accum (src/vec.h generic path): one product at a time, ascending input.
 #pragma once
+#include <mutex>
+
 #include "dss_common.h"
 #include "lpcnet_device.h"
 
@@ -294,3 +296,21 @@ __device__ __forceinline__ f32x2 dss_pk_mul_hi(f32x2 w, f32x2 x)
         "v_pk_add_f32 %[a], %[a], %[p3]"                                                         \
         : [a] "+v"(ACC)                                                                          \
         : [p0] "v"((P)[0]), [p1] "v"((P)[1]), [p2] "v"((P)[2]), [p3] "v"((P)[3]))
+
+// ---- host side: the launchers' table of compiled instantiations ---------------------------------------------------------
+// Raises the dynamic LDS limit of every kernel of a launcher's table (entries with a member fn) to `bytes`, once per device: the
+// attribute belongs to the device's code object, and states on different devices may launch from different threads.
+struct DssLdsLimitOnce {
+    std::mutex mu;
+    unsigned long long done = 0;        // bit = device
+    template <typename V, size_t N> int raise(const V (&table)[N], int bytes)
+    {
+        int dev = 0;
+        DSS_HIP_CHECK(hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lk(mu);
+        if (done >> (dev & 63) & 1) return DSS_OK;
+        for (const V &v : table) DSS_HIP_CHECK(hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        done |= 1ull << (dev & 63);
+        return DSS_OK;
+    }
+};

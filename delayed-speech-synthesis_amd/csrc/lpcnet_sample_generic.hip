@@ -61,7 +61,7 @@ __device__ __forceinline__ void generic_role_a(SampleLds &L, const DssModelDev &
         ff0 = m.fc_factor[tid]; ff1 = m.fc_factor[DSS_FC_OUT + tid];
     }
     const bool recur_first = m.h.gru_a_order == DSS_GRUA_RECUR_FIRST;      // association of the z/r pre-activations
-    const int nzr = m.gate[0].slots, nhh = m.gate[2].slots;      // z and r lists share one padded length (dss_capi.cpp)
+    const int nzr = m.gate[0].slots, nhh = m.gate[2].slots;      // z and r lists share one padded length (dss_lpcnet_model.cpp)
     const int level = 31 - __clz(tid | 1);                                   // node = (1 << level) | prefix
     unsigned long long stamp_acc[6] = {0, 0, 0, 0, 0, 0}, t_prev = 0;
     int cur = 0;
@@ -120,7 +120,7 @@ __device__ __forceinline__ void generic_role_a(SampleLds &L, const DssModelDev &
                     ACC += W[u][3] * xv.w;                                                       \
                 }
                 // (no conditional loads: a conditionally defined array stays alive across loop iterations and spills;
-                // dss_capi.cpp pads the z and r lists to one common multiple of 8 and the h list to a multiple of 16)
+                // dss_lpcnet_model.cpp pads the z and r lists to one common multiple of 8 and the h list to a multiple of 16)
                 for (int sl = 0; sl < nzr; sl += 8) {                               // z and r rounds: 16 blocks in flight
                     int pz[8], pr[8];
                     float wz[8][4], wr[8][4];

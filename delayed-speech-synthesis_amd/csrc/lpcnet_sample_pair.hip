@@ -888,6 +888,17 @@ int dss_pair_fits(const DssModelDev &m)
     return m.fast_ok && !m.ext && (size_t)m.hblk_floats * sizeof(float) <= DSS_PAIR_HBLK_BYTES;
 }
 
+// Every compiled instantiation of lpcnet_sample_pair_kernel, named here and nowhere else: the attribute pass walks the table, the
+// launch picks from it by the template arguments.
+struct PairVariant { bool trace, stamp; int z; bool ragged; const void *fn; };
+#define DSS_VARIANT(T, S2, R) {T, S2, 10, R, (const void *)lpcnet_sample_pair_kernel<T, S2, 10, R>}, {T, S2, 12, R, (const void *)lpcnet_sample_pair_kernel<T, S2, 12, R>}
+static const PairVariant pair_variants[] = {
+    DSS_VARIANT(false, false, false), DSS_VARIANT(true, false, false), DSS_VARIANT(false, true, false),       // uniform, trace, phase stamps
+    DSS_VARIANT(false, false, true),  DSS_VARIANT(true, false, true),                                         // ragged, ragged trace
+};
+#undef DSS_VARIANT
+static DssLdsLimitOnce pair_lds_limit;
+
 // trace: 0, 1 (excitation / pcm trace and teacher forcing), 2 (phase stamps of the diagnostic build: uniform calls only).
 // Ragged calls (b.slot_of / b.count_of) run the RAGGED instantiation: rows 2k and 2k+1 share a workgroup, so a caller
 // that orders its rows by length (longest first, as the synthesis queue does) pairs rows of near-equal length.
@@ -898,36 +909,15 @@ int dss_launch_sample_network_pair(const DssModelDev &m, DssBatchDev &b, int n_u
     const bool ragged = b.slot_of || b.count_of;
     if (ragged && trace == 2) { dss_set_error("phase stamps are taken on uniform calls only"); return DSS_EINVAL; }
     const size_t dyn = ((size_t)m.hblk_floats * sizeof(float) + 15) & ~(size_t)15;
-    const bool z10 = m.zr_cap <= 10;
-    static std::mutex attr_mu;
-    static unsigned long long attr_set = 0;
-    int dev = 0;
-    DSS_HIP_CHECK(hipGetDevice(&dev));
-    {
-        std::lock_guard<std::mutex> attr_lk(attr_mu);
-        if (!(attr_set >> (dev & 63) & 1)) {
-#define DSS_SET_ATTR(K) DSS_HIP_CHECK(hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, DSS_PAIR_HBLK_BYTES))
-            DSS_SET_ATTR((lpcnet_sample_pair_kernel<false, false, 10, false>)); DSS_SET_ATTR((lpcnet_sample_pair_kernel<false, false, 12, false>));
-            DSS_SET_ATTR((lpcnet_sample_pair_kernel<true, false, 10, false>));  DSS_SET_ATTR((lpcnet_sample_pair_kernel<true, false, 12, false>));
-            DSS_SET_ATTR((lpcnet_sample_pair_kernel<false, true, 10, false>));  DSS_SET_ATTR((lpcnet_sample_pair_kernel<false, true, 12, false>));
-            DSS_SET_ATTR((lpcnet_sample_pair_kernel<false, false, 10, true>));  DSS_SET_ATTR((lpcnet_sample_pair_kernel<false, false, 12, true>));
-            DSS_SET_ATTR((lpcnet_sample_pair_kernel<true, false, 10, true>));   DSS_SET_ATTR((lpcnet_sample_pair_kernel<true, false, 12, true>));
-#undef DSS_SET_ATTR
-            attr_set |= 1ull << (dev & 63);
-        }
-    }
-    const dim3 grid((n_utts + 1) / 2), block(512);
-#define DSS_LAUNCH(T, S2, R)                                                                                           \
-    do {                                                                                                               \
-        if (z10) hipLaunchKernelGGL((lpcnet_sample_pair_kernel<T, S2, 10, R>), grid, block, dyn, s, m, b, n_utts, n_frames, d_pcm); \
-        else hipLaunchKernelGGL((lpcnet_sample_pair_kernel<T, S2, 12, R>), grid, block, dyn, s, m, b, n_utts, n_frames, d_pcm);     \
-    } while (0)
-    if (trace == 2) DSS_LAUNCH(false, true, false);
-    else if (trace && ragged) DSS_LAUNCH(true, false, true);
-    else if (trace) DSS_LAUNCH(true, false, false);
-    else if (ragged) DSS_LAUNCH(false, false, true);
-    else DSS_LAUNCH(false, false, false);
-#undef DSS_LAUNCH
+    const bool stamp = trace == 2;
+    const int z = m.zr_cap <= 10 ? 10 : 12;
+    const void *fn = nullptr;
+    for (const PairVariant &v : pair_variants)
+        if (v.trace == (trace && !stamp) && v.stamp == stamp && v.z == z && v.ragged == ragged) fn = v.fn;
+    if (!fn) { dss_set_error("pair kernel: no instantiation for this call"); return DSS_EINVAL; }
+    if (const int rc = pair_lds_limit.raise(pair_variants, DSS_PAIR_HBLK_BYTES)) return rc;
+    void *args[] = {(void *)&m, (void *)&b, &n_utts, &n_frames, &d_pcm};
+    hipLaunchKernel(fn, dim3((n_utts + 1) / 2), dim3(512), args, dyn, s);
     DSS_HIP_CHECK(hipGetLastError());
     return DSS_OK;
 }
