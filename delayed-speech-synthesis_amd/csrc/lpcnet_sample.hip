@@ -10,7 +10,7 @@
 //   GRU A z- and r-gate 8x4 blocks (15k floats)  VGPRs of waves 0..5 (lane = unit; 8 slots per gate on waves 0..3,
 //                                                 all DSS_ZRC on waves 4..5, which get the heaviest row groups)
 //   GRU A h-gate 8x4 blocks (30k floats)          LDS, one 128-byte record per block, grouped per wave
-//   GRU B input weights (18k floats)              inputs 0..95 and 288..351 in VGPRs of waves 6 and 7 (lane = row); the other 224
+//   GRU B input weights (18k floats)              inputs 0..95 and 296..359 in VGPRs of waves 6 and 7 (lane = row); the other 224
 //                                                 stream from L2 every sample into the registers that will hold their products
 //   dual-FC (8k floats)                           VGPRs of waves 0..3 (lane = tree node)
 // Roles inside the 512-thread workgroup (8 waves, 2 per SIMD); three workgroup barriers B C D per sample (a fourth,
@@ -75,11 +75,17 @@
 // LDS answers in 50+ cycles while the six GRU A waves run their h chains, so DSS_GBG_MUL keeps several pairs of reads in flight.
 // (round 5: 80 / 104 / 104 / 96 -- a shorter on-the-fly segment now that the GRU A waves' address arithmetic is lighter; same-box
 //  A/B against 96 / 96 / 96 / 96: 38.3 vs 38.5 ms.  80/96/112 the same, 64/96/128, 80/96/128 and 96/96/112 slower: 38.9 / 41.4 / 40.9)
+// (profiles/early_relay_experiment.md, on the short activations: 96 / 96 / 104 / 88 with GB4H = 24 -- wave 7 forms 8 products fewer in
+//  front of segment 1's sums and multiplies 8 inputs fewer in place behind segment 2, wave 6 sums 16 inputs more on the fly.  Same-box
+//  A/B, parent 80/104/104/96 + 32: 36.50 ms; the split alone 36.35, with GB4H = 24 35.95, 16 or 40 36.3; 96/104/104/80 with GB4H 16 or 24
+//  36.27; 80/104/104/96 with 24 36.6; 96/96/96/96 36.4, 96/104/96/88 36.7, 80/112/104/88 36.5, 64/112/112/96 37.6; a GB1 of 112 or a GB3
+//  of 112 next to a GB1 of 96 spills on wave 6: 41-43 ms.  Starting segment 1 before barrier B was not built: its inputs are not two
+//  waves' -- the host sorts row groups by weight, units 0..7 of the seeded model are wave 4's -- and no GRU A wave waits there for long.)
 #ifndef GB1
-#define GB1 80
+#define GB1 96
 #endif
 #ifndef GB2
-#define GB2 104
+#define GB2 96
 #endif
 #ifndef GB3
 #define GB3 104
@@ -116,6 +122,8 @@
                                   //   Later (profiles/wave7_dtob_experiment.md), once wave 7 no longer waits for the threshold table between D and B:
                                   //   D..B  wave 3 at 3, level with wave 7 on its SIMD;  B..C  wave 6 at 0 from its last hand-over on (speculation
                                   //         and thresholds are needed at barrier C only; its SIMD neighbour, wave 2, ends its h chain 150 cycles before C).
+                                  //   Since then the waits of waves 0, 1 at barrier B are gone: stamped, wave 0 is the last wave there and wave 1
+                                  //   20-45 cycles ahead of it (profiles/early_relay_experiment.md).
 #ifndef DSS_ACT_SHORT
 #define DSS_ACT_SHORT 7           // sites that take the short table activations of lpcnet_device.h (same bits, 10 dependent instructions per
 #endif                            //   round instead of 17):  1 GRU A z/r, 2 GRU A h, 4 GRU B gates (wave 7), 8 dual-FC.  Never in the extended
@@ -124,7 +132,7 @@
                                   //   8 LOSES wherever it is added (alone 37.63, 4 + 8 37.35, 1 + 2 + 8 36.98, all four 36.63): the dual-FC keeps
                                   //   the plain form.
 #ifndef GB4H
-#define GB4H 32
+#define GB4H 24
 #endif
 #define GB4R (GB4 - GB4H)
 static_assert(GB4 <= GB2, "segment 4's products reuse segment 2's registers");
@@ -465,12 +473,13 @@ __device__ __forceinline__ void dss_role_a(SampleLds &L, float *hblk_lds, const 
                 }
                 L.state_a[DSS_NEW(cur)][unit] = st;
                 if (STAMP) { asm volatile("" :: "v"(st)); const unsigned t = DSS_NOW(); sa[3] += t - ta; ta = t; }
+                else if (DSS_RELAY_STAMP) { asm volatile("" :: "v"(st) : "memory"); ta = DSS_NOW(); }
             }
             __syncthreads();                                                        // barrier B
             if (DSS_PHASE_PRIO && !HAS_FC) __builtin_amdgcn_s_setprio(0);
             if (DSS_PHASE_PRIO && HAS_FC && wave == 3) __builtin_amdgcn_s_setprio(0);
             if (STAMP) { const unsigned t = DSS_NOW(); sa[4] += t - ta; ta = t; }
-            else if (DSS_RELAY_STAMP) ta = DSS_NOW();
+            else if (DSS_RELAY_STAMP) { const unsigned t = DSS_NOW(); sa[4] += t - ta; ta = t; }   // new state stored .. barrier B released
 #if DSS_KNOCKOUT      /* development builds only (results WRONG on purpose): what the relay's SIMD neighbours cost it, profiles/r5_latency_kernel_experiment.md */
             if (!((DSS_KNOCKOUT & 1) && (wave == 2 || wave == 3)) && !((DSS_KNOCKOUT & 4) && (wave == 0 || wave == 1))) { DSS_H_CHAIN(L.state_a[DSS_NEW(cur)]) }
             if (!((DSS_KNOCKOUT & 2) && (wave == 2 || wave == 3))) { DSS_ZR_PRODUCTS(L.state_a[DSS_NEW(cur)]) }
@@ -548,8 +557,10 @@ __device__ __forceinline__ void dss_role_a(SampleLds &L, float *hblk_lds, const 
     __syncthreads();                                                                // final barrier
     if (STAMP && lane == 0 && b.trace_exc)
         for (int k = 0; k < 9; ++k) b.trace_exc[((size_t)utt * 6 + wave) * 9 + k] = (float)sa[k];
-    if (DSS_RELAY_STAMP && !STAMP && lane == 0 && blockIdx.x == 0)
+    if (DSS_RELAY_STAMP && !STAMP && lane == 0 && blockIdx.x == 0) {
         reinterpret_cast<unsigned *>(pcm_out_dbg + (size_t)utt * n_frames * DSS_FRAME_SIZE)[16 + wave] = sa[5];
+        reinterpret_cast<unsigned *>(pcm_out_dbg + (size_t)utt * n_frames * DSS_FRAME_SIZE)[24 + wave] = sa[4];
+    }
     b.gru_a_state[(size_t)slot * NA + unit] = st;
 }
 
@@ -778,9 +789,10 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
                 float sb_old = L.state_b[lane & (NB - 1)];           // the h lanes' own unit: read here, not after the chain
                 asm volatile("" : "+v"(rec), "+v"(sb_old));
                 if (STAMP && seq > 1) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); stamp_acc[6] += DSS_NOW() - t_d; }
+                else if (DSS_RELAY_STAMP) t_d = DSS_NOW();
                 __syncthreads();                                                        // barrier B
                 if (STAMP) { const unsigned t = DSS_NOW(); stamp_acc[2] += t - t_prev; t_prev = t; }
-                else if (RS) t_prev = DSS_NOW();
+                else if (RS) { t_prev = DSS_NOW(); stamp_acc[6] += t_prev - t_d; }      // this wave's wait at barrier B
                 // While wave 6 runs segment 1, this wave forms the products of segment 2 (weights from L2); while wave 6 sums
                 // segment 3, those of segment 4's first GB4R inputs into the same registers.  Its own part of the chain is sums only.
                 const float *an = L.state_a[DSS_NEW(cur)];
@@ -858,8 +870,10 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
             b.trace_pcm[(size_t)gridDim.x * 6 + utt] = (float)stamp_acc[6];      // behind the six-slot records of all rows
             if (gridDim.x == 1) for (int k = 0; k < 6; ++k) b.trace_pcm[64 + k] = (float)r7[k];
         }
-        if (DSS_RELAY_STAMP && !STAMP && lane == 0 && blockIdx.x == 0)
+        if (DSS_RELAY_STAMP && !STAMP && lane == 0 && blockIdx.x == 0) {
             for (int k = 0; k < 8; ++k) reinterpret_cast<unsigned *>(pcm_out + (size_t)utt * n_frames * DSS_FRAME_SIZE)[k] = r7[k];
+            reinterpret_cast<unsigned *>(pcm_out + (size_t)utt * n_frames * DSS_FRAME_SIZE)[13] = stamp_acc[6];
+        }
         if (lane < NB) b.gru_b_state[(size_t)slot * NB + lane] = L.state_b[lane];
         if (lane < DSS_LPC_ORDER) b.last_sig[(size_t)slot * DSS_LPC_ORDER + lane] = ls_lane;
         if (lane == 0) {
