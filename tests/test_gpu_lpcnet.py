@@ -657,13 +657,16 @@ def test_pair_kernel_other_models_and_selection(oracle):
         lpcnet.load_model(synthetic_blob(0))
 
 
+PAIR_RULE_ROWS = 601        # more rows than an MI355X has CUs (256): the automatic rule gives such a call to the pair kernel
+
+
 def test_pair_kernel_is_chosen_beyond_one_utterance_per_cu(golden, model):
     """601 utterances on 256 CUs: the automatic choice (one full round of 512 rows on the pair kernel, the remaining 89 as
     one round of the one-utterance kernel, which starts at row 512: b.utt0), the forced pair kernel (an odd count: its last
     workgroup is half filled) and the forced latency kernel agree bit for bit with each other and with the golden utterance."""
     from dss_amd.lpcnet import LPCNetBatch
     g = golden("lpcnet_self.npz")
-    B, F = 601, 30
+    B, F = PAIR_RULE_ROWS, 30
     feats = np.stack([synthetic_features(2, F)] * B)
     feats[1::2] = synthetic_features(5, F)
     gpu = LPCNetBatch(B, F)
