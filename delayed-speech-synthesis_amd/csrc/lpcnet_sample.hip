@@ -28,6 +28,10 @@
 // Issue priorities follow the phase (DSS_PHASE_PRIO): the relay waves run at 3 from barrier D to barrier C (wave 6 only until it has
 // handed segment 3 over) and at 0 from C to D, where they only fetch the next sample's weights beside the dual-FC of waves 2, 3;
 // from D to B waves 4, 5 run at 1, ahead of waves 0, 1, and wave 3 at 3 beside wave 7.
+// Between barriers D and B every instruction of a GRU A wave is on the sample's serial path, and a wave issues about one instruction
+// per 5 cycles whatever its kind, so what the result does not need is kept out of there (DSS_SERIAL_SLOTS): the length of a wave's
+// z/r lists is a constant of the code, not a value tested per pair of slots; the tree walk keeps its node index in heap form; a
+// table's row offset is one scalar product; the relay's tags are in their register before a segment's last sums.
 // Summation order inside every row is exactly the C source's (one product at a time, ascending input),
 // and the library is built with -ffp-contract=off, so results are bit-identical to the scalar C path.
 #include <cstddef>
@@ -51,6 +55,8 @@
             c0 = c0n; c1 = c1n;                                                                  \
         }                                                                                        \
     }
+// segment 1 of GRU B (DSS_GB_CHAIN): its hand-over tag goes into its register in front of the chain's last group of 16 inputs
+#define DSS_GB_BEFORE_LAST_GROUP { DSS_GB_TAG(seq * 4 + 1) }
 #include "lpcnet_sample_common.h"
 #undef HC
 // diagnostic build: the low 32 bits of the shader clock (differences of stamps; 64-bit accumulators cost the stamped build registers)
@@ -131,6 +137,16 @@
                                   //   (profiles/activation_experiment.md): 1 alone 37.44, 2 alone 37.32, 1 + 2 36.70, 4 alone 36.90, 1 + 2 + 4 36.58;
                                   //   8 LOSES wherever it is added (alone 37.63, 4 + 8 37.35, 1 + 2 + 8 36.98, all four 36.63): the dual-FC keeps
                                   //   the plain form.
+// DSS_SERIAL_SLOTS (lpcnet_sample_common.h; profiles/serial_path_slots_experiment.md): issue slots taken off the serial path, one bit each --
+//   1  (not in the code any more) the order of the GRU A sums as a template constant, 8 VALU -> 2 per sample: measured, no gain alone and
+//      0.15 ms slower beside the other four; it doubled the instantiations.  The order stays the model's run-time flag
+//   2  role A compiled for its wave's z/r list length (NZ, dss_role_a_len): no s_and_b64 + s_cbranch per two slots inside the chains
+//   4  the tree walk in heap form: 19 scalar instructions instead of 24
+//   8  embedding rows addressed as SGPR base + (index * row bytes + lane * 12): 2 instructions per table instead of ~6
+//  16  the hand-over tag written to its register in front of a segment's last sums: the last v_add_f32 is followed by the ds_write_b64
+// Same-box A/B, 256 x 1 s: each switch ALONE is 0.0 ... +0.6 ms behind the parent, all five together are 0.5 ms ahead of it, the four
+// that ship (30) 0.7; taking any one of those four out of the five costs 0.15 ... 0.9 ms (the addresses most).  The note has every
+// arm.  Bit 2 multiplies the role's code (dss_role_a_len).
 #ifndef GB4H
 #define GB4H 24
 #endif
@@ -232,9 +248,13 @@ __device__ __forceinline__ float *dss_tansig_dy(SampleLds &L) { return L.state_a
         }                                                                                        \
     }
 // the sums of a pre-multiplied segment: one dependent chain, input order
-#define DSS_GB_SUMS(N)                                                                           \
+#define DSS_GB_SUMS(N) DSS_GB_SUMS_(N, false, 0)
+// ... of a segment that is published with tag V: DSS_GB_TAG in front of the last four sums
+#define DSS_GB_SUMS_TAG(N, V) DSS_GB_SUMS_(N, true, V)
+#define DSS_GB_SUMS_(N, TAGGED, V)                                                               \
     {                                                                                            \
         _Pragma("unroll") for (int q = 0; q < (N) / 4; ++q) {                                    \
+            if constexpr (TAGGED) if (q == (N) / 4 - 1) { DSS_GB_TAG(V) }                        \
             acc += PQ[q].x;                                                                      \
             acc += PQ[q].y;                                                                      \
             acc += PQ[q].z;                                                                      \
@@ -246,11 +266,25 @@ __device__ __forceinline__ float *dss_tansig_dy(SampleLds &L) { return L.state_a
 // (4 * sample number + segments done): the taker polls its own lane's word, and the read that sees every lane's tag has the
 // sums in it -- one LDS round trip per hand-over instead of flag, wait, sums.  Hand-written ds_ instructions: the word must be
 // written and read as ONE 8-byte access, and __builtin_bit_cast of a vector ELEMENT reads element 0 with this clang.
+// The tag depends on the sample number alone.  DSS_GB_TAG puts it into the vector register beside the running sum BEFORE the
+// segment's last sums (pinned by an empty asm), so that the last v_add_f32 is followed by the ds_write_b64 and not by a shift, an or
+// and a move (DSS_SERIAL_SLOTS & 16).  Not before the whole segment: the relay waves have no register to spare for that long, the
+// product registers of the sums already made are free by then.
+// DSS_GB_PUBLISH takes the pre-set register only where a DSS_GB_TAG of the SAME value was expanded since the last publish (gb_tag_v;
+// both tests fold at compile time): a publish without its tag, or with another value, writes V as before instead of leaving the
+// taker polling for a tag that never comes.
+#define DSS_GB_TAG(V)                                                                            \
+    if constexpr ((DSS_SERIAL_SLOTS & 16) != 0) {                                                \
+        gb_tag_v = (int)(V);                                                                     \
+        gb_tag = __builtin_bit_cast(float, gb_tag_v);                                            \
+        asm volatile("" : "+v"(gb_tag));                                                         \
+    }
 #define DSS_GB_PUBLISH(V)                                                                        \
     {                                                                                            \
         const int tagi_ = (int)(V);                                                              \
-        const f32x2 pw_ = {acc, __builtin_bit_cast(float, tagi_)};                               \
+        const f32x2 pw_ = {acc, ((DSS_SERIAL_SLOTS & 16) && gb_tag_v == tagi_) ? gb_tag : __builtin_bit_cast(float, tagi_)}; \
         asm volatile("ds_write_b64 %0, %1" :: "v"(gb_addr), "v"(pw_) : "memory");                \
+        gb_tag_v = 0;                            /* (no tag is 0: they start at 4 * 1 + 1) */   \
     }
 #define DSS_GB_AWAIT(V)                                                                          \
     {                                                                                            \
@@ -319,7 +353,11 @@ __device__ __forceinline__ float *dss_tansig_dy(SampleLds &L) { return L.state_a
 #define DSS_NEW(cur) (EXT ? ((cur) ^ 1) : 0)
 #define DSS_OLD(cur) (EXT ? (cur) : 0)
 
-template <bool TRACE, bool STAMP, int Z, bool HAS_FC, bool EXT>
+// NZ: the wave's z/r register slots in use (m.wave_nzr) as a compile-time constant, or -1 = read at run time.  The length is fixed
+// for the whole call, but as a run-time value it is tested in front of every two slots INSIDE the dependent z/r chains: one
+// s_and_b64 + one s_cbranch per pair, two more in front, twelve issue slots a sample on a 10-slot wave.  The kernel picks the
+// role's copy once, outside the frame loop (dss_role_a_len); the runs then carry no test at all.
+template <bool TRACE, bool STAMP, int Z, bool HAS_FC, bool EXT, int NZ = -1>
 __device__ __forceinline__ void dss_role_a(SampleLds &L, float *hblk_lds, const DssModelDev &m, const DssBatchDev &b,
                                            int n_frames, int utt, int slot, int nf, int fc0, int tid, int wave, int lane,
                                            short *pcm_out_dbg)
@@ -328,7 +366,7 @@ __device__ __forceinline__ void dss_role_a(SampleLds &L, float *hblk_lds, const 
     const int unit = m.unit_of[tid];                             // z/r chains + gates of this unit
     const int uh = m.unit_h[tid];                                // h-gate chain of this (other) unit
     const int nh = __builtin_amdgcn_readfirstlane(m.wave_nh[wave]);
-    const int nzr = __builtin_amdgcn_readfirstlane(m.wave_nzr[wave]);
+    const int nzr = NZ >= 0 ? NZ : __builtin_amdgcn_readfirstlane(m.wave_nzr[wave]);
     const int nzt = EXT ? __builtin_amdgcn_readfirstlane(m.wave_nzt[wave]) : 0;   // z/r blocks beyond the register slots (LDS records)
     const char *hw = reinterpret_cast<const char *>(hblk_lds + m.grp_hoff[tid >> 3]) + (lane & 7) * 16;
     f32x4 WZ[2 * ZRC];                                           // [0,ZRC) z slots, [ZRC,2ZRC) r slots
@@ -366,6 +404,8 @@ __device__ __forceinline__ void dss_role_a(SampleLds &L, float *hblk_lds, const 
     const int level = 31 - __clz(tid | 1);                       // FC node = (1 << level) | prefix
     const bool recur_first = m.h.gru_a_order == DSS_GRUA_RECUR_FIRST;     // wave-uniform (kernel argument)
     const float *dtab = dss_tansig_dy(L);
+    // byte offset of this lane's nine values inside a row of the lane-ordered embedding tables (DSS_SERIAL_SLOTS & 8)
+    const unsigned emb_lane = (unsigned)tid * 12u;
     int cur = 0, seq = 0;
     float st = L.state_a[0][unit];
     unsigned sa[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, ta = 0;   // diagnostic build only ([8]: barrier D .. the first embedding load is about to go out)
@@ -413,9 +453,19 @@ __device__ __forceinline__ void dss_role_a(SampleLds &L, float *hblk_lds, const 
                 // the nine embedding values of this lane: three 12-byte loads from the lane-ordered copies of the tables
                 // (m.embed_lane: [index][lane][gate]), 768 contiguous bytes per wave and table
                 typedef float f32x3 __attribute__((ext_vector_type(3)));
-                const f32x3 es = *reinterpret_cast<const f32x3 *>(m.embed_lane[0] + ((unsigned)si * NA + (unsigned)tid) * 3);
-                const f32x3 ep = *reinterpret_cast<const f32x3 *>(m.embed_lane[1] + ((unsigned)pi * NA + (unsigned)tid) * 3);
-                const f32x3 ee = *reinterpret_cast<const f32x3 *>(m.embed_lane[2] + ((unsigned)ei * NA + (unsigned)tid) * 3);
+                // Row offsets in bytes: the row (NA * 12 bytes) times the index stays scalar, one vector instruction adds the lane's
+                // offset, and the load takes the table's SGPR base with that 32-bit offset (256 rows: far below 2^32).  As an index
+                // into float[] the same sum cost an add, a multiply by 3, a shift and a 64-bit vector address per table.
+                f32x3 es, ep, ee;
+                if constexpr ((DSS_SERIAL_SLOTS & 8) != 0) {
+                    es = *reinterpret_cast<const f32x3 *>(reinterpret_cast<const char *>(m.embed_lane[0]) + ((unsigned)si * (NA * 12u) + emb_lane));
+                    ep = *reinterpret_cast<const f32x3 *>(reinterpret_cast<const char *>(m.embed_lane[1]) + ((unsigned)pi * (NA * 12u) + emb_lane));
+                    ee = *reinterpret_cast<const f32x3 *>(reinterpret_cast<const char *>(m.embed_lane[2]) + ((unsigned)ei * (NA * 12u) + emb_lane));
+                } else {
+                    es = *reinterpret_cast<const f32x3 *>(m.embed_lane[0] + ((unsigned)si * NA + (unsigned)tid) * 3);
+                    ep = *reinterpret_cast<const f32x3 *>(m.embed_lane[1] + ((unsigned)pi * NA + (unsigned)tid) * 3);
+                    ee = *reinterpret_cast<const f32x3 *>(m.embed_lane[2] + ((unsigned)ei * NA + (unsigned)tid) * 3);
+                }
                 const float es0 = es.x, es1 = es.y, es2 = es.z, ep0 = ep.x, ep1 = ep.y, ep2 = ep.z, ee0 = ee.x, ee1 = ee.y, ee2 = ee.z;
                 if (STAMP) { const unsigned t = DSS_NOW(); sa[0] += t - ta; ta = t; }
                 const float gz = ((cz + es0) + ep0) + ee0;                          // compute_gru_a_input
@@ -429,7 +479,7 @@ __device__ __forceinline__ void dss_role_a(SampleLds &L, float *hblk_lds, const 
                 // what is left on the critical path are the dependent sums, z and r chains interleaved
 #pragma unroll
                 for (int s2 = 0; s2 < ZRC; s2 += 2) {
-                    if (s2 >= nzr) break;
+                    if (s2 >= nzr) break;                        // (folds where the role is compiled for its list length, NZ)
 #pragma unroll
                     for (int u = 0; u < 2; ++u) {
                         az += PR[s2 + u].x; ar += PR[ZRC + s2 + u].x;
@@ -564,6 +614,20 @@ __device__ __forceinline__ void dss_role_a(SampleLds &L, float *hblk_lds, const 
     b.gru_a_state[(size_t)slot * NA + unit] = st;
 }
 
+// Role A compiled for the wave's list length where that is the role's capacity or one pair of slots below it (the host sorts
+// the row groups by weight: the benchmark's model runs 10 / 8 slots on waves 4, 5 and 8 / 6 / 6 / 6 on waves 2, 3, 1, 0), for
+// any length otherwise.  Three copies of the role's code; more lengths were not worth their build time and code size.
+template <bool TRACE, bool STAMP, int Z, bool HAS_FC, bool EXT, typename... Args>
+__device__ __forceinline__ void dss_role_a_len(const DssModelDev &m, int wave, Args &&... args)
+{
+    if constexpr ((DSS_SERIAL_SLOTS & 2) != 0 && !TRACE && !STAMP && Z <= 10) {      // (the 12-slot role spills: its exact copies spilled twice as much)
+        const int nzr = __builtin_amdgcn_readfirstlane(m.wave_nzr[wave]);
+        if (nzr == Z) return dss_role_a<TRACE, STAMP, Z, HAS_FC, EXT, Z>(args...);
+        if (nzr == Z - 2) return dss_role_a<TRACE, STAMP, Z, HAS_FC, EXT, Z - 2>(args...);
+    }
+    dss_role_a<TRACE, STAMP, Z, HAS_FC, EXT, -1>(args...);
+}
+
 // RAGGED: rows name their decoder slot and frame count (b.slot_of / b.count_of).  A separate instantiation, so the
 // uniform form keeps its register allocation (the two extra live scalars cost 1.3 % there); the trace build always
 // honours the lists.
@@ -607,9 +671,9 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
     __syncthreads();
 
     if (wave < 4) {
-        dss_role_a<TRACE, STAMP, (Z < 8 ? Z : 8), true, EXT>(L, hblk_lds, m, b, n_frames, utt, slot, nf, fc0, tid, wave, lane, pcm_out);
+        dss_role_a_len<TRACE, STAMP, (Z < 8 ? Z : 8), true, EXT>(m, wave, L, hblk_lds, m, b, n_frames, utt, slot, nf, fc0, tid, wave, lane, pcm_out);
     } else if (wave < 6) {
-        dss_role_a<TRACE, STAMP, Z, false, EXT>(L, hblk_lds, m, b, n_frames, utt, slot, nf, fc0, tid, wave, lane, pcm_out);
+        dss_role_a_len<TRACE, STAMP, Z, false, EXT>(m, wave, L, hblk_lds, m, b, n_frames, utt, slot, nf, fc0, tid, wave, lane, pcm_out);
     } else if (wave == 6) {
         // =====================================================================================================
         // role B1: GRU B, segments 1 and 3; lane = row (0..15 z, 16..31 r, 32..47 h)
@@ -638,6 +702,8 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
             const float gbc = b.frame_out[((size_t)utt * n_frames + f) * DSS_COND_STRIDE + 3 * NA + row];
             for (int i = 0; i < DSS_FRAME_SIZE; ++i) {
                 float acc = gbb0 + gbc;                                                 // compute_gruB
+                float gb_tag = 0.f;
+                int gb_tag_v = 0;                                                       // the value DSS_GB_TAG has put into gb_tag, 0 = none
                 ++seq;
                 if (seq == 1) {
                     DSS_GBG_LOADS(GB3, (GB1 + GB2) / 4)                                 // (every later sample: loaded at the end of the one before)
@@ -657,7 +723,7 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
                 DSS_RSTAMP(PQ[GB3 / 4 - 1], r6[1], t6)
                 DSS_GB_AWAIT(seq * 4 + 2)
                 DSS_RSTAMP(acc, r6[2], t6)
-                DSS_GB_SUMS(GB3)
+                DSS_GB_SUMS_TAG(GB3, seq * 4 + 3)
                 DSS_GB_PUBLISH(seq * 4 + 3)
                 DSS_RSTAMP(acc, r6[3], t6)
 #if DSS_RELAY_MASK
@@ -799,12 +865,13 @@ lpcnet_sample_kernel(DssModelDev m, DssBatchDev b, int n_frames, short *__restri
 #if DSS_RELAY_MASK
                 if (lane < NB3) {
 #endif
-                float acc;
+                float acc, gb_tag = 0.f;
+                int gb_tag_v = 0;
                 DSS_GBG_MUL(an + GB1, GB2, DSS_D2)
                 DSS_RSTAMP(PQ[GB2 / 4 - 1], r7[0], t_prev)
                 DSS_GB_AWAIT(seq * 4 + 1)
                 DSS_RSTAMP(acc, r7[1], t_prev)
-                DSS_GB_SUMS(GB2)
+                DSS_GB_SUMS_TAG(GB2, seq * 4 + 2)
                 DSS_GB_PUBLISH(seq * 4 + 2)
                 DSS_RSTAMP(acc, r7[2], t_prev)
                 // Segment 4: the weights of its last GB4H inputs from L2 into the registers segment 2 has left (issued BEFORE the

@@ -165,6 +165,10 @@ __device__ __forceinline__ unsigned dss_lds_addr(const void *p)
 // One s_waitcnt per group of four reads instead of the compiler's one per read (gfx9 encoding, vmcnt/expcnt left at
 // their maxima): a wave issues about one instruction per 5 cycles whatever its kind, waits included.
 #define DSS_WAIT_LGKM(N) __builtin_amdgcn_s_waitcnt(0xC07F | ((N) << 8))
+// what the including kernel does in front of the chain's last group of 16 inputs, whichever buffer holds it (lpcnet_sample.hip: the hand-over tag)
+#ifndef DSS_GB_BEFORE_LAST_GROUP
+#define DSS_GB_BEFORE_LAST_GROUP
+#endif
 #define DSS_GB_CHAIN(AN, N)                                                                      \
     {                                                                                            \
         f32x4 avA[4], avB[4];                                                                    \
@@ -179,6 +183,7 @@ __device__ __forceinline__ unsigned dss_lds_addr(const void *p)
             __builtin_amdgcn_sched_barrier(0);   /* keep the prefetch ahead of the arithmetic */ \
             if (g + 1 < (N) / 16) DSS_WAIT_LGKM(4); else DSS_WAIT_LGKM(0);                       \
             __builtin_amdgcn_sched_barrier(0);                                                   \
+            if (g + 1 >= (N) / 16) { DSS_GB_BEFORE_LAST_GROUP }      /* an odd number of groups: this is the last */ \
             DSS_GB_GROUP(avA, g)                                                                 \
             __builtin_amdgcn_sched_barrier(0);                                                   \
             if (g + 2 < (N) / 16) DSS_GB_LOAD(avA, AN, g + 2)                                    \
@@ -186,6 +191,7 @@ __device__ __forceinline__ unsigned dss_lds_addr(const void *p)
             if (g + 1 < (N) / 16) {                                                              \
                 if (g + 2 < (N) / 16) DSS_WAIT_LGKM(4); else DSS_WAIT_LGKM(0);                   \
                 __builtin_amdgcn_sched_barrier(0);                                               \
+                if (g + 2 >= (N) / 16) { DSS_GB_BEFORE_LAST_GROUP }                              \
                 DSS_GB_GROUP(avB, g + 1)                                                         \
             }                                                                                    \
             __builtin_amdgcn_sched_barrier(0);                                                   \
@@ -214,8 +220,14 @@ __device__ __forceinline__ unsigned dss_lds_addr(const void *p)
     }
 
 // Tree walk over the 256 decision bits the dual-FC waves left in BITS (8 words): every operand is wave-uniform, so this is scalar
-// bit arithmetic.  8 levels, 3 scalar instructions each: test the node's bit (s_bitcmp1_b64 -> SCC), val = 2*val + SCC
-// (s_addc_u32), next node index.  Nodes 1..63 live in m0, 64..127 in m1, 128..191 in m2, 192..255 in m3.
+// bit arithmetic.  The node index is kept in heap form, level marker included (n = 1; n = 2n + bit(n)): a level is two scalar
+// instructions, test the node's bit (s_bitcmp1_b64 -> SCC) and n = n + n + SCC (s_addc_u32), whose result already IS the child's
+// index; the marker comes off once at the end.  19 instructions (24 with the prefix kept bare and the index rebuilt by an s_or_b32
+// per level; tools/verify/tree_walk_check.c compares the two forms).  Nodes 1..63 live in m0, 64..127 in m1, 128..191 in m2,
+// 192..255 in m3; s_bitcmp1_b64 takes only the low six bits of its index, so from level 6 on n serves as it is.
+#ifndef DSS_SERIAL_SLOTS
+#define DSS_SERIAL_SLOTS 30       // instruction slots taken off the serial path between barriers D and B (lpcnet_sample.hip tells what each bit is;
+#endif                            //   the pair kernel takes bit 4, the tree walk, from here)
 #define DSS_TREE_WALK_AT(VAL, BITS)                                                                       \
     {                                                                                            \
         const uint4 b0 = *reinterpret_cast<const uint4 *>(&(BITS)[0]);                           \
@@ -224,22 +236,39 @@ __device__ __forceinline__ unsigned dss_lds_addr(const void *p)
         const unsigned long long m1 = ((unsigned long long)__builtin_amdgcn_readfirstlane(b0.w) << 32) | (unsigned)__builtin_amdgcn_readfirstlane(b0.z); \
         const unsigned long long m2 = ((unsigned long long)__builtin_amdgcn_readfirstlane(b1.y) << 32) | (unsigned)__builtin_amdgcn_readfirstlane(b1.x); \
         const unsigned long long m3 = ((unsigned long long)__builtin_amdgcn_readfirstlane(b1.w) << 32) | (unsigned)__builtin_amdgcn_readfirstlane(b1.z); \
-        int tnode_;                                                                              \
         unsigned long long mm_;                                                                  \
-        asm volatile(                                                                            \
-            "s_mov_b32 %0, 0\n\t"                                                                \
-            "s_bitcmp1_b64 %3, 1\n\t"          "s_addc_u32 %0, %0, %0\n\t"                       \
-            "s_or_b32 %1, %0, 2\n\t"           "s_bitcmp1_b64 %3, %1\n\t"   "s_addc_u32 %0, %0, %0\n\t" \
-            "s_or_b32 %1, %0, 4\n\t"           "s_bitcmp1_b64 %3, %1\n\t"   "s_addc_u32 %0, %0, %0\n\t" \
-            "s_or_b32 %1, %0, 8\n\t"           "s_bitcmp1_b64 %3, %1\n\t"   "s_addc_u32 %0, %0, %0\n\t" \
-            "s_or_b32 %1, %0, 16\n\t"          "s_bitcmp1_b64 %3, %1\n\t"   "s_addc_u32 %0, %0, %0\n\t" \
-            "s_or_b32 %1, %0, 32\n\t"          "s_bitcmp1_b64 %3, %1\n\t"   "s_addc_u32 %0, %0, %0\n\t" \
-            "s_bitcmp1_b64 %4, %0\n\t"         "s_addc_u32 %0, %0, %0\n\t"                       \
-            "s_cmp_lt_u32 %0, 64\n\t"          "s_cselect_b64 %2, %5, %6\n\t"                    \
-            "s_bitcmp1_b64 %2, %0\n\t"         "s_addc_u32 %0, %0, %0"                            \
-            : "=&s"(VAL), "=&s"(tnode_), "=&s"(mm_)                                              \
-            : "s"(m0), "s"(m1), "s"(m2), "s"(m3)                                                 \
-            : "scc");                                                                            \
+        if constexpr ((DSS_SERIAL_SLOTS & 4) != 0) {                                             \
+            asm volatile(                                                                        \
+                "s_bitcmp1_b64 %2, 1\n\t"          "s_addc_u32 %0, 1, 1\n\t"                      \
+                "s_bitcmp1_b64 %2, %0\n\t"         "s_addc_u32 %0, %0, %0\n\t"                    \
+                "s_bitcmp1_b64 %2, %0\n\t"         "s_addc_u32 %0, %0, %0\n\t"                    \
+                "s_bitcmp1_b64 %2, %0\n\t"         "s_addc_u32 %0, %0, %0\n\t"                    \
+                "s_bitcmp1_b64 %2, %0\n\t"         "s_addc_u32 %0, %0, %0\n\t"                    \
+                "s_bitcmp1_b64 %2, %0\n\t"         "s_addc_u32 %0, %0, %0\n\t"                    \
+                "s_bitcmp1_b64 %3, %0\n\t"         "s_addc_u32 %0, %0, %0\n\t"                    \
+                "s_cmp_lt_u32 %0, 0xc0\n\t"        "s_cselect_b64 %1, %4, %5\n\t"                 \
+                "s_bitcmp1_b64 %1, %0\n\t"         "s_addc_u32 %0, %0, %0\n\t"                    \
+                "s_and_b32 %0, %0, 0xff"                                                         \
+                : "=&s"(VAL), "=&s"(mm_)                                                         \
+                : "s"(m0), "s"(m1), "s"(m2), "s"(m3)                                             \
+                : "scc");                                                                        \
+        } else {                                                                                 \
+            int tnode_;                                                                          \
+            asm volatile(                                                                        \
+                "s_mov_b32 %0, 0\n\t"                                                            \
+                "s_bitcmp1_b64 %3, 1\n\t"          "s_addc_u32 %0, %0, %0\n\t"                   \
+                "s_or_b32 %1, %0, 2\n\t"           "s_bitcmp1_b64 %3, %1\n\t"   "s_addc_u32 %0, %0, %0\n\t" \
+                "s_or_b32 %1, %0, 4\n\t"           "s_bitcmp1_b64 %3, %1\n\t"   "s_addc_u32 %0, %0, %0\n\t" \
+                "s_or_b32 %1, %0, 8\n\t"           "s_bitcmp1_b64 %3, %1\n\t"   "s_addc_u32 %0, %0, %0\n\t" \
+                "s_or_b32 %1, %0, 16\n\t"          "s_bitcmp1_b64 %3, %1\n\t"   "s_addc_u32 %0, %0, %0\n\t" \
+                "s_or_b32 %1, %0, 32\n\t"          "s_bitcmp1_b64 %3, %1\n\t"   "s_addc_u32 %0, %0, %0\n\t" \
+                "s_bitcmp1_b64 %4, %0\n\t"         "s_addc_u32 %0, %0, %0\n\t"                   \
+                "s_cmp_lt_u32 %0, 64\n\t"          "s_cselect_b64 %2, %5, %6\n\t"                \
+                "s_bitcmp1_b64 %2, %0\n\t"         "s_addc_u32 %0, %0, %0"                        \
+                : "=&s"(VAL), "=&s"(tnode_), "=&s"(mm_)                                          \
+                : "s"(m0), "s"(m1), "s"(m2), "s"(m3)                                             \
+                : "scc");                                                                        \
+        }                                                                                        \
     }
 
 // a pair buffer of one 8x4 block: the block's four inputs for both utterances (two ds_read_b128)
