@@ -31,7 +31,10 @@ extern "C" void *dss_event_create(void)
 {
     if (dss_ensure_device()) return nullptr;
     hipEvent_t e = nullptr;
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { dss_set_error("hipEventCreate failed"); return nullptr; }
+    // hipEventReleaseToSystem: the event's completion releases the device's stores at system scope.  That is what HIP documents
+    // as making kernel stores into non-coherent page-locked memory (dss_host_alloc(bytes, 1)) visible to a host that learns of
+    // completion from dss_event_query / dss_event_synchronize, as the segment queue does.
+    if (hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventReleaseToSystem) != hipSuccess) { dss_set_error("hipEventCreate failed"); return nullptr; }
     return (void *)e;
 }
 
@@ -73,8 +76,11 @@ extern "C" int dss_stream_wait_event(void *hip_stream, void *event)
 }
 
 // Page-locked host memory for results that come back asynchronously (PCM of a finished segment).  cached != 0: ordinary
-// cacheable pages (hipHostMallocNonCoherent) -- the CPU reads them at memory speed; the device's writes are visible once the
-// copy's event has completed, which is the only time the host looks.  cached == 0: coherent (fine-grained) pages.
+// cacheable pages (hipHostMallocNonCoherent) -- the CPU reads them at memory speed; the device's writes are visible once an
+// event from dss_event_create recorded behind the copy has completed (such events release to system scope, see there), or
+// after dss_stream_synchronize on the copy's stream.  An event of any other origin has to be created with
+// hipEventReleaseToSystem to give the same guarantee.  That is the only time the host looks.  cached == 0: coherent
+// (fine-grained) pages.
 extern "C" void *dss_host_alloc(size_t bytes, int cached)
 {
     if (dss_ensure_device()) return nullptr;
@@ -169,7 +175,11 @@ extern "C" int dss_memcpy_d2h_async(void *host_dst, const void *d_src, size_t by
     if (((uintptr_t)host_dst | (uintptr_t)d_src) & 15) { dss_set_error("dss_memcpy_d2h_async: both pointers must be 16-byte aligned"); return DSS_EINVAL; }
     if (!bytes) return DSS_OK;
     void *dev_view = nullptr;                       // the device's address of the page-locked block (fails for pageable memory)
-    DSS_HIP_CHECK(hipHostGetDevicePointer(&dev_view, host_dst, 0));
+    if (hipHostGetDevicePointer(&dev_view, host_dst, 0) != hipSuccess || !dev_view) {
+        (void)hipGetLastError();                    // reported here: left in place it would fail the next launch's check, ours or torch's
+        dss_set_error("dss_memcpy_d2h_async: the destination is not page-locked memory (dss_host_alloc): it has no device view");
+        return DSS_EINVAL;
+    }
     const size_t n16 = bytes / 16;
     const int tail = (int)(bytes - n16 * 16);
     const unsigned grid = (unsigned)std::min<size_t>(std::max<size_t>((n16 + 255) / 256, 1), 512);

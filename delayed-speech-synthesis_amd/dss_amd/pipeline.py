@@ -289,11 +289,12 @@ class GatedStreamingPipeline(_DecoderMixin):
         offset_samples, pcm int16 host array, last); see SegmentSynthesisQueue.poll_chunks."""
         return self.queue.poll_chunks()
 
-    def close(self):
-        """Stop the queue's worker thread and release its lanes (also done when the pipeline is dropped)."""
+    def close(self, join_timeout: float = 5.0):
+        """Stop the queue's worker thread and release its lanes (also done when the pipeline is dropped).  Raises, and frees
+        nothing, when the worker has not come back within `join_timeout` seconds (SegmentSynthesisQueue.close)."""
         q = getattr(self, "queue", None)
         if q is not None:
-            q.close()
+            q.close(join_timeout)
 
     def __del__(self):
         try:

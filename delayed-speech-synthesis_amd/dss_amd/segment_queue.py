@@ -18,6 +18,13 @@ segments that closed on different streams are synthesised side by side and nothi
 ``poll()`` returns the segments finished since the last call; it never waits.  ``threaded=False`` keeps everything on the
 caller's thread (jobs are then launched and retired inside ``poll()`` / ``drain()``): the blocking mode uses it.
 
+Failure: an exception while a job is launched or retired ends the queue, and it stays ended.  The queue settles -- every open
+segment is retired as failed: nothing open, no stream busy, every pool row free -- and from then on ``submit``, ``poll``,
+``poll_chunks`` and ``drain`` raise RuntimeError("segment synthesis worker failed") with the original exception as its cause, every
+time they are called; nothing waits for a worker that is gone.  (Unthreaded, the call in which it happens raises the original
+exception itself.)  Audio of segments that had finished but were not yet polled is not salvaged.  ``close()`` still releases
+everything.
+
 Lanes: each has its own HIP stream, decoder scratch, vocoder scratch and result buffer.  ROCm maps streams onto
 ``GPU_MAX_HW_QUEUES`` hardware queues (4 by default) and two streams that share one run their kernels one after the other:
 a lane sharing the TICK's queue would put 140 ms of vocoder in front of a tick.  So the number of lanes defaults to
@@ -68,6 +75,23 @@ def select_job(pending, busy, max_rows):
             keep.append(sg)
         seen.add(sg.stream)
     return job, keep
+
+
+def pool_size(pool_rows, n_streams: int, rows_per_job: int) -> int:
+    """Rows of the segment pool: what the host asked for, else two per stream or four jobs' worth, whichever is more."""
+    if pool_rows is None:
+        return max(2 * int(n_streams), 4 * int(rows_per_job))
+    if int(pool_rows) < 1:
+        raise ValueError(f"pool_rows={pool_rows}: the segment pool needs at least one row")
+    return int(pool_rows)
+
+
+def check_fits(n_segments: int, pool_rows: int) -> None:
+    """One submit takes one pool row per segment and holds them until their jobs retire: more segments than the pool has rows
+    could wait for ever."""
+    if n_segments > pool_rows:
+        raise ValueError(f"{n_segments} segments in one submit, but the segment pool has {pool_rows} rows "
+                         "(pool_rows; split the submit or build the queue with a larger pool)")
 
 
 def progress_chunks(lengths, sent, counts, retired=False):
@@ -158,6 +182,7 @@ class SegmentSynthesisQueue:
         self._L = _lib.require_gpu()
         self.gate, self.S, self.C = gate, gate.S, int(n_features)
         self.cap, self.R, self.n_out = int(seg_cap), int(rows_per_job), int(n_out)
+        rows = self.rows = pool_size(pool_rows, self.S, self.R)
         self.module = decoder_module
         if decoder_factory is None and decoder_module is None:
             raise ValueError("a decoder kernel factory or a decoder module is needed")
@@ -165,7 +190,6 @@ class SegmentSynthesisQueue:
             n_lanes = default_lanes()
         self.progressive = bool(progressive)
         self.lanes = [_Lane(self._L, vocoder, decoder_factory, self.R, self.cap, self.n_out, self.progressive) for _ in range(int(n_lanes))]
-        rows = int(pool_rows or max(2 * self.S, 4 * self.R))
         self.pool = torch.zeros((rows, self.cap, self.C), dtype=torch.float32, device="cuda")
         self._free_rows = list(range(rows - 1, -1, -1))
         self._free_events: list = []
@@ -173,7 +197,7 @@ class SegmentSynthesisQueue:
         self.pending: collections.deque = collections.deque()
         self.busy = np.zeros(self.S, dtype=bool)              # streams with a job in flight
         self.finished: list = []
-        self.latencies_ms: list = []                          # segment closed (submit) -> PCM seen on the host (poll)
+        self.latencies_ms = collections.deque(maxlen=65536)   # segment closed (submit) -> PCM seen on the host (poll)
         self.chunks: list = []                                # progressive: (stream, tag, offset_samples, pcm, last) not yet polled
         self.first_pcm_latencies_ms = collections.deque(maxlen=65536)   # progressive: submit -> the piece at offset 0 on the host
         self.lane_wait_ms = collections.deque(maxlen=65536)             # submit -> launch on a lane
@@ -186,7 +210,7 @@ class SegmentSynthesisQueue:
         # shared between the caller's thread (submit / poll / drain) and the worker: pending, the free lists, finished, counters
         self._cv = threading.Condition(threading.RLock())
         self._stop = False
-        self._error = None
+        self._error = None                                    # what ended the queue; never cleared (see _fail)
         self._thread = None
         if threaded:
             self._thread = threading.Thread(target=self._worker, name="dss-segment-queue", daemon=True)
@@ -206,6 +230,7 @@ class SegmentSynthesisQueue:
     def submit(self, streams, events, lengths, tags, tick_stream=None):
         """Take segments (streams[i], events[i]) of the gate's LAST push (lengths[i] frames; tags[i] is handed back with the
         PCM).  One collect launch + one event on the tick's stream; nothing waits."""
+        self._raise_worker_error()
         n = len(streams)
         if n == 0:
             return
@@ -214,28 +239,35 @@ class SegmentSynthesisQueue:
         for ln in lengths:
             if ln > self.cap:
                 raise ValueError(f"segment of {ln} frames exceeds max_segment_frames={self.cap}")
-        self._raise_worker_error()
+        check_fits(n, self.rows)
         with self._cv:
             while len(self._free_rows) < n:                   # pool exhausted: wait for a job (never in a paced run)
                 if self._thread is not None:
                     self._cv.wait(0.001)
                     self._raise_worker_error()
-                else:
-                    self._dispatch()
-                    if not self._wait_one():
-                        raise RuntimeError("segment pool exhausted with no job in flight")
+                elif not self._pump(self._dispatch) and not self._pump(self._wait_one):
+                    raise RuntimeError("segment pool exhausted with no job in flight")
             rows = [self._free_rows.pop() for _ in range(n)]
             ev = self._free_events.pop() if self._free_events else None
-        self.gate.collect_torch(streams, events, rows, self.pool, hip_stream=ts)
-        if ev is None:
-            ev = L.dss_event_create()
-            if not ev:
-                raise _lib.DssError(L.dss_last_error().decode())
-            self._all_events.append(ev)
-        _lib.check(L.dss_event_record(ev, ts))
+        try:
+            self.gate.collect_torch(streams, events, rows, self.pool, hip_stream=ts)
+            if ev is None:
+                ev = L.dss_event_create()
+                if not ev:
+                    raise _lib.DssError(L.dss_last_error().decode())
+                self._all_events.append(ev)
+            _lib.check(L.dss_event_record(ev, ts))
+        except BaseException:                                 # nothing was queued: the rows and the event go back as they came
+            with self._cv:
+                self._free_rows.extend(reversed(rows))
+                if ev is not None:
+                    self._free_events.append(ev)
+                self._cv.notify_all()
+            raise
         ready = _Ready(ev)
         now = time.perf_counter()
         with self._cv:
+            self._raise_worker_error()                        # failed meanwhile: _fail has taken the rows back already
             for s, ln, row, tag in zip(streams, lengths, rows, tags):
                 ready.refs += 1
                 self.pending.append(_Segment(int(s), int(ln), row, tag, ready, now))
@@ -244,8 +276,32 @@ class SegmentSynthesisQueue:
 
     def _raise_worker_error(self):
         if self._error is not None:
-            e, self._error = self._error, None
-            raise RuntimeError("segment synthesis worker failed") from e
+            raise RuntimeError("segment synthesis worker failed") from self._error
+
+    def _fail(self, error: BaseException):
+        """End the queue on `error` (the first one stays) and settle it: every open segment -- the failed job's, those of jobs
+        on other lanes, those still waiting -- is retired as failed, so nothing is open, no stream is busy and every pool row is
+        free.  Rows of a job still running on the device are never handed out again: submit() refuses from here on, and
+        close() waits for the lanes' streams before it frees anything.  Their events stay out of the free list."""
+        with self._cv:
+            if self._error is None:
+                self._error = error
+            for lane in self.lanes:
+                lane.job = None
+            self.pending.clear()
+            self.busy[:] = False
+            self._free_rows = list(range(self.rows - 1, -1, -1))
+            self._open = 0
+            self._cv.notify_all()
+
+    def _pump(self, fn):
+        """A step of the queue on the caller's thread (unthreaded form): what it raises ends the queue like a failure of the
+        worker would, and reaches the caller as it is."""
+        try:
+            return fn()
+        except BaseException as e:
+            self._fail(e)
+            raise
 
     # ---- side streams -----------------------------------------------------------------------------------------
     def _launch(self, lane: _Lane, job: List[_Segment]):
@@ -379,17 +435,15 @@ class SegmentSynthesisQueue:
                         self._cv.wait()                       # nothing open: sleep until submit() or close()
                     elif not did:
                         self._cv.wait(0.0002)                 # jobs in flight: look at their events again in 0.2 ms (or on submit)
-        except BaseException as e:                            # surfaces on the caller's next submit / poll / drain
-            self._error = e
-            with self._cv:
-                self._cv.notify_all()
+        except BaseException as e:                            # surfaces on every later submit / poll / drain
+            self._fail(e)
 
     def poll(self):
         """Segments finished since the last call, as (stream, tag, pcm int16 host array), a stream's own in closing order.
         Never blocks.  (Unthreaded form: also retires finished jobs and starts waiting segments on free lanes.)"""
         self._raise_worker_error()
         if self._thread is None:
-            self._step()
+            self._pump(self._step)
         with self._cv:
             out, self.finished = self.finished, []
         return out
@@ -399,11 +453,11 @@ class SegmentSynthesisQueue:
         offset_samples, pcm int16 host array, last).  A stream's pieces come in frame order, all of a segment before any of its
         next one; each segment ends with exactly one ``last`` piece (an empty one for a segment of 0 frames).  Never blocks.
         (Unthreaded form: also looks at the jobs in flight, as ``poll()`` does.)"""
+        self._raise_worker_error()
         if not self.progressive:
             raise RuntimeError("poll_chunks() needs SegmentSynthesisQueue(..., progressive=True)")
-        self._raise_worker_error()
         if self._thread is None:
-            self._step()
+            self._pump(self._step)
         with self._cv:
             out, self.chunks = self.chunks, []
         return out
@@ -416,22 +470,29 @@ class SegmentSynthesisQueue:
         """Wait for everything submitted so far; returns what poll() would have returned over that time."""
         out = self.poll()
         while self._open:
+            self._raise_worker_error()                        # a queue that failed has nothing open, and says so every time
             if self._thread is not None:
                 with self._cv:
                     if self._open and not self.finished and self._error is None:
                         self._cv.wait(0.001)
-            elif not self._wait_one():
-                self._dispatch()
+            elif not self._pump(self._wait_one):
+                self._pump(self._dispatch)
             out += self.poll()
         return out
 
-    def close(self):
+    def close(self, join_timeout: float = 5.0):
+        """Stop the worker and release lanes, streams, events and page-locked memory.  A worker that has not come back within
+        `join_timeout` seconds may be inside a launch or a retire, using all of them: then nothing is freed and this raises;
+        call it again once the worker can finish."""
         th = getattr(self, "_thread", None)
         if th is not None:
             with self._cv:
                 self._stop = True
                 self._cv.notify_all()
-            th.join(timeout=5.0)
+            th.join(timeout=join_timeout)
+            if th.is_alive():
+                raise RuntimeError(f"segment synthesis worker is still running after {join_timeout} s: nothing was freed, "
+                                   "call close() again")
             self._thread = None
         for lane in getattr(self, "lanes", []):
             lane.close()

@@ -41,6 +41,7 @@ def make_kernel(module, n_streams: int, tol: float = 1e-4):
     import torch
     import warnings
     k = VadLstmGPU(n_streams, module)
+    probe = None
     try:
         dev = next(module.parameters()).device
         x = np.random.default_rng(20240301).standard_normal((1, 8, k.C)).astype(np.float32)
@@ -48,10 +49,13 @@ def make_kernel(module, n_streams: int, tol: float = 1e-4):
             want, _ = module(torch.from_numpy(x).to(dev), module.create_new_initial_state(batch_size=1, device=str(dev)))
         probe = VadLstmGPU(1, module)
         _, got = probe.step_torch(torch.from_numpy(x).cuda(), want_logits=True)
-        err = float((got - want.to(got.device)).abs().max())
+        err = float((got - want.to(got.device)).abs().max())       # (.max() -> float waits for the probe's launch)
     except Exception as e:
         warnings.warn(f"detector probe failed ({type(e).__name__}: {e}); running the module as given", RuntimeWarning, stacklevel=2)
         return None
+    finally:
+        if probe is not None:
+            probe.close()
     if not err <= tol:
         warnings.warn(f"detector module has the reference's parameters but its forward differs from LSTM + Linear by {err:.3g} on a "
                       "probe; running the module as given (PyTorch-ROCm), not the kernel", RuntimeWarning, stacklevel=2)
@@ -71,10 +75,13 @@ class VadLstmGPU:
             raise MemoryError(self._L.dss_last_error().decode())
         _lib.check(self._L.dss_vad_load_weights(self._h, *[a.ctypes.data for a in w]))
 
-    def __del__(self):
+    def close(self):
+        """Release the device buffers now (also done when the object is dropped)."""
         if getattr(self, "_h", None):
             self._L.dss_vad_destroy(self._h)
             self._h = None
+
+    __del__ = close
 
     def reset(self, stream: int = -1, hip_stream=None):
         """Zero state of one stream (or all).  Enqueued on the stream the steps run on (torch's current one by default), so it is

@@ -70,13 +70,17 @@ int dss_event_record(void *event, void *hip_stream);
 int dss_event_query(void *event);                 /* 1 = finished, 0 = not yet, < 0 = error */
 int dss_event_synchronize(void *event);
 int dss_stream_wait_event(void *hip_stream, void *event);
-/* Page-locked host memory (results that arrive by asynchronous copy).  cached != 0: ordinary cacheable pages, valid to
- * read once the copy's event has completed; 0: coherent pages. */
+/* Page-locked host memory (results that arrive by asynchronous copy).  cached != 0: ordinary cacheable pages
+ * (hipHostMallocNonCoherent), valid to read once an event from dss_event_create, recorded on the copy's stream behind the copy,
+ * has completed (dss_event_query == 1 or dss_event_synchronize), or after dss_stream_synchronize on that stream.  Events from
+ * dss_event_create carry hipEventReleaseToSystem, which is what HIP requires for device stores into such pages to be visible
+ * to the host at the event; a host that brings events of its own must create them with that flag.  0: coherent pages. */
 void *dss_host_alloc(size_t bytes, int cached);
 void dss_host_free(void *p);
 /* Device -> page-locked host memory (from dss_host_alloc), ordered on hip_stream; both pointers 16-byte aligned.  Runs as a
  * small kernel that stores into the mapped host pages, NOT as a DMA copy: a DMA copy queued behind a long kernel holds up
- * every other copy of the process (the tick's packet upload) until that kernel has finished. */
+ * every other copy of the process (the tick's packet upload) until that kernel has finished.  A null or misaligned pointer
+ * or a destination that is not page-locked gives DSS_EINVAL; nothing is enqueued and the HIP runtime's last error stays clear. */
 int dss_memcpy_d2h_async(void *host_dst, const void *d_src, size_t bytes, void *hip_stream);
 /* Explicitly coherent (fine-grained) page-locked memory (hipHostMallocCoherent): the device's stores reach it while a kernel
  * is still running.  The only memory dss_lpcnet_batch_synthesize_ragged_progress_dev accepts.  Freed with dss_host_free. */

@@ -70,6 +70,25 @@ def test_select_job_random_schedules_never_reorder_a_stream():
             assert done[s] == sorted(done[s]), (trial, s)         # tags were handed out in closing order
 
 
+def test_pool_size_and_the_capacity_check():
+    """The pool's size (two rows per stream or four jobs' worth unless the host names one; never less than a row) and the check
+    in front of submit(): a tick that closes more segments than the pool has rows can never be served, so it is refused with
+    both numbers instead of waiting for rows that cannot come."""
+    import pytest
+    sq = _module()
+    assert sq.pool_size(None, 128, 32) == 256 and sq.pool_size(None, 3, 32) == 128 and sq.pool_size(None, 3, 1) == 6
+    assert sq.pool_size(3, 128, 32) == 3 and sq.pool_size(1, 1, 1) == 1
+    for bad in (0, -1):
+        with pytest.raises(ValueError, match="pool_rows"):
+            sq.pool_size(bad, 3, 1)
+    for n in (0, 1, 4):
+        sq.check_fits(n, 4)
+    with pytest.raises(ValueError, match=r"\b5 segments\b.*\b4 rows\b"):
+        sq.check_fits(5, 4)
+    with pytest.raises(ValueError, match=r"\b200 segments\b.*\b128 rows\b"):
+        sq.check_fits(200, 128)
+
+
 def test_default_lanes_follow_the_hardware_queue_count(monkeypatch):
     sq = _module()
     monkeypatch.delenv("GPU_MAX_HW_QUEUES", raising=False)

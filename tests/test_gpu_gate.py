@@ -337,7 +337,16 @@ def test_segment_queue_refuses_and_reports():
         for k in range(env.size // 40):
             pipe.push(ecog[:, k * 40:(k + 1) * 40])
         pipe.flush()
-    pipe.close()
+    # ... and on every call after that one: a host that caught the first report and flushes at shutdown is told again, it
+    # does not wait for a worker that is gone
+    from segment_queue_harness import DEADLINE, within
+    for _ in range(2):
+        with pytest.raises(RuntimeError, match="worker failed") as ei:
+            within(DEADLINE, pipe.flush)
+        assert str(ei.value.__cause__) == "injected"
+    with pytest.raises(RuntimeError, match="worker failed"):
+        within(DEADLINE, lambda: pipe.push(ecog[:, :40]))
+    within(DEADLINE, pipe.close)
 
 
 def test_asynchronous_path_at_full_size_128_streams():
