@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "dss_host.h"
+#include "lpc_tables.h"
 
 struct BlobView {
     const float *embed_pitch, *conv1_w, *conv1_b, *conv2_w, *conv2_b, *dense1_w, *dense1_b, *dense2_w, *dense2_b;
@@ -466,12 +467,9 @@ static void dss_tansig_tables(float *t)
     }
 }
 
-// derived tables (host libm, exactly as xiph builds them at run time)
-struct LibmTables {
-    float tansig[DSS_TANSIG_Y + 201] = {0}, logit[256], u2l[256], dct[18 * 18], costab[320], ia[160], ib[160];
-    int iband[160];
-    double lagw[17];
-    std::vector<float> cos_kl;       // [160][17]
+// derived tables (host libm, exactly as xiph builds them at run time); those of lpc_from_cepstrum are LpcTables (lpc_tables.h)
+struct LibmTables : LpcTables {
+    float tansig[DSS_TANSIG_Y + 201] = {0}, logit[256], u2l[256];
     LibmTables()
     {
         dss_tansig_tables(tansig);
@@ -480,26 +478,6 @@ struct LibmTables {
             logit[i] = -log((1 - prob) / prob);
             u2l[i] = host_ulaw2lin((float)i);
         }
-        for (int i = 0; i < 18; ++i)                                                                  // freq.c check_init()
-            for (int j = 0; j < 18; ++j) {
-                dct[i * 18 + j] = cos((i + .5) * j * M_PI / 18);
-                if (j == 0) dct[i * 18 + j] *= sqrt(.5);
-            }
-        for (int i = 0; i < 320; ++i) costab[i] = (float)cos(2. * M_PI * i / 320);
-        static const int eband5ms[18] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 34, 40};
-        for (int i = 0; i < 17; ++i) {                                                                // interp_band_gain()
-            const int band_size = (eband5ms[i + 1] - eband5ms[i]) * 4;
-            for (int j = 0; j < band_size; ++j) {
-                const float frac = (float)j / band_size;
-                ia[eband5ms[i] * 4 + j] = 1 - frac;
-                ib[eband5ms[i] * 4 + j] = frac;
-                iband[eband5ms[i] * 4 + j] = i;
-            }
-        }
-        for (int i = 0; i < 17; ++i) lagw[i] = (1 - 6e-5 * i * i);
-        cos_kl.resize((size_t)160 * 17);
-        for (int k = 0; k < 160; ++k)
-            for (int lag = 0; lag < 17; ++lag) cos_kl[(size_t)k * 17 + lag] = costab[(k * lag) % 320];
     }
 };
 

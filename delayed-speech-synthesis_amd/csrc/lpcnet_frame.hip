@@ -13,6 +13,7 @@
 // so a wave reads 256 contiguous bytes per input; a block reuses each weight across RT rows staged in LDS.
 #include "dss_common.h"
 #include "lpcnet_device.h"
+#include "lpc_chain.h"
 
 #define FIN (DSS_NB_FEATURES + 64)    // 84: features + pitch embedding
 
@@ -121,97 +122,37 @@ dense_rows_kernel(const float *__restrict__ x, long x_utt_stride, int x_row_stri
 }
 
 // ---- lpc_from_cepstrum (freq.c) for every (utterance, frame): 32 lanes per frame -----------------------------
-// The chain of a frame -- inverse DCT of the cepstrum, band energies, band interpolation, the 17 autocorrelation lags as a
-// direct inverse DFT (160 terms each, in ascending bin order), lag window, Levinson-Durbin -- with the reference's operation
-// order inside every element; what is independent runs on different lanes: one band per lane, one bin per lane, one LAG per
-// lane (its 160-term sum stays one sequential chain), and the recursion on one lane.  One lane per frame (rounds 1-3) took
-// 60 us whatever the batch: 160 x 17 dependent pairs of instructions per lane behind scalar loads of the cosine table.
-__constant__ float c_compensation[DSS_NB_BANDS] = {0.8f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 0.666667f, 0.5f, 0.5f, 0.5f,
-                                                   0.333333f, 0.25f, 0.25f, 0.2f, 0.166667f, 0.173913f};
+// The chain itself is lpc_chain_frame (lpc_chain.h), which the feature encoder shares.
 #define LPC_FPB 2                 // frames per 64-thread block
 
 __global__ void __launch_bounds__(64)
 frame_lpc_kernel(DssModelDev m, DssBatchDev b, const float *__restrict__ feat, int total, int n_frames, int feat_stride,
                  double idct_scale)
 {
-    __shared__ __attribute__((aligned(16))) float ck_lds[160][20];          // m.cos_kl ([bin][17 lags])
+    __shared__ __attribute__((aligned(16))) float ck_lds[160][LPC_CK_STRIDE];          // m.cos_kl ([bin][17 lags])
     __shared__ float cs[LPC_FPB][DSS_NB_BANDS + 2], exs[LPC_FPB][DSS_NB_BANDS + 2], xr[LPC_FPB][160], as[LPC_FPB][DSS_LPC_ORDER + 4];
-    constexpr int eband5ms[DSS_NB_BANDS] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 34, 40};
+    const DssLpcTables T = {m.dct_table, m.cos_kl, m.interp_a, m.interp_b, m.lag_window};
     const int tid = threadIdx.x, sub = tid >> 5, l = tid & 31;
     int gid = blockIdx.x * LPC_FPB + sub;
     const bool valid = gid < total;
     if (!valid) gid = total - 1;
     const int utt = gid / n_frames, t = gid - utt * n_frames;
-    for (int k = tid; k < 160 * (DSS_LPC_ORDER + 1); k += 64) ck_lds[k / (DSS_LPC_ORDER + 1)][k % (DSS_LPC_ORDER + 1)] = m.cos_kl[k];
+    lpc_chain_load_ck(T, ck_lds, tid, 64);
     const float *cep = feat + (size_t)gid * feat_stride;
     if (l < DSS_NB_BANDS) cs[sub][l] = l == 0 ? cep[0] + 4 : cep[l];
     __syncthreads();
-    if (l < DSS_NB_BANDS) {                                                 // band l: inverse DCT term by term, then the energy
-        float sum = 0;
+    float lpc[DSS_LPC_ORDER];
+    lpc_chain_frame(T, idct_scale, ck_lds, cs[sub], exs[sub], xr[sub], as[sub], l, lpc);
+    if (l == 0 && valid) {
+        float *dst = b.lpc_buf + ((size_t)utt * (n_frames + 2) + t + 2) * 16;
 #pragma unroll
-        for (int j = 0; j < DSS_NB_BANDS; ++j) sum += cs[sub][j] * m.dct_table[l * DSS_NB_BANDS + j];
-        const float e = (float)((double)sum * idct_scale);                 // sum*sqrt(2./NB_BANDS)
-        exs[sub][l] = (float)(pow(10.0, (double)e) * (double)c_compensation[l]);
-    }
-    __syncthreads();
-    for (int k = l; k < 160; k += 32) {                                     // interp_band_gain: bin k lies in band i
-        int i = 0;
-#pragma unroll
-        for (int q = 1; q < DSS_NB_BANDS - 1; ++q) i += (k >= eband5ms[q] * 4);
-        xr[sub][k] = m.interp_a[k] * exs[sub][i] + m.interp_b[k] * exs[sub][i + 1];
-    }
-    __syncthreads();
-    if (l <= DSS_LPC_ORDER) {                                               // lag l: direct inverse DFT, bins ascending
-        float ac = xr[sub][0];
-        for (int k = 1; k < 160; ++k) {
-            const float x2 = 2.f * xr[sub][k];
-            ac += x2 * ck_lds[k][l];
-        }
-        float a;
-        if (l == 0) a = (float)((double)ac + ((double)ac * 1e-4 + 320 / 12 / 38.));
-        else a = (float)((double)ac * m.lag_window[l]);
-        as[sub][l] = a;
-    }
-    __syncthreads();
-    if (l == 0) {                                                           // Levinson-Durbin (the recursion is serial)
-        float a[DSS_LPC_ORDER + 1];
-#pragma unroll
-        for (int i = 0; i <= DSS_LPC_ORDER; ++i) a[i] = as[sub][i];
-        float lpc[DSS_LPC_ORDER];
-#pragma unroll
-        for (int i = 0; i < DSS_LPC_ORDER; ++i) lpc[i] = 0.f;
-        float error = a[0];
-        bool live = a[0] != 0;
-#pragma unroll
-        for (int i = 0; i < DSS_LPC_ORDER; i++) {
-            if (live) {
-                float rr = 0;
-#pragma unroll
-                for (int j = 0; j < i; j++) rr += lpc[j] * a[i - j];
-                rr += a[i + 1];
-                const float r = -rr / error;
-                lpc[i] = r;
-#pragma unroll
-                for (int j = 0; j < (i + 1) >> 1; j++) {
-                    const float tmp1 = lpc[j], tmp2 = lpc[i - 1 - j];
-                    lpc[j] = tmp1 + r * tmp2;
-                    lpc[i - 1 - j] = tmp2 + r * tmp1;
-                }
-                error = error - (r * r) * error;
-                if (error < .001f * a[0]) live = false;                      // the C loop's break
-            }
-        }
-        if (valid) {
-            float *dst = b.lpc_buf + ((size_t)utt * (n_frames + 2) + t + 2) * 16;
-#pragma unroll
-            for (int i = 0; i < DSS_LPC_ORDER; ++i) dst[i] = lpc[i];
-        }
+        for (int i = 0; i < DSS_LPC_ORDER; ++i) dst[i] = lpc[i];
     }
 }
 
 // lpc_from_cepstrum's `pow(10.f, Ex[i]) * compensation[i]` (freq.c) is a double pow rounded to float after the
 // multiplication; the LPC taps are bit-exact only if the device's pow and the host libm's agree after that rounding.
-// tests/test_gpu_lpcnet.py sweeps the reachable exponent range through this kernel (same expression as line 141).
+// tests/test_gpu_lpcnet.py sweeps the reachable exponent range through this kernel (the expression of lpc_chain.h's band step).
 __global__ void exp10_selftest_kernel(const float *__restrict__ x, const float *__restrict__ comp, float *__restrict__ out, long n)
 {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -207,6 +207,14 @@ def _declare(L):
         "dss_vad_group_publish": (i, [vp, i, vp, vp]),
         "dss_vad_group_window_dev": (i, [vp, vp, i, vp]),
         "dss_vad_group_trial_dev": (i, [vp, vp, i, i, vp]),
+        "dss_fenc_create": (vp, []),
+        "dss_fenc_destroy": (None, [vp]),
+        "dss_fenc_frame_offsets": (C.c_longlong, [vp, i, vp]),
+        "dss_fenc_features_trials": (C.c_longlong, [vp, vp, C.c_longlong, vp, i, vp]),
+        "dss_fenc_features_trials_dev": (C.c_longlong, [vp, vp, C.c_longlong, vp, i, vp, vp]),
+        "dss_fenc_tap_scores": (C.c_longlong, [vp, vp, C.c_longlong]),
+        "dss_fenc_enable_timing": (i, [vp, i]),
+        "dss_fenc_kernel_ms": (C.c_double, [vp, i]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

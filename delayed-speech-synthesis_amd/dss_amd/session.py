@@ -16,8 +16,11 @@ and with them the statistics, are bit-identical to the reference chain.  Parsing
     ``vad_labels`` (an ``EnergyBasedVad`` per trial on the session's wav) and ``trial_ids``: ``session_corpus`` below, with
     the labels of all trials in one pass over the audio (``AcousticVadGPU.labels_trials``).  The per-trial loudness
     normalisation through pydub is opt-in (``normalize_audio=True``; by default the audio is labelled as it is handed over);
-    its arithmetic is pinned by tests/golden/trial_audio.npz.  ``lpc_coefficients`` stay outside: they need xiph's LPCNet
-    feature encoder.  The array that encoder is given per trial is ``session_trial_audio``.
+    its arithmetic is pinned by tests/golden/trial_audio.npz.
+  * ``prepare_corpus.py:55-76``: ``lpc_coefficients`` -- ``session_lpc_coefficients`` below (and ``session_corpus`` with
+    ``lpc_coefficients=True``): the array ``session_trial_audio`` prepares per trial, through the LPC feature encoder
+    (``feature_encoder.LpcFeatureEncoderGPU``) for all trials in one call.  That encoder is this project's statement of the
+    published method; parity with xiph's ``LPCFeatureEncoder`` is not pinned.
 """
 from __future__ import annotations
 
@@ -157,6 +160,43 @@ def session_trial_audio(wav: np.ndarray, trials, stimulus_labels, fs: int = 1000
     return out, np.concatenate([[0], np.cumsum([n for _, n in ranges], dtype=np.int64)]).astype(np.int64)
 
 
+def lpc_rows(n_samples: int) -> int:
+    """Rows of ``lpc_coefficients`` a trial of ``n_samples`` prepared samples gives: ``features[3:-1]`` of its n // 160 frames
+    (prepare_corpus.py:74)."""
+    return max(int(n_samples) // 160 - 4, 0)
+
+
+def session_lpc_coefficients(wav: np.ndarray, trials, stimulus_labels, fs: int = 1000, fs_audio: int = 16000,
+                             shift_seconds: float = 0.016, norm_db: float = -3.0) -> np.ndarray:
+    """prepare_corpus.get_lpc_coefficients (prepare_corpus.py:55-76): float32 (sum rows_i, 20).  Every trial's audio is
+    prepared as ``session_trial_audio`` prepares it and stays on the device; a fresh encoder per trial, all trials in one call
+    (``LpcFeatureEncoderGPU.features_trials_torch``); ``features[3:-1]`` of every trial, concatenated.  The encoder is this
+    project's statement of the published method; parity with xiph's is not pinned."""
+    import torch
+    from . import feature_encoder, trial_audio
+    wav = np.asarray(wav)
+    if wav.dtype != np.int16 or wav.ndim != 1:
+        raise ValueError("wav must be a one-dimensional int16 array")
+    ranges = trial_audio_ranges(trials, fs, fs_audio, len(wav))
+    silence = [label == "SILENCE" for label in stimulus_labels]
+    if len(silence) != len(ranges):
+        raise ValueError("one stimulus label per trial")
+    offsets = np.concatenate([[0], np.cumsum([n for _, n in ranges], dtype=np.int64)]).astype(np.int64)
+    v = acoustic_vad.AcousticVadGPU(fs=fs_audio)
+    enc = feature_encoder.LpcFeatureEncoderGPU()
+    try:
+        v.set_gain(post=trial_audio.post_gain(norm_db))
+        d_wav = torch.from_numpy(np.ascontiguousarray(wav)).cuda()
+        audio = v.prepared_audio_trials_torch(d_wav, ranges, lead=int(shift_seconds * fs_audio), normalize=True, silence=silence)
+        feats, fo = enc.features_trials_torch(audio, offsets)
+        keep = [feats[int(fo[i]) + 3:int(fo[i + 1]) - 1] for i in range(len(ranges)) if fo[i + 1] - fo[i] > 4]
+        out = torch.cat(keep) if keep else feats[:0]
+        return out.cpu().numpy()
+    finally:
+        enc.close()
+        v.close()
+
+
 def trial_ids(trials, stimulus_labels, stimuli, fs: int = 1000) -> np.ndarray:
     """prepare_corpus.get_trial_ids (prepare_corpus.py:118-137): per frame the one-based index of the trial's stimulus in
     ``stimuli``, negated when the trial repeats the stimulus of the trial before it (and positive again on the next
@@ -179,13 +219,15 @@ def trial_ids(trials, stimulus_labels, stimuli, fs: int = 1000) -> np.ndarray:
 def session_corpus(recording: np.ndarray, wav: np.ndarray, trials, stimulus_labels, stimuli, normalization: np.ndarray,
                    fs: int = 1000, fs_audio: int = 16000, bad_channels: Optional[Sequence[int]] = None,
                    contaminated_channels: Optional[Sequence[int]] = None, shift_seconds: float = 0.016,
-                   normalize_audio: bool = False) -> dict:
-    """Three of the four arrays prepare_corpus.main stores per recording (prepare_corpus.py:218-234), ready for the user's own
+                   normalize_audio: bool = False, lpc_coefficients: bool = False, norm_db: float = -3.0) -> dict:
+    """The arrays prepare_corpus.main stores per recording (prepare_corpus.py:218-234), ready for the user's own
     ``save_data_to_hdf``: ``hga_activity`` = (session_features - mean) / std with ``normalization`` = vstack([mean, std]) of the
     day, ``vad_labels`` (bool), ``trial_ids`` (int16).  Raises ValueError when a trial's frame count differs between the
     features and the labels (a trial clamped at the end of the wav, a sampling-rate ratio that truncates): the reference
-    would write misaligned arrays.  ``lpc_coefficients`` is not a key: it needs xiph's LPCNet feature encoder, which this
-    package does not have (its five symbols fail cleanly).  By default the wav is labelled as it is handed over; with
+    would write misaligned arrays.  With ``lpc_coefficients=True`` the fourth array is added under that key
+    (``session_lpc_coefficients``: float32 (N, 20), this project's statement of the encoder, parity with xiph's not pinned;
+    ``norm_db`` is get_lpc_coefficients' ``norm``), and a trial whose row count there differs from its feature frames raises
+    ValueError too; without the keyword the dict has the three keys only.  By default the wav is labelled as it is handed over; with
     ``normalize_audio`` every non-SILENCE trial gets the reference's pydub loudness normalisation first (on the device), which
     is what prepare_corpus.get_vad_labels labels."""
     trials = [(int(a), int(b)) for a, b in trials]
@@ -198,6 +240,8 @@ def session_corpus(recording: np.ndarray, wav: np.ndarray, trials, stimulus_labe
         w_vad = acoustic_vad.trial_frames(n_samples, v_window, v_shift)
         if w_hga != w_vad:
             raise ValueError(f"trial {k}: {w_hga} feature frames but {w_vad} label frames")
+        if lpc_coefficients and w_hga != lpc_rows(n_samples):
+            raise ValueError(f"trial {k}: {w_hga} feature frames but {lpc_rows(n_samples)} rows of LPC coefficients")
     feats = session_features(recording, trials, fs, bad_channels, contaminated_channels)
     if normalize_audio:
         labels = session_vad_labels(wav, trials, stimulus_labels, fs, fs_audio, shift_seconds, normalize=True)
@@ -206,4 +250,10 @@ def session_corpus(recording: np.ndarray, wav: np.ndarray, trials, stimulus_labe
     ids = trial_ids(trials, stimulus_labels, stimuli, fs)
     if not (len(feats) == len(labels) == len(ids)):
         raise ValueError(f"misaligned corpus: {len(feats)} feature frames, {len(labels)} labels, {len(ids)} trial ids")
-    return dict(hga_activity=(feats - stats[0]) / stats[1], vad_labels=labels, trial_ids=ids)
+    corpus = dict(hga_activity=(feats - stats[0]) / stats[1], vad_labels=labels, trial_ids=ids)
+    if lpc_coefficients:
+        lpc = session_lpc_coefficients(wav, trials, stimulus_labels, fs, fs_audio, shift_seconds, norm_db)
+        if len(lpc) != len(feats):
+            raise ValueError(f"misaligned corpus: {len(feats)} feature frames, {len(lpc)} rows of LPC coefficients")
+        corpus["lpc_coefficients"] = lpc
+    return corpus

@@ -18,7 +18,8 @@
  * training corpus, Part 8 the two recurrent models over the trials of such a corpus (the validation passes of the
  * reference's training scripts), Part 9 the training of the neural detector, Part 10 that of the decoder, Part 11 the
  * spectrograms behind the reference's spectral analyses, Part 13 several decoders trained side by side, Part 14 the trainers'
- * dropout masks drawn on the device, Part 15 several detectors trained side by side, each described at its declarations.
+ * dropout masks drawn on the device, Part 15 several detectors trained side by side, Part 16 the LPC feature encoder behind a
+ * training corpus' `lpc_coefficients`, each described at its declarations.
  *
  * Error convention: functions returning int return 0 on success and a negative DSS_E* code on failure;
  * dss_last_error() gives a thread-local message.  Creators return NULL on failure (the reference's
@@ -112,9 +113,9 @@ int lpcnet_get_size(void);
  * incremented (first failure and every 1000th are also printed to stderr). */
 long dss_error_count(void);
 
-/* cLPCNet.pxd:15-19 -- feature encoder (used only by prepare_corpus.py:72-73).  NOT provided: create returns NULL
- * (the reference's LPCFeatureEncoder.__cinit__ raises MemoryError, LPCNet.pyx:53-56), the others return -1 and
- * zero their output. */
+/* cLPCNet.pxd:15-19 -- feature encoder (used only by prepare_corpus.py:72-73).  NOT provided under these names: create
+ * returns NULL (the reference's LPCFeatureEncoder.__cinit__ raises MemoryError, LPCNet.pyx:53-56), the others return -1 and
+ * zero their output.  The encoder this library has is Part 16, under names of its own. */
 typedef struct LPCNetEncState LPCNetEncState;
 LPCNetEncState *lpcnet_encoder_create(void);
 int lpcnet_encoder_init(LPCNetEncState *st);
@@ -946,6 +947,44 @@ int dss_vad_group_window_dev(dss_vad_group *g, const dss_vad_group_trial *trials
  * is over is left alone by the later pairs.  Window w's loss goes to d_losses[w]; apply_step is taken as 1.  Also refuses a
  * window outside 1 .. max_window.  Returns the number of pairs launched, max over the models of ceil(len / window). */
 int dss_vad_group_trial_dev(dss_vad_group *g, const dss_vad_group_trial *trials, int window, int frames_are_f64, void *hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Part 16 -- LPC feature encoder: the `lpc_coefficients` of a training corpus (prepare_corpus.py:55-76 runs xiph's
+ * LPCFeatureEncoder over every trial's int16 audio, LPCNet.pyx:65-87).  The method here is THIS PROJECT'S STATEMENT of the
+ * published encoder (the binding definition is tests/feature_encoder_reference.py); parity with xiph's code
+ * is not pinned, no copy of it being at hand.  Per 160-sample frame 36 float32 values: 18 Bark cepstral coefficients, the pitch
+ * feature (18) and correlation (19) as the decoder of Part 1 reads them, and the 16 LPC taps (20..35) the decoder derives from
+ * that cepstrum (the same device code).  One fresh encoder per trial; a whole trial list runs in three launches on one stream
+ * with no host synchronisation between them (csrc/feature_encoder.hip).  No LPCNet model is needed.
+ *
+ * A trial list is an int16 concatenation and n_trials + 1 ascending offsets (a HOST array; what session_trial_audio
+ * returns): trial i is samples offsets[i] .. offsets[i + 1] and gives (offsets[i + 1] - offsets[i]) / 160 frames; a trial
+ * shorter than 160 samples gives none.  The five xiph encoder symbols of Part 1 stay failing stubs.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct dss_fenc dss_fenc;
+dss_fenc *dss_fenc_create(void);
+void dss_fenc_destroy(dss_fenc *f);
+/* Pure host function: out[0 .. n_trials] = the first output frame of every trial and, last, the total, which is also
+ * returned (out may be NULL).  DSS_EINVAL for a negative first offset or offsets that decrease. */
+long long dss_fenc_frame_offsets(const long long *offsets, int n_trials, long long *out);
+/* Host buffers: audio int16[n], out36 float32 (total frames, 36).  Returns the total number of frames.  An empty list
+ * (n_trials == 0) or one without a whole frame is a no-op that returns 0.  DSS_EINVAL, before anything is launched, for
+ * offsets that decrease or run past n. */
+long long dss_fenc_features_trials(dss_fenc *f, const short *audio, long long n, const long long *offsets, int n_trials,
+                                   float *out36);
+/* The same on device-resident audio and output (offsets stays a host array, read before the call returns), launched on
+ * hip_stream; the results are complete when the stream reaches the end of the call's work. */
+long long dss_fenc_features_trials_dev(dss_fenc *f, const short *d_audio, long long n, const long long *offsets, int n_trials,
+                                       float *d_out36, void *hip_stream);
+/* The score scratch of the last call, for tests: (2 * total frames, 256) float64, row s = sub-frame s of the list; columns
+ * 0 .. 254 are the damped normalised cross-correlations at lag 256 - column, column 255 (lag 1, which nothing reads) holds the
+ * sub-frame's normalised weight.  n must be the number of values; waits for the call's stream.  Returns the number of rows. */
+long long dss_fenc_tap_scores(dss_fenc *f, double *out, long long n);
+/* Development timing (tools/time_feature_encoder.py): with `on`, every later call records events around its three launches
+ * (no host synchronisation); dss_fenc_kernel_ms waits for the last timed call and returns the device time in ms of launch
+ * `which`: 0 spectrum / cepstrum / LPC, 1 residual and scores, 2 pitch track.  Negative when there is no timed call. */
+int dss_fenc_enable_timing(dss_fenc *f, int on);
+double dss_fenc_kernel_ms(dss_fenc *f, int which);
 
 #ifdef __cplusplus
 }
