@@ -10,6 +10,26 @@
   logits' sup norm) and within 1e-12 of numpy float64 on the returned logits, the correct count exact, prob within 1e-6, the
   per-trial MSE within 1e-12 relative of numpy float64 on the returned features; ``vad_validation`` / ``decoder_validation``
   return their sum / ratio / mean.
+
+All of that is at the reference's sizes on decoder handles of 3, 4, 5 and 64 streams.  The tests named ``test_case_table_*`` run
+the case table of tests/validation_cases.py (its conditions on the float64 reference alone: tests/test_cpu_validation.py).
+Bounds, and beside them the worst figure measured on an MI355X over every entry:
+
+* decoder, W = 2 and W = 4 chunks, chunks whose regressor blocks are pure padding or straddle a trial's end, O = 1, 3, 31, 32,
+  K = 2H = 254 and 256, H = C = 1, float32 and float64 frames: every trial bit-identical to ``forward_rows_torch`` on a
+  one-stream handle given that trial alone (so the handles of 300, 256 and 129 streams are bit-identical to each other),
+  nothing written behind the last trial and no row left unwritten (the output holds a sentinel beforehand); features within
+  ``bound(scale)`` = 2e-6 / 5e-5 of float64 on every trial: measured 1.05e-7 at scale 1 ((127, 255), 31 outputs; 4.98e-8 on the
+  300-trial entry, 7.56e-8 at the reference size through ``decoder_validation``'s own handle), 9.34e-8 at scale 4;
+* detector at (7, 5), (33, 17), (159, 127), (160, 128), (1, 1): bit-identical to ``step_torch`` per trial, labels equal to the
+  float64 argmax on every frame (0 differences), logits within ``bound(scale)``: measured 4.17e-8 at scale 1 and 2.92e-7 at scale
+  4, both at (160, 128); the tie model: labels all 0, prob exactly 0.5, |loss - ln 2| measured 0 (bound 1e-12);
+* scores on synthetic logits (trials of 1, 255, 256, 257, 512, 513 frames, exp underflow, equal logits): a trial's loss within
+  1e-12 x max(1, its largest per-frame cross-entropy) of numpy float64 (derived in ``test_case_table_scores``): measured 7.96e-13
+  where the largest cross-entropy is 1600, i.e. 5.0e-4 of the bound, and 2.5e-16 where it is below 10; ``correct`` exact; prob
+  within 1e-6: measured 2.97e-8, and exactly 0, 1 and 0.5 where it has to be; ``prob = NULL`` changes no bit;
+* MSE with frames x outputs of 1, 255 ... 258, 279 elements: within 1e-12 relative of numpy float64: measured 2.15e-16 (4.35e-16
+  on the 130 trials at the reference size); exactly 0.0 where the features are their targets.
 Every figure is printed before it is asserted (run with -rP)."""
 import numpy as np
 import pytest
@@ -259,3 +279,267 @@ def test_decoder_trials_against_float64_and_mse(scale):
               decoder_validation(BiLstmDecoderGPU(5, 1500, state_dict=sd), cat, tg, ids)):          # a handle the caller keeps
         assert np.array_equal(r["features"].view(np.int32), feats.cpu().numpy().view(np.int32))
         assert np.array_equal(r["per_trial_mse"], mse) and r["loss"] == float(mse.mean())
+
+
+# ---- the case table (tests/validation_cases.py) -------------------------------------------------------------------------------------
+SENTINEL = 777.0
+SPARE_ROWS = 8
+
+
+def _cuda(x, f64):
+    return torch.from_numpy(x if f64 else x.astype(np.float32)).cuda()
+
+
+def _decoder_trials(k, x, ranges):
+    """``dss_dec_forward_trials_dev`` into a tensor that holds SENTINEL beforehand and SPARE_ROWS rows more than the list fills: a
+    row that is not written keeps the sentinel, and nothing may be written behind the last trial."""
+    from dss_amd import _lib
+    from dss_amd.validation import _ranges
+    first, length, total = _ranges(k._L, int(x.shape[0]), ranges)
+    feats = torch.full((total + SPARE_ROWS, k.O), SENTINEL, dtype=torch.float32, device="cuda")
+    _lib.check(k._L.dss_dec_forward_trials_dev(k._h, x.data_ptr(), int(x.dtype == torch.float64), int(x.shape[0]), len(first),
+                                               first.ctypes.data, length.ctypes.data, feats.data_ptr(), torch.cuda.current_stream().cuda_stream))
+    assert bool((feats[total:] == SENTINEL).all()), "rows behind the last trial were written"
+    assert not bool((feats[:total] == SENTINEL).any()), "a row of the features was not written"
+    return feats[:total]
+
+
+def _detector_trials(k, x, ranges):
+    """``dss_vad_forward_trials_dev`` into labels of -7 and logits of SENTINEL with SPARE_ROWS rows more than the list fills."""
+    from dss_amd import _lib
+    from dss_amd.validation import _ranges
+    first, length, total = _ranges(k._L, int(x.shape[0]), ranges)
+    labels = torch.full((total + SPARE_ROWS,), -7, dtype=torch.int32, device="cuda")
+    logits = torch.full((total + SPARE_ROWS, 2), SENTINEL, dtype=torch.float32, device="cuda")
+    _lib.check(k._L.dss_vad_forward_trials_dev(k._h, x.data_ptr(), int(x.dtype == torch.float64), int(x.shape[0]), len(first),
+                                               first.ctypes.data, length.ctypes.data, labels.data_ptr(), logits.data_ptr(),
+                                               torch.cuda.current_stream().cuda_stream))
+    assert bool((labels[total:] == -7).all()) and bool((logits[total:] == SENTINEL).all()), "rows behind the last trial were written"
+    assert bool(((labels[:total] == 0) | (labels[:total] == 1)).all()) and not bool((logits[:total] == SENTINEL).any())
+    return labels[:total], logits[:total]
+
+
+def _each_trial_alone(sd, x, ranges):
+    """``forward_rows_torch`` on a ONE-stream handle, given each trial alone: the concatenated features in list order."""
+    from dss_amd.decoder import BiLstmDecoderGPU
+    k = BiLstmDecoderGPU(1, max(n for _, n in ranges), state_dict=sd)
+    out = []
+    for a, n in ranges:
+        feats = torch.full((1, n, k.O), SENTINEL, dtype=torch.float32, device="cuda")
+        out.append(k.forward_rows_torch(x[a:a + n][None].contiguous(), None, [n], feats, n)[0])
+    return torch.cat(out)
+
+
+def _trial_ids(lengths):
+    return np.concatenate([np.full(n, (k % 3 + 1) * (-1) ** k, np.int16) for k, n in enumerate(lengths)])
+
+
+def _first_difference(got, want, lengths):
+    """The first trial (list position, length) in which two concatenated results differ in a bit, or None."""
+    for k, s in enumerate(V.bounds_of(lengths)):
+        if not torch.equal(_bits(got[s]), _bits(want[s])):
+            return k, lengths[k]
+    return None
+
+
+@pytest.mark.parametrize("f64", [False, True])
+@pytest.mark.parametrize("e", [e for e in V.DECODER if not e.corpus_form], ids=V.dec_ident)
+def test_case_table_decoder(e, f64):
+    """Per decoder entry and handle: every trial of the trial form has the bits of ``forward_rows_torch`` on a one-stream handle
+    given that trial alone (so W = 2 and W = 4 chunks, their partners taken from the longest-first order, equal single-trial
+    calls, and the handles of 300, 256 and 129 streams equal each other); every feature within ``bound(scale)`` of the float64
+    decoder, every trial of every entry compared; the output is written exactly where the list says."""
+    from dss_amd.decoder import BiLstmDecoderGPU
+    sd, x64, ranges = V.decoder_inputs(e)
+    lengths = [n for _, n in ranges]
+    x = _cuda(x64, f64)
+    alone = _each_trial_alone(sd, x, ranges)
+    truth = V.decoder_truth(e)
+    want = np.concatenate([truth[i, :n] for i, n in enumerate(lengths)])
+    for streams in e.handles:
+        k = BiLstmDecoderGPU(streams, max(lengths), state_dict=sd)
+        got = _decoder_trials(k, x, ranges)
+        assert _first_difference(got, alone, lengths) is None, (streams, V.decoder_chunks(lengths, streams))
+        assert torch.equal(_bits(k.forward_trials_torch(x, ranges)), _bits(got))
+        err = float(np.abs(got.cpu().numpy().astype(np.float64) - want).max())
+        print(f"{V.dec_ident(e)} f64={f64} handle of {streams} (chunks {V.decoder_chunks(lengths, streams)}): "
+              f"|features - float64| {err:.2e} (bound {R.bound(e.scale):.0e})")
+        assert err <= R.bound(e.scale)
+
+
+@pytest.mark.parametrize("f64", [False, True])
+def test_case_table_decoder_validation_at_the_reference_size(f64):
+    """130 trials of 1 .. 12 frames at (100, 64) through ``decoder_validation(state_dict, ...)`` with ``max_streams`` left alone: the
+    W = 2 chunk a corpus of more than 128 validation trials starts with.  Features bit-identical to single-trial calls and within
+    bound of float64, the per-trial MSE within 1e-12 relative of numpy float64 on them."""
+    from dss_amd.validation import decoder_validation
+    e = V.REFERENCE_SIZE
+    sd, x64, ranges = V.decoder_inputs(e)
+    lengths = [n for _, n in ranges]
+    assert [a for a, _ in ranges] == [int(v) for v in np.cumsum([0] + lengths[:-1])] and len(x64) == sum(lengths)
+    frames = x64 if f64 else x64.astype(np.float32)
+    tg = np.random.default_rng(9600).standard_normal((len(x64), e.O)).astype(np.float32)
+    r = decoder_validation(sd, frames, tg, _trial_ids(lengths))
+    feats = torch.from_numpy(r["features"]).cuda()
+    assert _first_difference(feats, _each_trial_alone(sd, _cuda(x64, f64), ranges), lengths) is None
+    truth = V.decoder_truth(e)
+    got = r["features"].astype(np.float64)
+    err = float(np.abs(got - np.concatenate([truth[i, :n] for i, n in enumerate(lengths)])).max())
+    d = got - tg.astype(np.float64)
+    want_mse = np.array([np.mean(d[s] ** 2) for s in V.bounds_of(lengths)])
+    rel = float((np.abs(r["per_trial_mse"] - want_mse) / want_mse).max())
+    print(f"reference size f64={f64}: |features - float64| {err:.2e} (bound {R.bound(e.scale):.0e}); largest relative |mse - numpy| {rel:.2e}")
+    assert err <= R.bound(e.scale)
+    assert (np.abs(r["per_trial_mse"] - want_mse) <= 1e-12 * want_mse).all() and r["loss"] == float(r["per_trial_mse"].mean())
+
+
+def test_case_table_decoder_validation_sums():
+    """``decoder_validation`` on an odd size, (33, 17) with one output: the features are the trial form's, ``per_trial_mse`` the
+    reduction's on them, ``loss`` their mean; a state_dict and a handle the caller keeps agree bit for bit."""
+    from dss_amd.decoder import BiLstmDecoderGPU
+    from dss_amd.validation import decoder_validation
+    e = V.DECODER_VALIDATION
+    sd, x64, ranges = V.decoder_inputs(e)
+    lengths = [n for _, n in ranges]
+    cat = np.concatenate([x64[a:a + n] for a, n in ranges])
+    tg = np.random.default_rng(9601).standard_normal((len(cat), e.O)).astype(np.float32)
+    feats = _decoder_trials(BiLstmDecoderGPU(2, max(lengths), state_dict=sd), _cuda(x64, True), ranges)
+    mse = _mse(feats, torch.from_numpy(tg).cuda(), lengths)
+    d = feats.cpu().numpy().astype(np.float64) - tg.astype(np.float64)
+    want = np.array([np.mean(d[s] ** 2) for s in V.bounds_of(lengths)])
+    print(f"{V.dec_ident(e)}: largest relative |mse - numpy| {(np.abs(mse - want) / want).max():.2e}")
+    assert (np.abs(mse - want) <= 1e-12 * want).all()
+    ids = _trial_ids(lengths)
+    for r in (decoder_validation(sd, cat, tg, ids), decoder_validation(sd, cat, tg, ids, max_streams=2),
+              decoder_validation(BiLstmDecoderGPU(2, max(lengths), state_dict=sd), cat, tg, ids)):
+        assert r["features"].shape == (len(cat), e.O) and np.array_equal(r["features"].view(np.int32), feats.cpu().numpy().view(np.int32))
+        assert np.array_equal(r["per_trial_mse"], mse) and r["loss"] == float(mse.mean())
+
+
+@pytest.mark.parametrize("f64", [False, True])
+@pytest.mark.parametrize("e", V.DETECTOR, ids=V.vad_ident)
+def test_case_table_detector(e, f64):
+    """Per detector entry: every trial of the trial form has the bits of ``step_torch`` on a fresh one-stream handle; logits
+    within ``bound(scale)`` of the float64 detector; labels equal to its argmax on EVERY frame (the entries have no near-tie:
+    tests/test_cpu_validation.py::test_case_table_detector_has_no_near_tie)."""
+    from dss_amd.vad import VadLstmGPU
+    sd, x64, ranges = V.detector_inputs(e)
+    x = _cuda(x64, f64)
+    labels, logits = _detector_trials(VadLstmGPU(2, state_dict=sd), x, ranges)
+    for (a, n), s in zip(ranges, V.bounds_of(e.lengths)):
+        lab, lg = VadLstmGPU(1, state_dict=sd).step_torch(x[None, a:a + n], want_logits=True)
+        assert torch.equal(_bits(logits[s]), _bits(lg[0])), f"trial ({a}, {n}): logits differ from the streaming form"
+        assert torch.equal(labels[s], lab[0]), f"trial ({a}, {n}): labels differ from the streaming form"
+    want = V.detector_truth(e)
+    err = float(np.abs(logits.cpu().numpy().astype(np.float64) - want).max())
+    differ = int((labels.cpu().numpy() != (want[:, 1] > want[:, 0])).sum())
+    print(f"{V.vad_ident(e)} f64={f64}: |logits - float64| {err:.2e} (bound {R.bound(e.scale):.0e}); label differences {differ} of {len(want)}")
+    assert err <= R.bound(e.scale)
+    assert differ == 0
+
+
+def test_case_table_tie_model():
+    """Equal classifier rows: every logit pair equal bit for bit, so every label 0 (the first maximum wins), prob exactly 0.5
+    and a loss of ln 2 on every frame -- each frame scored as a trial of its own, against both targets."""
+    from dss_amd.vad import VadLstmGPU
+    sd, x64, ranges = V.detector_inputs(V.TIE)
+    labels, logits = _detector_trials(VadLstmGPU(2, state_dict=sd), _cuda(x64, False), ranges)
+    z = logits.cpu().numpy()
+    assert np.array_equal(z[:, 0].view(np.int32), z[:, 1].view(np.int32)) and np.ptp(z[:, 0]) > 0
+    assert not labels.cpu().numpy().any()
+    want = V.detector_truth(V.TIE)
+    print(f"tie model: |logits - float64| {np.abs(z - want).max():.2e} (bound {R.bound(1):.0e})")
+    assert np.abs(z - want).max() <= R.bound(1)
+    n = len(z)
+    for tg in (np.zeros(n, np.uint8), np.ones(n, np.uint8)):
+        loss, correct, prob = _score(logits, labels, tg, [1] * n)
+        print(f"tie model, targets {int(tg[0])}: largest |loss - ln 2| {np.abs(loss - np.log(2.0)).max():.2e}")
+        assert np.array_equal(prob, np.full(n, 0.5, np.float32))
+        assert np.abs(loss - np.log(2.0)).max() <= 1e-12
+        assert np.array_equal(correct, 1 - tg.astype(np.int32))
+
+
+def test_case_table_detector_validation_sums():
+    """``vad_validation`` on an odd size, (33, 17): ``loss`` is the sum and ``accuracy`` the ratio of the per-trial figures, which
+    are the reduction's on the trial form's logits; a state_dict and a handle the caller keeps agree bit for bit."""
+    from dss_amd.vad import VadLstmGPU
+    from dss_amd.validation import vad_validation
+    e = V.DETECTOR_VALIDATION
+    sd, x64, ranges = V.detector_inputs(e)
+    lengths = list(e.lengths)
+    cat = np.concatenate([x64[a:a + n] for a, n in ranges])
+    tg = np.resize(np.array([0, 0, 1, 1, 1], np.uint8), len(cat))
+    labels, logits = _detector_trials(VadLstmGPU(1, state_dict=sd), _cuda(x64, True), ranges)
+    loss, correct, prob = _score(logits, labels, tg, lengths)
+    ce = V.cross_entropy(logits.cpu().numpy(), tg)
+    want = np.array([ce[s].mean() for s in V.bounds_of(lengths)])
+    print(f"{V.vad_ident(e)}: largest |loss - numpy| {np.abs(loss - want).max():.2e}, largest per-frame cross-entropy {ce.max():.3f}")
+    assert np.abs(loss - want).max() <= 1e-12 * max(1.0, ce.max())
+    lab = labels.cpu().numpy()
+    assert np.array_equal(correct, [int((lab[s] == tg[s]).sum()) for s in V.bounds_of(lengths)])
+    ids = _trial_ids(lengths)
+    for r in (vad_validation(sd, cat, tg, ids), vad_validation(VadLstmGPU(3, state_dict=sd), cat, tg.astype(bool), ids)):
+        assert np.array_equal(r["per_trial_loss"], loss) and np.array_equal(r["per_trial_correct"], correct)
+        assert np.array_equal(r["pred"], lab) and np.array_equal(r["prob"], prob)
+        assert r["loss"] == float(loss.sum()) and r["accuracy"] == float(correct.sum()) / len(cat)
+
+
+def test_case_table_scores():
+    """``dss_vad_score_trials_dev`` on synthetic float32 logits: trials of 1, 255, 256, 257, 512 and 513 frames (its tile is 256
+    frames); N(0, 3) logits mixed with runs where exp(z - m) underflows and runs of equal logits; targets equal to the strict
+    argmax, to its complement, and in runs against every kind of frame; labels the argmax and its complement.
+
+    The bound on a trial's loss against numpy float64 on the same logits is 1e-12 x max(1, the trial's largest per-frame
+    cross-entropy).  It is derived, not measured: a sequential float64 sum of L <= 513 terms is off by at most L x 2^-53 x sum|ce|,
+    which after the division by L is under 513 x 1.1e-16 = 6e-14 times the largest term, and numpy's own mean is at least as
+    close; device and host ``log`` / ``exp`` differ by a few ulp (2.2e-16 relative) of each term, and the sum m + log(.) rounds
+    once more at the size of the result.  All of that is below 1e-13 x max(1, max ce); the bound leaves a factor of ten.
+    ``correct`` is exact; ``prob`` is within 1e-6 of the float64 softmax (it is a float32: 6e-8 relative), exactly 0.0 / 1.0
+    where the other logit's exp underflows and exactly 0.5 on equal logits (exp(-ln 2 (1 + a few 1e-16)) rounds to 0.5 in float32).
+    With ``prob = NULL`` the other results are the same bits."""
+    z, kind, argmax, runs = V.score_inputs()
+    lengths = list(V.SCORE_LENGTHS)
+    sl = V.bounds_of(lengths)
+    logits = torch.from_numpy(z).cuda()
+    soft = V.softmax_speech(z)
+    worst = worst_prob = 0.0
+    for tname, tg in (("argmax", argmax.astype(np.uint8)), ("complement", (1 - argmax).astype(np.uint8)), ("runs", runs)):
+        ce = V.cross_entropy(z, tg)
+        want = np.array([ce[s].mean() for s in sl])
+        bound = np.array([1e-12 * max(1.0, ce[s].max()) for s in sl])
+        for lname, lab in (("argmax", argmax), ("complement", 1 - argmax)):
+            labels = torch.from_numpy(np.ascontiguousarray(lab, dtype=np.int32)).cuda()
+            loss, correct, prob = _score(logits, labels, tg, lengths)
+            loss_np, correct_np, _ = _score(logits, labels, tg, lengths, want_prob=False)
+            assert np.array_equal(loss.view(np.int64), loss_np.view(np.int64)) and np.array_equal(correct, correct_np)
+            ratio = float((np.abs(loss - want) / bound).max())
+            print(f"targets {tname}, labels {lname}: |loss - numpy| {np.abs(loss - want).max():.2e}, at most {ratio:.1e} of a trial's bound; "
+                  f"|prob - softmax| {np.abs(prob - soft).max():.2e}; correct {correct.tolist()}")
+            worst, worst_prob = max(worst, ratio), max(worst_prob, float(np.abs(prob - soft).max()))
+            assert (np.abs(loss - want) <= bound).all()
+            assert np.array_equal(correct, [int((lab[s] == tg[s]).sum()) for s in sl])
+            if tname == "argmax":
+                assert np.array_equal(correct, lengths if lname == "argmax" else [0] * len(lengths))
+            assert np.abs(prob - soft).max() <= 1e-6
+            assert np.array_equal(prob[kind == 1], np.zeros((kind == 1).sum(), np.float32))
+            assert np.array_equal(prob[kind == 2], np.ones((kind == 2).sum(), np.float32))
+            assert np.array_equal(prob[kind == 3], np.full((kind == 3).sum(), 0.5, np.float32))
+        if tname != "runs":          # loss 0 / the whole gap on the underflow runs
+            under = (kind == 1) | (kind == 2)
+            assert set(np.unique(ce[under])) == ({0.0} if tname == "argmax" else {2.0 * V.UNDERFLOW})
+    print(f"scores: worst |loss - numpy| / bound {worst:.1e}, worst |prob - softmax| {worst_prob:.2e}")
+
+
+@pytest.mark.parametrize("frames,outputs", V.MSE_CASES)
+def test_case_table_mse(frames, outputs):
+    """``dss_dec_mse_trials_dev`` with frames x outputs on either side of the kernel's stride of 256 elements, between two short
+    trials: within 1e-12 relative of numpy float64, and exactly 0.0 where the features are their targets bit for bit."""
+    lengths, feats, tg = V.mse_inputs(frames, outputs)
+    f, t = torch.from_numpy(feats).cuda(), torch.from_numpy(tg).cuda()
+    mse = _mse(f, t, lengths)
+    d = feats.astype(np.float64) - tg.astype(np.float64)
+    want = np.array([np.mean(d[s] ** 2) for s in V.bounds_of(lengths)])
+    print(f"({frames}, {outputs}): largest relative |mse - numpy| {(np.abs(mse - want) / want).max():.2e}")
+    assert (np.abs(mse - want) <= 1e-12 * want).all()
+    zero = _mse(f, f.clone(), lengths)
+    assert np.array_equal(zero, np.zeros(len(lengths))) and not np.signbit(zero).any()
