@@ -21,24 +21,19 @@ struct dss_avad {
     double *d_win = nullptr, *d_tw = nullptr, *d_mel_w = nullptr;
     int *d_band_lo = nullptr, *d_band_off = nullptr;
     // per call (one call per handle in flight)
-    std::vector<DssAvadTrialDesc> desc;
-    std::vector<DssAvadTile> tiles;
-    DssAvadTrialDesc *d_desc = nullptr;  size_t desc_cap = 0;
-    DssAvadTile *d_tiles = nullptr;      size_t tiles_cap = 0;
-    double *d_le = nullptr;              size_t le_cap = 0;       // log energies when the caller does not want them
+    DssDevTable<DssAvadTrialDesc> desc;
+    DssDevTable<DssAvadTile> tiles;
+    DssDevArray<double> d_le;                                     // log energies when the caller does not want them
     // staging of the host-buffer form
-    short *d_audio = nullptr;            size_t audio_cap = 0;
-    unsigned char *d_labels = nullptr;   size_t labels_cap = 0;
-    double *d_le_out = nullptr;          size_t le_out_cap = 0;
-    double *d_thr = nullptr;             size_t thr_cap = 0;
+    DssDevArray<short> d_audio;
+    DssDevArray<unsigned char> d_labels;
+    DssDevArray<double> d_le_out, d_thr;
     // the prepared audio (dss_avad_set_gain, dss_avad_prepare_trials*)
     double *d_gain = nullptr;            bool gain_set = false;
-    std::vector<DssAvadPeakTile> ptiles;
-    std::vector<DssAvadTile> stiles;
-    DssAvadPeakTile *d_ptiles = nullptr; size_t ptiles_cap = 0;
-    DssAvadTile *d_stiles = nullptr;     size_t stiles_cap = 0;
-    int *d_peaks = nullptr;              size_t peaks_cap = 0;
-    short *d_prep = nullptr;             size_t prep_cap = 0;
+    DssDevTable<DssAvadPeakTile> ptiles;
+    DssDevTable<DssAvadTile> stiles;
+    DssDevArray<int> d_peaks;
+    DssDevArray<short> d_prep;
 };
 
 // One call's outputs and options, all optional but for what the entry point demands.
@@ -161,26 +156,15 @@ extern "C" int dss_avad_vote_host(const double *log_energy, int W, const dss_ava
     return DSS_OK;
 }
 
-extern "C" void dss_avad_destroy(dss_avad *h)
-{
-    if (!h) return;
-    hipSetDevice(h->device);
-    hipDeviceSynchronize();
-    h->blocks.free_all();
-    delete h;
-}
+extern "C" void dss_avad_destroy(dss_avad *h) { dss_destroy_handle(h); }
 
 static int avad_setup(dss_avad *h, const double *window_fn, const double *mel)
 {
     const dss_avad_params &p = h->p;
     const int N = p.window;
-    std::vector<double> win((size_t)N), tw((size_t)2 * N);
-    for (int j = 0; j < N; ++j) {
-        win[j] = window_fn[j] * (1.0 / 32768.0);          // exact: x / 2^15 * w == x * (w * 2^-15)
-        const double a = 2.0 * M_PI * (double)j / (double)N;
-        tw[2 * j] = cos(a);
-        tw[2 * j + 1] = sin(a);
-    }
+    std::vector<double> win((size_t)N);
+    const std::vector<double> tw = dss_twiddles(N);
+    for (int j = 0; j < N; ++j) win[j] = window_fn[j] * (1.0 / 32768.0);          // exact: x / 2^15 * w == x * (w * 2^-15)
     // every band's column of the mel matrix as its run first nonzero .. last nonzero (a triangular filter: one run)
     std::vector<double> mel_w;
     std::vector<int> lo((size_t)p.n_bands), off((size_t)p.n_bands + 1);
@@ -261,62 +245,55 @@ static int avad_run(dss_avad *h, const short *d_audio, long long audio_base, int
     const bool want_peaks = use_gain || c.d_peaks;
     // descriptor table, longest trial first: the long trials' tiles start first and the short ones fill the tail
     const std::vector<int> order = trials_longest_first(n_trials, len);
-    std::vector<long long> out_frame((size_t)n_trials), out_sample((size_t)n_trials);
-    long long total = 0, samples = 0;
-    for (int i = 0; i < n_trials; ++i) {
-        out_frame[i] = total; out_sample[i] = samples;
-        if (want_frames) total += (len[i] - N) / shift + 1;
-        samples += len[i];
-    }
-    h->desc.resize((size_t)n_trials);
-    h->tiles.clear(); h->ptiles.clear(); h->stiles.clear();
+    const std::vector<long long> out_frame = trials_offsets(n_trials, [&](int i) { return want_frames ? (len[i] - N) / shift + 1 : 0; });
+    const std::vector<long long> out_sample = trials_offsets(n_trials, [&](int i) { return len[i]; });
+    const long long total = out_frame[n_trials];
+    std::vector<DssAvadTile> &tiles = h->tiles.host, &stiles = h->stiles.host;
+    std::vector<DssAvadPeakTile> &ptiles = h->ptiles.host;
+    h->desc.host.resize((size_t)n_trials);
+    tiles.clear(); ptiles.clear(); stiles.clear();
     for (int k = 0; k < n_trials; ++k) {
         const int i = order[k];
-        DssAvadTrialDesc &t = h->desc[k];
+        DssAvadTrialDesc &t = h->desc.host[k];
         t.first = first[i] - audio_base; t.out_frame = out_frame[i]; t.out_sample = out_sample[i]; t.n = len[i]; t.lead = lead[i];
         t.W = want_frames ? (len[i] - N) / shift + 1 : 0; t.silence = c.silence && c.silence[i] ? 1 : 0; t.index = i;
         t.normalize = c.normalize && c.normalize[i] ? 1 : 0;
-        for (int f0 = 0; f0 < t.W; f0 += AVAD_TILE_FRAMES) h->tiles.push_back(DssAvadTile{k, f0});
+        for (int f0 = 0; f0 < t.W; f0 += AVAD_TILE_FRAMES) tiles.push_back(DssAvadTile{k, f0});
         if (want_peaks) {
             // the cut audio[first .. first + n), clamped where the audio ends: the last `lead` samples count although the shift drops them
             const long long cut = std::min((long long)len[i], c.n_avail - t.first);
             for (long long s0 = 0; s0 < cut; s0 += AVAD_PEAK_TILE)
-                h->ptiles.push_back(DssAvadPeakTile{t.first + s0, (int)std::min((long long)AVAD_PEAK_TILE, cut - s0), i});
+                ptiles.push_back(DssAvadPeakTile{t.first + s0, (int)std::min((long long)AVAD_PEAK_TILE, cut - s0), i});
         }
         if (c.d_prepared)
-            for (long long s0 = 0; s0 < t.n; s0 += AVAD_PEAK_TILE) h->stiles.push_back(DssAvadTile{k, (int)s0});
+            for (long long s0 = 0; s0 < t.n; s0 += AVAD_PEAK_TILE) stiles.push_back(DssAvadTile{k, (int)s0});
     }
-    if (h->tiles.size() > 0x7fffffffULL || h->ptiles.size() > 0x7fffffffULL || h->stiles.size() > 0x7fffffffULL) {
+    if (tiles.size() > 0x7fffffffULL || ptiles.size() > 0x7fffffffULL || stiles.size() > 0x7fffffffULL) {
         dss_set_error("acoustic VAD: too many tiles for one launch");
         return DSS_EINVAL;
     }
     double *d_le = c.d_le;
     int *d_peaks = c.d_peaks;
-    int rc = h->blocks.grow_headroom(&h->d_desc, &h->desc_cap, h->desc.size());
-    if (!rc) rc = h->blocks.grow_headroom(&h->d_tiles, &h->tiles_cap, h->tiles.size());
-    if (!rc && want_frames && !d_le) { rc = h->blocks.grow_headroom(&h->d_le, &h->le_cap, (size_t)total); d_le = h->d_le; }
-    if (!rc && want_peaks) rc = h->blocks.grow_headroom(&h->d_ptiles, &h->ptiles_cap, h->ptiles.size());
-    if (!rc && want_peaks && !d_peaks) { rc = h->blocks.grow_headroom(&h->d_peaks, &h->peaks_cap, (size_t)n_trials); d_peaks = h->d_peaks; }
-    if (!rc && c.d_prepared) rc = h->blocks.grow_headroom(&h->d_stiles, &h->stiles_cap, h->stiles.size());
+    int rc = DSS_OK;
+    if (want_frames && !d_le) { rc = h->d_le.grow_headroom(h->blocks, (size_t)total); d_le = h->d_le; }
+    if (!rc && want_peaks && !d_peaks) { rc = h->d_peaks.grow_headroom(h->blocks, (size_t)n_trials); d_peaks = h->d_peaks; }
+    if (!rc) rc = h->desc.upload(h->blocks, st);
+    if (!rc) rc = h->tiles.upload(h->blocks, st);
     if (rc) return rc;
-    DSS_HIP_CHECK(hipMemcpyAsync(h->d_desc, h->desc.data(), sizeof(DssAvadTrialDesc) * h->desc.size(), hipMemcpyHostToDevice, st));
-    if (!h->tiles.empty())
-        DSS_HIP_CHECK(hipMemcpyAsync(h->d_tiles, h->tiles.data(), sizeof(DssAvadTile) * h->tiles.size(), hipMemcpyHostToDevice, st));
     if (want_peaks) {
         DSS_HIP_CHECK(hipMemsetAsync(d_peaks, 0, sizeof(int) * (size_t)n_trials, st));
-        if (!h->ptiles.empty())
-            DSS_HIP_CHECK(hipMemcpyAsync(h->d_ptiles, h->ptiles.data(), sizeof(DssAvadPeakTile) * h->ptiles.size(), hipMemcpyHostToDevice, st));
-        rc = dss_launch_avad_peak(d_audio, h->d_ptiles, (int)h->ptiles.size(), d_peaks, st);
+        rc = h->ptiles.upload(h->blocks, st);
+        if (!rc) rc = dss_launch_avad_peak(d_audio, h->ptiles.dev, (int)ptiles.size(), d_peaks, st);
         if (rc) return rc;
     }
     if (want_frames) {
-        rc = dss_launch_avad_energy(h->d, d_audio, h->d_desc, h->d_tiles, (int)h->tiles.size(), d_le, use_gain ? d_peaks : nullptr, st);
-        if (!rc) rc = dss_launch_avad_vote(h->d, h->d_desc, n_trials, d_le, c.d_labels, c.d_thr, st);
+        rc = dss_launch_avad_energy(h->d, d_audio, h->desc.dev, h->tiles.dev, (int)tiles.size(), d_le, use_gain ? d_peaks : nullptr, st);
+        if (!rc) rc = dss_launch_avad_vote(h->d, h->desc.dev, n_trials, d_le, c.d_labels, c.d_thr, st);
         if (rc) return rc;
     }
-    if (c.d_prepared && !h->stiles.empty()) {
-        DSS_HIP_CHECK(hipMemcpyAsync(h->d_stiles, h->stiles.data(), sizeof(DssAvadTile) * h->stiles.size(), hipMemcpyHostToDevice, st));
-        rc = dss_launch_avad_prepare(h->d, d_audio, h->d_desc, h->d_stiles, (int)h->stiles.size(), d_peaks, c.d_prepared, st);
+    if (c.d_prepared && !stiles.empty()) {
+        rc = h->stiles.upload(h->blocks, st);
+        if (!rc) rc = dss_launch_avad_prepare(h->d, d_audio, h->desc.dev, h->stiles.dev, (int)stiles.size(), d_peaks, c.d_prepared, st);
         if (rc) return rc;
     }
     return (int)total;
@@ -348,10 +325,10 @@ extern "C" int dss_avad_labels_trials(dss_avad *h, const int16_t *audio, long lo
     // only the samples the trials span cross the bus, once, however the trials overlap
     long long lo, hi;
     trials_hull(n_trials, first, len, lead, &lo, &hi);
-    int rc = h->blocks.grow_headroom(&h->d_audio, &h->audio_cap, (size_t)(hi - lo) + 1);
-    if (!rc) rc = h->blocks.grow_headroom(&h->d_labels, &h->labels_cap, (size_t)total);
-    if (!rc) rc = h->blocks.grow_headroom(&h->d_le_out, &h->le_out_cap, (size_t)total);
-    if (!rc) rc = h->blocks.grow_headroom(&h->d_thr, &h->thr_cap, (size_t)n_trials);
+    int rc = h->d_audio.grow_headroom(h->blocks, (size_t)(hi - lo) + 1);
+    if (!rc) rc = h->d_labels.grow_headroom(h->blocks, (size_t)total);
+    if (!rc) rc = h->d_le_out.grow_headroom(h->blocks, (size_t)total);
+    if (!rc) rc = h->d_thr.grow_headroom(h->blocks, (size_t)n_trials);
     if (rc) return rc;
     if (hi > lo) DSS_HIP_CHECK(hipMemcpy(h->d_audio, audio + lo, sizeof(short) * (size_t)(hi - lo), hipMemcpyHostToDevice));
     AvadCall c;
@@ -402,12 +379,12 @@ extern "C" int dss_avad_prepare_trials(dss_avad *h, const int16_t *audio, long l
     trials_hull(n_trials, first, len, nullptr, &lo, &hi);
     hi = std::max(lo, std::min(hi, n_audio));
     for (int i = 0; i < n_trials; ++i) samples += len[i];
-    int rc = h->blocks.grow_headroom(&h->d_audio, &h->audio_cap, (size_t)(hi - lo) + 1);
-    if (!rc && labels) rc = h->blocks.grow_headroom(&h->d_labels, &h->labels_cap, (size_t)total);
-    if (!rc && labels) rc = h->blocks.grow_headroom(&h->d_le_out, &h->le_out_cap, (size_t)total);
-    if (!rc && labels) rc = h->blocks.grow_headroom(&h->d_thr, &h->thr_cap, (size_t)n_trials);
-    if (!rc && prepared) rc = h->blocks.grow_headroom(&h->d_prep, &h->prep_cap, (size_t)samples + 1);
-    if (!rc && peaks) rc = h->blocks.grow_headroom(&h->d_peaks, &h->peaks_cap, (size_t)n_trials);
+    int rc = h->d_audio.grow_headroom(h->blocks, (size_t)(hi - lo) + 1);
+    if (!rc && labels) rc = h->d_labels.grow_headroom(h->blocks, (size_t)total);
+    if (!rc && labels) rc = h->d_le_out.grow_headroom(h->blocks, (size_t)total);
+    if (!rc && labels) rc = h->d_thr.grow_headroom(h->blocks, (size_t)n_trials);
+    if (!rc && prepared) rc = h->d_prep.grow_headroom(h->blocks, (size_t)samples + 1);
+    if (!rc && peaks) rc = h->d_peaks.grow_headroom(h->blocks, (size_t)n_trials);
     if (rc) return rc;
     if (hi > lo) DSS_HIP_CHECK(hipMemcpy(h->d_audio, audio + lo, sizeof(short) * (size_t)(hi - lo), hipMemcpyHostToDevice));
     AvadCall c;

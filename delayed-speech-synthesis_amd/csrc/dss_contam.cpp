@@ -22,14 +22,10 @@ struct dss_contam {
     DssDevBlocks blocks;
     double *d_win = nullptr, *d_tw = nullptr, *d_shift = nullptr;
     // per call (one call per handle in flight)
-    std::vector<unsigned char> keep;
-    unsigned char *d_keep = nullptr; size_t keep_cap = 0;
-    double *d_aud = nullptr;         size_t aud_cap = 0;
-    double *d_partial = nullptr;     size_t partial_cap = 0;
+    DssDevTable<unsigned char> keep;
+    DssDevArray<double> d_aud, d_partial;
     // staging of the host-buffer form
-    double *d_x = nullptr;           size_t x_cap = 0;
-    double *d_audio = nullptr;       size_t audio_cap = 0;
-    double *d_out = nullptr;         size_t out_cap = 0;
+    DssDevArray<double> d_x, d_audio, d_out;
 };
 
 extern "C" int dss_contam_check_params(const dss_contam_params *p)
@@ -138,33 +134,19 @@ extern "C" int dss_contam_plan(const dss_contam_params *p, long long n_rows, int
     return DSS_OK;
 }
 
-extern "C" void dss_contam_destroy(dss_contam *h)
-{
-    if (!h) return;
-    hipSetDevice(h->device);
-    hipDeviceSynchronize();
-    h->blocks.free_all();
-    delete h;
-}
+extern "C" void dss_contam_destroy(dss_contam *h) { dss_destroy_handle(h); }
 
 static int contam_setup(dss_contam *h, const double *window)
 {
     const dss_contam_params &p = h->p;
     dss_contam_shape(p.nperseg, p.hop, p.bin_lo, p.n_bins, p.max_lag, &h->v);
-    const int K4 = h->v.spec.K4, nfft = p.nperseg;
-    std::vector<double> win((size_t)K4, 0.0), tw((size_t)2 * nfft);
+    std::vector<double> win((size_t)h->v.spec.K4, 0.0);
     std::copy(window, window + p.nperseg, win.begin());
-    for (int j = 0; j < nfft; ++j) {
-        const double a = 2.0 * M_PI * (double)j / (double)nfft;
-        tw[2 * j] = cos(a);
-        tw[2 * j + 1] = sin(a);
-    }
-    int rc = h->blocks.alloc_bytes(win.size() * sizeof(double), (void **)&h->d_win);
-    if (!rc) rc = h->blocks.alloc_bytes(tw.size() * sizeof(double), (void **)&h->d_tw);
+    const std::vector<double> tw = dss_twiddles(p.nperseg);
+    int rc = h->blocks.upload(win.data(), win.size(), &h->d_win);
+    if (!rc) rc = h->blocks.upload(tw.data(), tw.size(), &h->d_tw);
     if (!rc) rc = h->blocks.alloc_bytes(CONTAM_PAD * sizeof(double), (void **)&h->d_shift);
     if (rc) return rc;
-    DSS_HIP_CHECK(hipMemcpy(h->d_win, win.data(), win.size() * sizeof(double), hipMemcpyHostToDevice));
-    DSS_HIP_CHECK(hipMemcpy(h->d_tw, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice));
     h->v.spec.win = h->d_win; h->v.spec.tw = h->d_tw;
     return DSS_OK;
 }
@@ -192,17 +174,16 @@ static int contam_run(dss_contam *h, const double *d_x, int ld, int C, const dou
                       const unsigned char *keep_frames, double *d_out, hipStream_t st)
 {
     const DssContamDev &v = h->v;
-    h->keep.assign((size_t)W, 1);
+    h->keep.host.assign((size_t)W, 1);
     if (keep_frames)
-        for (int t = 0; t < W; ++t) h->keep[t] = keep_frames[t] ? 1 : 0;
+        for (int t = 0; t < W; ++t) h->keep.host[t] = keep_frames[t] ? 1 : 0;
     int n_tiles, chunks, tiles_per_chunk;
     contam_cut(v, W, C, &n_tiles, &chunks, &tiles_per_chunk);
-    int rc = h->blocks.grow_headroom(&h->d_keep, &h->keep_cap, (size_t)W);
-    if (!rc) rc = h->blocks.grow_headroom(&h->d_aud, &h->aud_cap, (size_t)W * CONTAM_PAD);
-    if (!rc) rc = h->blocks.grow_headroom(&h->d_partial, &h->partial_cap, (size_t)chunks * v.nlag * C * contam_record(v.B));
+    int rc = h->d_aud.grow_headroom(h->blocks, (size_t)W * CONTAM_PAD);
+    if (!rc) rc = h->d_partial.grow_headroom(h->blocks, (size_t)chunks * v.nlag * C * contam_record(v.B));
+    if (!rc) rc = h->keep.upload(h->blocks, st);
     if (rc) return rc;
-    DSS_HIP_CHECK(hipMemcpyAsync(h->d_keep, h->keep.data(), (size_t)W, hipMemcpyHostToDevice, st));
-    return dss_launch_contam(v, d_x, ld, C, d_audio, T, W, h->d_keep, h->d_aud, h->d_shift, h->d_partial, chunks, tiles_per_chunk, d_out, st);
+    return dss_launch_contam(v, d_x, ld, C, d_audio, T, W, h->keep.dev, h->d_aud, h->d_shift, h->d_partial, chunks, tiles_per_chunk, d_out, st);
 }
 
 extern "C" int dss_contam_moments_dev(dss_contam *h, const double *d_brain, long long n_rows, int ld, int C, const double *d_audio,
@@ -224,16 +205,13 @@ extern "C" int dss_contam_moments(dss_contam *h, const double *brain, long long 
     DSS_HIP_CHECK(hipSetDevice(h->device));
     long long off[8];
     dss_contam_layout(h->v, C, off);
-    int rc = h->blocks.grow_headroom(&h->d_x, &h->x_cap, (size_t)n_rows * ld + 1);
-    if (!rc) rc = h->blocks.grow_headroom(&h->d_audio, &h->audio_cap, (size_t)n_rows);
-    if (!rc) rc = h->blocks.grow_headroom(&h->d_out, &h->out_cap, (size_t)off[7]);
+    int rc = h->d_x.grow_headroom(h->blocks, (size_t)n_rows * ld + 1);
+    if (!rc) rc = h->d_audio.grow_headroom(h->blocks, (size_t)n_rows);
+    if (!rc) rc = h->d_out.grow_headroom(h->blocks, (size_t)off[7]);
     if (rc) return rc;
     // the last row ends behind its C channels: the caller's array may be a view that ends there
     DSS_HIP_CHECK(hipMemcpy(h->d_x, brain, sizeof(double) * ((size_t)(n_rows - 1) * ld + C), hipMemcpyHostToDevice));
     DSS_HIP_CHECK(hipMemcpy(h->d_audio, audio, sizeof(double) * (size_t)n_rows, hipMemcpyHostToDevice));
     rc = contam_run(h, h->d_x, ld, C, h->d_audio, n_rows, (int)W, keep_frames, h->d_out, nullptr);
-    if (rc) return rc;
-    DSS_HIP_CHECK(hipStreamSynchronize(nullptr));
-    DSS_HIP_CHECK(hipMemcpy(out, h->d_out, sizeof(double) * (size_t)off[7], hipMemcpyDeviceToHost));
-    return DSS_OK;
+    return rc ? rc : dss_fetch(out, h->d_out.p, (size_t)off[7]);
 }

@@ -21,9 +21,8 @@ struct dss_dec {
     // trial lists (dss_dec_forward_trials_dev): per trial, longest first: output row | frame count, first row; pinned staging
     // and device
     DssPinnedStage tstage;
-    int *d_tmeta = nullptr;
-    long long *d_tout = nullptr;
-    size_t tmeta_cap = 0, tout_cap = 0;
+    DssDevArray<int> d_tmeta;
+    DssDevArray<long long> d_tout;
 };
 
 int dss_dec_device_weights(dss_dec *v, int *device, int *n_inputs, int *hidden_units, int *n_outputs, float *w[10])
@@ -170,15 +169,13 @@ extern "C" int dss_dec_forward_trials_dev(dss_dec *v, const void *d_frames, int 
     DSS_HIP_CHECK(hipSetDevice(v->device));
     hipStream_t st = (hipStream_t)hip_stream;
     const size_t n = (size_t)n_trials;
-    std::vector<long long> out_row(n);
-    long long row = 0;
-    for (int i = 0; i < n_trials; ++i) { out_row[i] = row; row += len[i]; }
+    const std::vector<long long> out_row = trials_offsets(n_trials, [&](int i) { return len[i]; });
     const std::vector<int> order = trials_longest_first(n_trials, len);
     long long *tout = (long long *)v->tstage.acquire((sizeof(long long) + 2 * sizeof(int)) * n);      // [n] output rows, then [2][n] ints
     if (!tout) { dss_set_error("pinned staging for the trial table failed"); return DSS_ENOMEM; }
     int *tmeta = (int *)(tout + n);
     for (int k = 0; k < n_trials; ++k) { const int i = order[k]; tmeta[k] = len[i]; tmeta[n + k] = (int)first[i]; tout[k] = out_row[i]; }
-    if ((rc = v->blocks.grow(&v->d_tmeta, &v->tmeta_cap, 2 * n)) || (rc = v->blocks.grow(&v->d_tout, &v->tout_cap, n))) return rc;
+    if ((rc = v->d_tmeta.grow(v->blocks, 2 * n)) || (rc = v->d_tout.grow(v->blocks, n))) return rc;
     DSS_HIP_CHECK(hipMemcpyAsync(v->d_tmeta, tmeta, sizeof(int) * 2 * n, hipMemcpyHostToDevice, st));
     DSS_HIP_CHECK(hipMemcpyAsync(v->d_tout, tout, sizeof(long long) * n, hipMemcpyHostToDevice, st));
     if ((rc = v->tstage.commit(st))) return rc;

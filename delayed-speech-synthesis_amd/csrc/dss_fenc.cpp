@@ -16,16 +16,14 @@ struct dss_fenc {
     DssFencDev d = {};
     DssDevBlocks blocks;
     // per call (one call per handle in flight)
-    std::vector<DssFencTrial> desc;
-    std::vector<DssFencTile> tiles;
-    DssFencTrial *d_desc = nullptr;  size_t desc_cap = 0;
-    DssFencTile *d_tiles = nullptr;  size_t tiles_cap = 0;
-    double *d_scores = nullptr;      size_t scores_cap = 0;
+    DssDevTable<DssFencTrial> desc;
+    DssDevTable<DssFencTile> tiles;
+    DssDevArray<double> d_scores;
     long long last_subframes = 0;
     hipStream_t last_stream = nullptr;
     // staging of the host-buffer form
-    short *d_audio = nullptr;        size_t audio_cap = 0;
-    float *d_out = nullptr;          size_t out_cap = 0;
+    DssDevArray<short> d_audio;
+    DssDevArray<float> d_out;
     // development timing: events around the three launches of a call
     bool timing = false, stamped = false;
     hipEvent_t stamps[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -53,26 +51,18 @@ extern "C" long long dss_fenc_frame_offsets(const long long *offsets, int n_tria
 extern "C" void dss_fenc_destroy(dss_fenc *f)
 {
     if (!f) return;
-    hipSetDevice(f->device);
-    hipDeviceSynchronize();
     for (hipEvent_t e : f->stamps)
         if (e) hipEventDestroy(e);
-    f->blocks.free_all();
-    delete f;
+    dss_destroy_handle(f);
 }
 
 static int fenc_setup(dss_fenc *f)
 {
     std::vector<float> win(FENC_WINDOW);
-    std::vector<double> tw((size_t)2 * FENC_WINDOW);
+    const std::vector<double> tw = dss_twiddles(FENC_WINDOW);
     for (int k = 0; k < FENC_FRAME; ++k) {
         const double s = sin(.5 * M_PI * (k + .5) / FENC_FRAME);
         win[k] = win[FENC_WINDOW - 1 - k] = (float)sin(.5 * M_PI * s * s);
-    }
-    for (int j = 0; j < FENC_WINDOW; ++j) {
-        const double a = 2.0 * M_PI * (double)j / (double)FENC_WINDOW;
-        tw[2 * j] = cos(a);
-        tw[2 * j + 1] = sin(a);
     }
     const LpcTables T;
     float *p32 = nullptr;
@@ -116,24 +106,21 @@ static long long fenc_check(const dss_fenc *f, long long n, const long long *off
 static int fenc_run(dss_fenc *f, const short *d_audio, long long base, const long long *offsets, int n_trials, long long total,
                     float *d_out36, hipStream_t st)
 {
-    f->desc.resize((size_t)n_trials);
-    f->tiles.clear();
+    f->desc.host.resize((size_t)n_trials);
+    f->tiles.host.clear();
     long long out = 0;
     for (int i = 0; i < n_trials; ++i) {
-        DssFencTrial &t = f->desc[i];
+        DssFencTrial &t = f->desc.host[i];
         t.first = offsets[i] - base; t.n = offsets[i + 1] - offsets[i]; t.out = out; t.frames = (int)(t.n / FENC_FRAME); t.pad = 0;
         out += t.frames;
-        for (int f0 = 0; f0 < t.frames; f0 += FENC_TILE_FRAMES) f->tiles.push_back(DssFencTile{i, f0});
+        for (int f0 = 0; f0 < t.frames; f0 += FENC_TILE_FRAMES) f->tiles.host.push_back(DssFencTile{i, f0});
     }
-    if (f->tiles.size() > 0x7fffffffULL / FENC_TILE_FRAMES) { dss_set_error("feature encoder: too many frames for one launch"); return DSS_EINVAL; }
-    int rc = f->blocks.grow_headroom(&f->d_desc, &f->desc_cap, f->desc.size());
-    if (!rc) rc = f->blocks.grow_headroom(&f->d_tiles, &f->tiles_cap, f->tiles.size());
-    if (!rc) rc = f->blocks.grow_headroom(&f->d_scores, &f->scores_cap, (size_t)total * 2 * FENC_LAGS);
-    if (rc) return rc;
-    DSS_HIP_CHECK(hipMemcpyAsync(f->d_desc, f->desc.data(), sizeof(DssFencTrial) * f->desc.size(), hipMemcpyHostToDevice, st));
-    DSS_HIP_CHECK(hipMemcpyAsync(f->d_tiles, f->tiles.data(), sizeof(DssFencTile) * f->tiles.size(), hipMemcpyHostToDevice, st));
-    rc = dss_launch_fenc(f->d, d_audio, f->d_desc, n_trials, f->d_tiles, (int)f->tiles.size(), d_out36, f->d_scores, st,
-                         f->timing ? f->stamps : nullptr);
+    if (f->tiles.host.size() > 0x7fffffffULL / FENC_TILE_FRAMES) { dss_set_error("feature encoder: too many frames for one launch"); return DSS_EINVAL; }
+    int rc = f->d_scores.grow_headroom(f->blocks, (size_t)total * 2 * FENC_LAGS);
+    if (!rc) rc = f->desc.upload(f->blocks, st);
+    if (!rc) rc = f->tiles.upload(f->blocks, st);
+    if (!rc) rc = dss_launch_fenc(f->d, d_audio, f->desc.dev, n_trials, f->tiles.dev, (int)f->tiles.host.size(), d_out36, f->d_scores, st,
+                                  f->timing ? f->stamps : nullptr);
     if (rc) return rc;
     f->stamped = f->timing;
     f->last_subframes = 2 * total;
@@ -164,15 +151,13 @@ extern "C" long long dss_fenc_features_trials(dss_fenc *f, const short *audio, l
     if (!audio || !out36) { dss_set_error("bad arguments"); return DSS_EINVAL; }
     DSS_HIP_CHECK(hipSetDevice(f->device));
     const long long lo = offsets[0], hi = offsets[n_trials];             // only the samples the trials span cross the bus
-    int rc = f->blocks.grow_headroom(&f->d_audio, &f->audio_cap, (size_t)(hi - lo));
-    if (!rc) rc = f->blocks.grow_headroom(&f->d_out, &f->out_cap, (size_t)total * FENC_OUT);
+    int rc = f->d_audio.grow_headroom(f->blocks, (size_t)(hi - lo));
+    if (!rc) rc = f->d_out.grow_headroom(f->blocks, (size_t)total * FENC_OUT);
     if (rc) return rc;
     DSS_HIP_CHECK(hipMemcpy(f->d_audio, audio + lo, sizeof(short) * (size_t)(hi - lo), hipMemcpyHostToDevice));
     rc = fenc_run(f, f->d_audio, lo, offsets, n_trials, total, f->d_out, nullptr);
-    if (rc) return rc;
-    DSS_HIP_CHECK(hipStreamSynchronize(nullptr));
-    DSS_HIP_CHECK(hipMemcpy(out36, f->d_out, sizeof(float) * (size_t)total * FENC_OUT, hipMemcpyDeviceToHost));
-    return total;
+    if (!rc) rc = dss_fetch(out36, f->d_out.p, (size_t)total * FENC_OUT);
+    return rc ? rc : total;
 }
 
 extern "C" long long dss_fenc_tap_scores(dss_fenc *f, double *out, long long n)

@@ -72,40 +72,35 @@ struct dss_hga {
     // optional fused front end
     int c_raw = 0, n_grids = 0;
     int *d_src_col = nullptr, *d_grid_of = nullptr, *d_comp_cols = nullptr, *d_comp_off = nullptr;
-    double *d_pre = nullptr, *d_raw = nullptr, *d_wire = nullptr;
-    size_t pre_cap = 0, raw_cap = 0, wire_cap = 0;
+    DssDevArray<double> d_pre, d_raw, d_wire;
     double *d_zi0[2] = {nullptr, nullptr};
-    double *d_in = nullptr, *d_out = nullptr;
-    size_t in_cap = 0, out_cap = 0;
+    DssDevArray<double> d_in, d_out;
     double *d_zs[2] = {nullptr, nullptr};                  // z-score mean / std on the device ...
     std::vector<double> zs_host[2];                        // ... and on the host (host-buffer entry points); empty = no z-score
     std::vector<double> zs_dev[2];                         // the values the resident device copies hold (dss_hga_set_zscore)
     // trial lists (dss_hga_extract_trials*): bad-channel patches, the descriptor table and the host-buffer form's staging
     std::vector<int> patch_dst, patch_cols, patch_off;     // empty = no patch
     int *d_patch_dst = nullptr, *d_patch_cols = nullptr, *d_patch_off = nullptr;
-    std::vector<DssHgaTrialDesc> desc;
-    DssHgaTrialDesc *d_desc = nullptr;
-    std::vector<long long> single_rows;                    // output frames of the trials that emit one frame
-    long long *d_single = nullptr;
-    double *d_trec = nullptr, *d_tout = nullptr;
-    size_t desc_cap = 0, single_cap = 0, trec_cap = 0, tout_cap = 0;
+    DssDevTable<DssHgaTrialDesc> desc;
+    DssDevTable<long long> single_rows;                    // output frames of the trials that emit one frame
+    DssDevArray<double> d_trec, d_tout;
 };
 
 static int hga_grow_rows(dss_hga *h, int need_rows)
 {
     if (need_rows <= h->d.cap_rows) return DSS_OK;
-    const int new_cap = need_rows + h->d.frame_length;
+    const int cap = need_rows + h->d.frame_length;
     double *nr = nullptr;
-    int rc = h->blocks.alloc_bytes(sizeof(double) * (size_t)h->d.S * new_cap * h->d.C, (void **)&nr);
+    int rc = h->blocks.alloc_bytes(sizeof(double) * (size_t)h->d.S * cap * h->d.C, (void **)&nr);
     if (rc) return rc;
     if (h->d.rows) {
-        DSS_HIP_CHECK(hipMemcpy2D(nr, sizeof(double) * (size_t)new_cap * h->d.C, h->d.rows,
+        DSS_HIP_CHECK(hipMemcpy2D(nr, sizeof(double) * (size_t)cap * h->d.C, h->d.rows,
                                   sizeof(double) * (size_t)h->d.cap_rows * h->d.C,
                                   sizeof(double) * (size_t)h->d.overlap * h->d.C, h->d.S, hipMemcpyDeviceToDevice));
         h->blocks.release(h->d.rows);
     }
     h->d.rows = nr;
-    h->d.cap_rows = new_cap;
+    h->d.cap_rows = cap;
     return DSS_OK;
 }
 
@@ -258,8 +253,8 @@ extern "C" int dss_hga_extract(dss_hga *h, const double *data, int n, double *ou
     const size_t in_n = (size_t)h->d.S * n * h->d.C;
     const int Wmax = dss_hga_frames_for(h, n);
     const size_t out_n = (size_t)h->d.S * (Wmax > 0 ? Wmax : 1) * h->d.C;
-    int rc = h->blocks.grow(&h->d_in, &h->in_cap, in_n);
-    if (!rc) rc = h->blocks.grow(&h->d_out, &h->out_cap, out_n);
+    int rc = h->d_in.grow(h->blocks, in_n);
+    if (!rc) rc = h->d_out.grow(h->blocks, out_n);
     if (rc) return rc;
     DSS_HIP_CHECK(hipMemcpy(h->d_in, data, in_n * sizeof(double), hipMemcpyHostToDevice));
     int W;
@@ -307,7 +302,7 @@ extern "C" int dss_hga_extract_raw_dev(dss_hga *h, const double *d_raw, int n, d
     DSS_HIP_CHECK(hipSetDevice(h->device));
     // two launches: the front end (HBM-bound), then the extractor (a one-launch form measured slower, profiles/r3_hga_experiment.md)
     const size_t need = (size_t)h->d.S * n * h->d.C;
-    int rc = h->blocks.grow(&h->d_pre, &h->pre_cap, need);
+    int rc = h->d_pre.grow(h->blocks, need);
     if (rc) return rc;
     rc = dss_launch_hga_frontend(d_raw, h->d_pre, h->d.S, n, h->c_raw, h->d.C, h->d_src_col, h->d_grid_of, h->n_grids,
                                      h->d_comp_cols, h->d_comp_off, (hipStream_t)hip_stream);
@@ -323,7 +318,7 @@ extern "C" int dss_hga_extract_wire_dev(dss_hga *h, const float *d_payload, int 
     DSS_HIP_CHECK(hipSetDevice(h->device));
     const int c_in = h->c_raw ? h->c_raw : h->d.C;
     const size_t need = (size_t)h->d.S * n * c_in;
-    int rc = h->blocks.grow(&h->d_wire, &h->wire_cap, need);
+    int rc = h->d_wire.grow(h->blocks, need);
     if (rc) return rc;
     rc = dss_launch_hga_wire(d_payload, h->d_wire, h->d.S, c_in, n, (hipStream_t)hip_stream);
     if (rc) return rc;
@@ -337,11 +332,11 @@ extern "C" int dss_hga_extract_raw(dss_hga *h, const double *raw, int n, double 
     if (!raw || !out || n <= 0) { dss_set_error("bad arguments"); return DSS_EINVAL; }
     DSS_HIP_CHECK(hipSetDevice(h->device));
     const size_t in_n = (size_t)h->d.S * n * h->c_raw;
-    int rc = h->blocks.grow(&h->d_raw, &h->raw_cap, in_n);
+    int rc = h->d_raw.grow(h->blocks, in_n);
     if (rc) return rc;
     const int Wmax = dss_hga_frames_for(h, n);
     const size_t out_n = (size_t)h->d.S * (Wmax > 0 ? Wmax : 1) * h->d.C;
-    rc = h->blocks.grow(&h->d_out, &h->out_cap, out_n);
+    rc = h->d_out.grow(h->blocks, out_n);
     if (rc) return rc;
     DSS_HIP_CHECK(hipMemcpy(h->d_raw, raw, in_n * sizeof(double), hipMemcpyHostToDevice));
     int W;
@@ -539,7 +534,7 @@ static int hga_trials_run(dss_hga *h, const double *d_rows, long long row_base, 
         // the front end runs once over the rows the trials span (they overlap and cover most of a recording), not per trial
         const long long span = hi - lo;
         if (span > 0x7fffffffLL / (h->c_raw > d.C ? h->c_raw : d.C)) { dss_set_error("trial list spans too many rows for one front-end launch"); return DSS_EINVAL; }
-        int rc = h->blocks.grow(&h->d_pre, &h->pre_cap, (size_t)span * d.C);
+        int rc = h->d_pre.grow(h->blocks, (size_t)span * d.C);
         if (rc) return rc;
         rc = dss_launch_hga_frontend(d_rows + (size_t)(lo - row_base) * h->c_raw, h->d_pre, 1, (int)span, h->c_raw, d.C, h->d_src_col,
                                      h->d_grid_of, h->n_grids, h->d_comp_cols, h->d_comp_off, st);
@@ -549,40 +544,35 @@ static int hga_trials_run(dss_hga *h, const double *d_rows, long long row_base, 
     }
     // descriptor table, longest trial first: the long trials' blocks start first and the short ones fill the tail
     const std::vector<int> order = trials_longest_first(n_trials, len);
-    std::vector<long long> out_row((size_t)n_trials);
-    long long total = 0;
-    for (int i = 0; i < n_trials; ++i) { out_row[i] = total; total += dss_hga_trial_frames_for(d.fs, d.wl, d.ws, len[i]); }
-    h->desc.resize((size_t)n_trials);
+    const std::vector<long long> out_row = trials_offsets(n_trials, [&](int i) { return dss_hga_trial_frames_for(d.fs, d.wl, d.ws, len[i]); });
+    const long long total = out_row[n_trials];
+    h->desc.host.resize((size_t)n_trials);
     for (int k = 0; k < n_trials; ++k) {
         const int i = order[k];
-        DssHgaTrialDesc &t = h->desc[k];
+        DssHgaTrialDesc &t = h->desc.host[k];
         t.in_row = start[i] - data_base; t.out_row = out_row[i]; t.n = len[i];
         t.W = dss_hga_trial_frames_for(d.fs, d.wl, d.ws, len[i]);
         t.zero_rows = len[i] >= d.frame_length ? 0 : d.frame_length - len[i];
         t.pad = 0;
     }
-    int rc = h->blocks.grow(&h->d_desc, &h->desc_cap, (size_t)n_trials);
+    int rc = h->desc.upload_exact(h->blocks, st);
     if (rc) return rc;
-    DSS_HIP_CHECK(hipMemcpyAsync(h->d_desc, h->desc.data(), sizeof(DssHgaTrialDesc) * (size_t)n_trials, hipMemcpyHostToDevice, st));
     const bool patched = finish && !h->patch_dst.empty();
     const bool zs = finish && d.zs_mean;
     // the patch stands between the log and the z-score (prepare_corpus.py:166-170), so with patches the z-score leaves the
     // trial kernel's epilogue and follows the patch kernel
-    rc = dss_launch_hga_trials(d, d_data, h->d_desc, n_trials, h->d_zi0[0], h->d_zi0[1], d_out, finish ? apply_log : 0,
+    rc = dss_launch_hga_trials(d, d_data, h->desc.dev, n_trials, h->d_zi0[0], h->d_zi0[1], d_out, finish ? apply_log : 0,
                                    zs && !patched, st);
     if (rc) return rc;
     if (patched) {
         // the reference patches trial by trial, and numpy sums the neighbours of a ONE-frame call differently (hga_patch_kernel)
-        h->single_rows.clear();
+        h->single_rows.host.clear();
         for (int i = 0; i < n_trials; ++i)
-            if (dss_hga_trial_frames_for(d.fs, d.wl, d.ws, len[i]) == 1) h->single_rows.push_back(out_row[i]);
-        if (!h->single_rows.empty()) {
-            rc = h->blocks.grow(&h->d_single, &h->single_cap, h->single_rows.size());
-            if (rc) return rc;
-            DSS_HIP_CHECK(hipMemcpyAsync(h->d_single, h->single_rows.data(), sizeof(long long) * h->single_rows.size(), hipMemcpyHostToDevice, st));
-        }
+            if (dss_hga_trial_frames_for(d.fs, d.wl, d.ws, len[i]) == 1) h->single_rows.host.push_back(out_row[i]);
+        rc = h->single_rows.upload_exact(h->blocks, st);
+        if (rc) return rc;
         rc = dss_launch_hga_patch(d_out, (long)total, d.C, (int)h->patch_dst.size(), h->d_patch_dst, h->d_patch_cols, h->d_patch_off,
-                                  h->d_single, (long)h->single_rows.size(), zs ? d.zs_mean : nullptr, zs ? d.zs_std : nullptr, st);
+                                  h->single_rows.dev, (long)h->single_rows.host.size(), zs ? d.zs_mean : nullptr, zs ? d.zs_std : nullptr, st);
     }
     return rc ? rc : (int)total;
 }
@@ -610,8 +600,8 @@ extern "C" int dss_hga_extract_trials(dss_hga *h, const double *rec, long long T
     long long lo, hi;
     trials_hull(n_trials, start, len, nullptr, &lo, &hi);
     // only the rows the trials span cross the bus, once, however the trials overlap
-    int rc = h->blocks.grow(&h->d_trec, &h->trec_cap, (size_t)(hi - lo) * c_in);
-    if (!rc) rc = h->blocks.grow(&h->d_tout, &h->tout_cap, (size_t)total * h->d.C);
+    int rc = h->d_trec.grow(h->blocks, (size_t)(hi - lo) * c_in);
+    if (!rc) rc = h->d_tout.grow(h->blocks, (size_t)total * h->d.C);
     if (rc) return rc;
     DSS_HIP_CHECK(hipMemcpy(h->d_trec, rec + (size_t)lo * c_in, sizeof(double) * (size_t)(hi - lo) * c_in, hipMemcpyHostToDevice));
     rc = hga_trials_run(h, h->d_trec, lo, n_trials, start, len, h->d_tout, 0, false, nullptr);

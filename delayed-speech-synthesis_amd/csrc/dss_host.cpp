@@ -1,4 +1,6 @@
-// csrc/dss_host.cpp -- what dss_host.h declares and no single operator owns: the owner of device memory, and trial lists.
+// csrc/dss_host.cpp -- what dss_host.h declares and no single operator owns: the owner of device memory, trial lists, twiddles.
+#include <math.h>
+
 #include <algorithm>
 
 #include "dss_host.h"
@@ -51,20 +53,13 @@ extern "C" int dss_trials_check(long long N, int n_trials, const long long *firs
     return DSS_OK;
 }
 
-// list positions, longest trial first (ties in list order): the long trials start first, the short ones fill the tail
-std::vector<int> trials_longest_first(int n_trials, const int *len)
+std::vector<double> dss_twiddles(int n)
 {
-    std::vector<int> order((size_t)n_trials);
-    for (int i = 0; i < n_trials; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return len[a] > len[b]; });
-    return order;
-}
-
-void trials_hull(int n_trials, const long long *first, const int *len, const int *lead, long long *lo, long long *hi)
-{
-    *lo = first[0]; *hi = first[0] + (len[0] - (lead ? lead[0] : 0));
-    for (int i = 1; i < n_trials; ++i) {
-        *lo = std::min(*lo, first[i]);
-        *hi = std::max(*hi, first[i] + (long long)(len[i] - (lead ? lead[i] : 0)));
+    std::vector<double> tw((size_t)2 * n);
+    for (int j = 0; j < n; ++j) {
+        const double a = 2.0 * M_PI * (double)j / (double)n;
+        tw[2 * j] = cos(a);
+        tw[2 * j + 1] = sin(a);
     }
+    return tw;
 }

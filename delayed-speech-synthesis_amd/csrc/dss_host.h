@@ -18,9 +18,26 @@ struct HostModel;
 DSS_LOCAL int get_model(HostModel **out_hm, const DssModelDev **out, bool acquire);
 DSS_LOCAL void release_model(HostModel *hm);
 
-// Trial lists (Part 8; the acoustic VAD's tables): list positions, longest trial first (ties in list order): the long trials start
-// first, the short ones fill the tail.
-DSS_LOCAL std::vector<int> trials_longest_first(int n_trials, const int *len);
+// Trial lists (Part 8; the tables of Parts 7, 11 and the HGA): list positions, longest trial first (ties in list order): the long
+// trials start first, the short ones fill the tail.  Lengths are int or long long (Part 11).
+template <typename L>
+static std::vector<int> trials_longest_first(int n_trials, const L *len)
+{
+    std::vector<int> order((size_t)n_trials);
+    for (int i = 0; i < n_trials; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return len[a] > len[b]; });
+    return order;
+}
+
+// Where every trial's output starts, in list order, and behind them the list's total: trial i emits count(i) frames (or rows).
+// The limits on these sums are the *_check_* functions', which run first.
+template <typename F>
+static std::vector<long long> trials_offsets(int n_trials, F count)
+{
+    std::vector<long long> off((size_t)n_trials + 1);
+    for (int i = 0; i < n_trials; ++i) off[i + 1] = off[i] + count(i);
+    return off;
+}
 
 // the chunks of a reduction over a trial list: DSS_TRIAL_CHUNK trials per launch, their lengths as kernel arguments
 template <typename F>
@@ -80,31 +97,81 @@ struct DSS_LOCAL DssDevBlocks {
         *p = (T *)d;
         return DSS_OK;
     }
-    // A device array that only grows: nothing when need <= *cap, else the old block is freed (hipFree waits for the device, so
-    // the buffer of a call still queued is not freed under it) and exactly `need` elements are allocated.  No spare bytes, not
-    // zeroed, contents not kept.
-    template <typename T>
-    int grow(T **p, size_t *cap, size_t need) { return need <= *cap ? DSS_OK : regrow(p, cap, need); }
-    // the same with dss_headroom(need) elements allocated, so that a slightly longer list next time does not allocate again
-    template <typename T>
-    int grow_headroom(T **p, size_t *cap, size_t need) { return need <= *cap ? DSS_OK : regrow(p, cap, dss_headroom(need)); }
+};
 
-    template <typename T>
-    int regrow(T **p, size_t *cap, size_t count)
+// first and one-past-last row that a trial list covers: trial i spans first[i] .. first[i] + len[i] - lead[i] (lead may be NULL)
+template <typename L>
+static void trials_hull(int n_trials, const long long *first, const L *len, const int *lead, long long *lo, long long *hi)
+{
+    *lo = first[0]; *hi = first[0] + (len[0] - (lead ? lead[0] : 0));
+    for (int i = 1; i < n_trials; ++i) {
+        *lo = std::min(*lo, first[i]);
+        *hi = std::max(*hi, first[i] + (long long)(len[i] - (lead ? lead[i] : 0)));
+    }
+}
+
+// A device array that only grows: nothing when need <= cap, else the old block is freed through the owner (hipFree waits for the
+// device, so the buffer of a call still queued is not freed under it) and exactly `need` elements are allocated, or with
+// grow_headroom dss_headroom(need), so that a slightly longer list next time does not allocate again.  No spare bytes, not zeroed,
+// contents not kept.  Reads as its pointer.
+template <typename T>
+struct DSS_LOCAL DssDevArray {
+    T *p = nullptr;
+    size_t cap = 0;
+
+    operator T *() const { return p; }
+    int grow(DssDevBlocks &blocks, size_t need) { return need <= cap ? DSS_OK : regrow(blocks, need); }
+    int grow_headroom(DssDevBlocks &blocks, size_t need) { return need <= cap ? DSS_OK : regrow(blocks, dss_headroom(need)); }
+    int regrow(DssDevBlocks &blocks, size_t count)
     {
-        release(*p);
-        *p = nullptr; *cap = 0;
-        void *d = nullptr;
-        int rc = alloc_bytes(count * sizeof(T), &d);
-        if (rc) return rc;
-        *p = (T *)d;
-        *cap = count;
+        blocks.release(p);
+        p = nullptr; cap = 0;
+        const int rc = blocks.alloc_bytes(count * sizeof(T), (void **)&p);
+        if (!rc) cap = count;
+        return rc;
+    }
+};
+
+// A table that a call fills on the host and its kernels read: upload() grows the device twin (upload_exact(): without headroom)
+// and copies host.size() elements on st, nothing for an empty table.  The source is pageable and rewritten by the next call: one
+// call per handle in flight.
+template <typename T>
+struct DSS_LOCAL DssDevTable {
+    std::vector<T> host;
+    DssDevArray<T> dev;
+
+    int upload_exact(DssDevBlocks &blocks, hipStream_t st) { return upload(blocks, st, false); }
+    int upload(DssDevBlocks &blocks, hipStream_t st, bool headroom = true)
+    {
+        const int rc = headroom ? dev.grow_headroom(blocks, host.size()) : dev.grow(blocks, host.size());
+        if (rc || host.empty()) return rc;
+        DSS_HIP_CHECK(hipMemcpyAsync(dev.p, host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice, st));
         return DSS_OK;
     }
 };
 
-// first and one-past-last row that a trial list covers: trial i spans first[i] .. first[i] + len[i] - lead[i] (lead may be NULL)
-DSS_LOCAL void trials_hull(int n_trials, const long long *first, const int *len, const int *lead, long long *lo, long long *hi);
+// cos, sin of 2 pi j / n for j = 0 .. n - 1, interleaved: the DFT tables of Parts 7, 11, 12 and 16
+DSS_LOCAL std::vector<double> dss_twiddles(int n);
+
+// The end of a *_destroy whose handle owns nothing but its blocks: queued work ends before its memory goes.
+template <typename H>
+static void dss_destroy_handle(H *h)
+{
+    if (!h) return;
+    hipSetDevice(h->device);
+    hipDeviceSynchronize();
+    h->blocks.free_all();
+    delete h;
+}
+
+// The tail of a host-buffer form: wait for the null stream, then count elements to the host.
+template <typename T>
+static int dss_fetch(T *out, const T *d, size_t count)
+{
+    DSS_HIP_CHECK(hipStreamSynchronize(nullptr));
+    DSS_HIP_CHECK(hipMemcpy(out, d, sizeof(T) * count, hipMemcpyDeviceToHost));
+    return DSS_OK;
+}
 
 // The device view of `bytes` at p, which must lie inside one block from dss_host_alloc_fine and be `align`-byte aligned;
 // DSS_EINVAL with a message otherwise (pageable or cached page-locked memory, a short block, misalignment).

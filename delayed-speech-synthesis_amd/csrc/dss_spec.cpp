@@ -18,14 +18,11 @@ struct dss_spec {
     DssDevBlocks blocks;
     double *d_win = nullptr, *d_tw = nullptr;
     // per call (one call per handle in flight)
-    std::vector<DssSpecTrial> desc;
-    std::vector<DssSpecTile> tiles;
-    DssSpecTrial *d_desc = nullptr;  size_t desc_cap = 0;
-    DssSpecTile *d_tiles = nullptr;  size_t tiles_cap = 0;
-    double *d_partial = nullptr;     size_t partial_cap = 0;     // per-trial sums of the mean spectrum
+    DssDevTable<DssSpecTrial> desc;
+    DssDevTable<DssSpecTile> tiles;
+    DssDevArray<double> d_partial;                               // per-trial sums of the mean spectrum
     // staging of the host-buffer forms
-    double *d_x = nullptr;           size_t x_cap = 0;
-    double *d_out = nullptr;         size_t out_cap = 0;
+    DssDevArray<double> d_x, d_out;
 };
 
 static int spec_frame_shape(int nperseg, int hop)
@@ -99,14 +96,7 @@ extern "C" int dss_spec_check_locked(int n_trials, const long long *length, cons
     return pre + post;
 }
 
-extern "C" void dss_spec_destroy(dss_spec *h)
-{
-    if (!h) return;
-    hipSetDevice(h->device);
-    hipDeviceSynchronize();
-    h->blocks.free_all();
-    delete h;
-}
+extern "C" void dss_spec_destroy(dss_spec *h) { dss_destroy_handle(h); }
 
 // The part of the device view that the parameters alone decide: what dss_spec_pick_geom reads.
 static void spec_shape(const dss_spec_params &p, DssSpecDev *d)
@@ -137,7 +127,7 @@ static int spec_setup(dss_spec *h, const double *window)
 {
     const dss_spec_params &p = h->p;
     const int K4 = (p.nperseg + 3) & ~3;
-    std::vector<double> win((size_t)K4, 0.0), tw((size_t)2 * p.nfft);
+    std::vector<double> win((size_t)K4, 0.0);
     double sq = 0.0;
     for (int k = 0; k < p.nperseg; ++k) {
         if (!isfinite(window[k])) { dss_set_error("spectrogram: the window holds a non-finite value"); return DSS_EINVAL; }
@@ -145,16 +135,10 @@ static int spec_setup(dss_spec *h, const double *window)
         sq += window[k] * window[k];
     }
     if (!(sq > 0.0)) { dss_set_error("spectrogram: the window is all zero"); return DSS_EINVAL; }
-    for (int j = 0; j < p.nfft; ++j) {
-        const double a = 2.0 * M_PI * (double)j / (double)p.nfft;
-        tw[2 * j] = cos(a);
-        tw[2 * j + 1] = sin(a);
-    }
-    int rc = h->blocks.alloc_bytes(win.size() * sizeof(double), (void **)&h->d_win);
-    if (!rc) rc = h->blocks.alloc_bytes(tw.size() * sizeof(double), (void **)&h->d_tw);
+    const std::vector<double> tw = dss_twiddles(p.nfft);
+    int rc = h->blocks.upload(win.data(), win.size(), &h->d_win);
+    if (!rc) rc = h->blocks.upload(tw.data(), tw.size(), &h->d_tw);
     if (rc) return rc;
-    DSS_HIP_CHECK(hipMemcpy(h->d_win, win.data(), win.size() * sizeof(double), hipMemcpyHostToDevice));
-    DSS_HIP_CHECK(hipMemcpy(h->d_tw, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice));
     DssSpecDev &d = h->d;
     spec_shape(p, &d);
     const double scale = 1.0 / (p.fs * sq);          // scipy: scale = 1.0 / (fs * (win * win).sum())
@@ -182,14 +166,6 @@ static int spec_check_layout(const dss_spec *h, int ld, int C)
     return DSS_OK;
 }
 
-static int spec_upload_desc(dss_spec *h, hipStream_t st)
-{
-    int rc = h->blocks.grow_headroom(&h->d_desc, &h->desc_cap, h->desc.size());
-    if (rc) return rc;
-    DSS_HIP_CHECK(hipMemcpyAsync(h->d_desc, h->desc.data(), sizeof(DssSpecTrial) * h->desc.size(), hipMemcpyHostToDevice, st));
-    return DSS_OK;
-}
-
 // The three operations on device-resident signals; d_x holds rows row_base .. of the caller's array.
 static long long spec_run_trials(dss_spec *h, const double *d_x, long long row_base, int ld, int C, int n_trials, const long long *first,
                                  const long long *length, double *d_out, hipStream_t st)
@@ -198,27 +174,22 @@ static long long spec_run_trials(dss_spec *h, const double *d_x, long long row_b
     DssSpecGeom g;
     if (!dss_spec_pick_geom(h->d, C, SPEC_KIND_TRIALS, &g)) { dss_set_error("spectrogram: the frame shape does not fit the kernel"); return DSS_EINVAL; }
     // descriptor table, longest trial first: the long trials' tiles start first and the short ones fill the tail
-    std::vector<int> order((size_t)n_trials);
-    for (int i = 0; i < n_trials; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return length[a] > length[b]; });
-    std::vector<long long> out_frame((size_t)n_trials);
-    long long total = 0;
-    for (int i = 0; i < n_trials; ++i) { out_frame[i] = total; total += (length[i] - N) / hop + 1; }
-    h->desc.resize((size_t)n_trials);
-    h->tiles.clear();
+    const std::vector<int> order = trials_longest_first(n_trials, length);
+    const std::vector<long long> out_frame = trials_offsets(n_trials, [&](int i) { return (length[i] - N) / hop + 1; });
+    std::vector<DssSpecTile> &tiles = h->tiles.host;
+    h->desc.host.resize((size_t)n_trials);
+    tiles.clear();
     for (int k = 0; k < n_trials; ++k) {
         const int i = order[k];
-        DssSpecTrial &t = h->desc[k];
+        DssSpecTrial &t = h->desc.host[k];
         t.first = first[i] - row_base; t.n = length[i]; t.out = out_frame[i]; t.W = (int)((length[i] - N) / hop + 1); t.frame0 = 0;
-        for (long long f0 = 0; f0 < t.W; f0 += g.F) h->tiles.push_back(DssSpecTile{k, (int)f0});
+        for (long long f0 = 0; f0 < t.W; f0 += g.F) tiles.push_back(DssSpecTile{k, (int)f0});
     }
-    if (h->tiles.size() > 0x7fffffffULL) { dss_set_error("spectrogram: too many tiles for one launch"); return DSS_EINVAL; }
-    int rc = spec_upload_desc(h, st);
-    if (!rc) rc = h->blocks.grow_headroom(&h->d_tiles, &h->tiles_cap, h->tiles.size());
-    if (rc) return rc;
-    DSS_HIP_CHECK(hipMemcpyAsync(h->d_tiles, h->tiles.data(), sizeof(DssSpecTile) * h->tiles.size(), hipMemcpyHostToDevice, st));
-    rc = dss_launch_spec_trials(h->d, g, d_x, ld, C, h->d_desc, h->d_tiles, (int)h->tiles.size(), d_out, st);
-    return rc ? rc : total;
+    if (tiles.size() > 0x7fffffffULL) { dss_set_error("spectrogram: too many tiles for one launch"); return DSS_EINVAL; }
+    int rc = h->desc.upload(h->blocks, st);
+    if (!rc) rc = h->tiles.upload(h->blocks, st);
+    if (!rc) rc = dss_launch_spec_trials(h->d, g, d_x, ld, C, h->desc.dev, h->tiles.dev, (int)tiles.size(), d_out, st);
+    return rc ? rc : out_frame[n_trials];
 }
 
 static int spec_run_locked(dss_spec *h, const double *d_x, long long row_base, int ld, int C, int n_trials, const long long *first,
@@ -226,14 +197,14 @@ static int spec_run_locked(dss_spec *h, const double *d_x, long long row_base, i
 {
     DssSpecGeom g;
     if (!dss_spec_pick_geom(h->d, C, SPEC_KIND_LOCKED, &g)) { dss_set_error("spectrogram: the frame shape does not fit the kernel"); return DSS_EINVAL; }
-    h->desc.resize((size_t)n_trials);
+    h->desc.host.resize((size_t)n_trials);
     for (int i = 0; i < n_trials; ++i) {
-        DssSpecTrial &t = h->desc[i];
+        DssSpecTrial &t = h->desc.host[i];
         t.first = first[i] - row_base; t.n = length[i]; t.out = i; t.W = (int)((length[i] - h->p.nperseg) / h->p.hop + 1);
         t.frame0 = onset[i] - pre;
     }
-    int rc = spec_upload_desc(h, st);
-    if (!rc) rc = dss_launch_spec_locked(h->d, g, d_x, ld, C, h->d_desc, n_trials, pre + post, d_out, st);
+    int rc = h->desc.upload(h->blocks, st);
+    if (!rc) rc = dss_launch_spec_locked(h->d, g, d_x, ld, C, h->desc.dev, n_trials, pre + post, d_out, st);
     return rc ? rc : pre + post;
 }
 
@@ -243,43 +214,37 @@ static int spec_run_mean(dss_spec *h, const double *d_x, long long row_base, int
     DssSpecGeom g;
     if (!dss_spec_pick_geom(h->d, C, SPEC_KIND_MEAN, &g)) { dss_set_error("spectrogram: the frame shape does not fit the kernel"); return DSS_EINVAL; }
     // the grid takes the longest trial first; every trial's sum lands at its place in the caller's list
-    std::vector<int> order((size_t)n_trials);
-    for (int i = 0; i < n_trials; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return length[a] > length[b]; });
-    h->desc.resize((size_t)n_trials);
+    const std::vector<int> order = trials_longest_first(n_trials, length);
+    h->desc.host.resize((size_t)n_trials);
     for (int k = 0; k < n_trials; ++k) {
         const int i = order[k];
-        DssSpecTrial &t = h->desc[k];
+        DssSpecTrial &t = h->desc.host[k];
         t.first = first[i] - row_base; t.n = length[i]; t.out = i; t.W = (int)((length[i] - h->p.nperseg) / h->p.hop + 1); t.frame0 = 0;
     }
-    int rc = spec_upload_desc(h, st);
-    if (!rc) rc = h->blocks.grow_headroom(&h->d_partial, &h->partial_cap, (size_t)n_trials * C * h->d.bins);
-    if (!rc) rc = dss_launch_spec_mean(h->d, g, d_x, ld, C, h->d_desc, n_trials, total, h->d_partial, d_out, st);
+    int rc = h->desc.upload(h->blocks, st);
+    if (!rc) rc = h->d_partial.grow_headroom(h->blocks, (size_t)n_trials * C * h->d.bins);
+    if (!rc) rc = dss_launch_spec_mean(h->d, g, d_x, ld, C, h->desc.dev, n_trials, total, h->d_partial, d_out, st);
     return rc;
 }
 
-// Host-buffer forms: only the rows the trials span cross the bus, once, however the trials overlap.
-static int spec_stage_rows(dss_spec *h, const double *x, int ld, int C, int n_trials, const long long *first, const long long *length,
-                           long long *row_base)
+// Host-buffer forms: only the rows the trials span cross the bus, once, however the trials overlap; run(row_base) is the
+// operation on the staged rows, into h->d_out, and its result the form's.
+template <typename Run>
+static long long spec_host_form(dss_spec *h, const double *x, int ld, int C, int n_trials, const long long *first, const long long *length,
+                                double *out, size_t count, Run run)
 {
-    long long lo = first[0], hi = first[0] + length[0];
-    for (int i = 1; i < n_trials; ++i) {
-        lo = std::min(lo, first[i]);
-        hi = std::max(hi, first[i] + length[i]);
-    }
-    int rc = h->blocks.grow_headroom(&h->d_x, &h->x_cap, (size_t)(hi - lo) * ld + 1);
+    long long lo, hi;
+    trials_hull(n_trials, first, length, nullptr, &lo, &hi);
+    int rc = h->d_x.grow_headroom(h->blocks, (size_t)(hi - lo) * ld + 1);
     if (rc) return rc;
     // the last row ends behind its C channels: the caller's array may be a view that ends there
     if (hi > lo) DSS_HIP_CHECK(hipMemcpy(h->d_x, x + lo * ld, sizeof(double) * ((size_t)(hi - lo - 1) * ld + C), hipMemcpyHostToDevice));
-    *row_base = lo;
-    return DSS_OK;
-}
-
-static int spec_fetch(dss_spec *h, double *out, size_t count)
-{
-    DSS_HIP_CHECK(hipStreamSynchronize(nullptr));
-    DSS_HIP_CHECK(hipMemcpy(out, h->d_out, sizeof(double) * count, hipMemcpyDeviceToHost));
-    return DSS_OK;
+    rc = h->d_out.grow_headroom(h->blocks, count);
+    if (rc) return rc;
+    const long long got = run(lo);
+    if (got < 0) return got;
+    rc = dss_fetch(out, h->d_out.p, count);
+    return rc ? rc : got;
 }
 
 extern "C" long long dss_spec_trials_dev(dss_spec *h, const double *d_x, long long n_rows, int ld, int C, int n_trials,
@@ -301,15 +266,9 @@ extern "C" long long dss_spec_trials(dss_spec *h, const double *x, long long n_r
     if (total <= 0) return total;
     if (!x || !out) { dss_set_error("bad arguments"); return DSS_EINVAL; }
     DSS_HIP_CHECK(hipSetDevice(h->device));
-    long long base = 0;
-    const size_t count = (size_t)total * C * h->d.bins;
-    int rc = spec_stage_rows(h, x, ld, C, n_trials, first, length, &base);
-    if (!rc) rc = h->blocks.grow_headroom(&h->d_out, &h->out_cap, count);
-    if (rc) return rc;
-    const long long got = spec_run_trials(h, h->d_x, base, ld, C, n_trials, first, length, h->d_out, nullptr);
-    if (got < 0) return got;
-    rc = spec_fetch(h, out, count);
-    return rc ? rc : total;
+    return spec_host_form(h, x, ld, C, n_trials, first, length, out, (size_t)total * C * h->d.bins, [&](long long base) {
+        return spec_run_trials(h, h->d_x, base, ld, C, n_trials, first, length, h->d_out, nullptr);
+    });
 }
 
 extern "C" int dss_spec_locked_dev(dss_spec *h, const double *d_x, long long n_rows, int ld, int C, int n_trials, const long long *first,
@@ -333,14 +292,9 @@ extern "C" int dss_spec_locked(dss_spec *h, const double *x, long long n_rows, i
     if (J < 0) return J;
     if (!x || !out) { dss_set_error("bad arguments"); return DSS_EINVAL; }
     DSS_HIP_CHECK(hipSetDevice(h->device));
-    long long base = 0;
-    const size_t count = (size_t)C * h->d.bins * J;
-    int rc = spec_stage_rows(h, x, ld, C, n_trials, first, length, &base);
-    if (!rc) rc = h->blocks.grow_headroom(&h->d_out, &h->out_cap, count);
-    if (!rc) rc = spec_run_locked(h, h->d_x, base, ld, C, n_trials, first, length, onset, pre, post, h->d_out, nullptr);
-    if (rc < 0) return rc;
-    rc = spec_fetch(h, out, count);
-    return rc ? rc : J;
+    return (int)spec_host_form(h, x, ld, C, n_trials, first, length, out, (size_t)C * h->d.bins * J, [&](long long base) {
+        return spec_run_locked(h, h->d_x, base, ld, C, n_trials, first, length, onset, pre, post, h->d_out, nullptr);
+    });
 }
 
 extern "C" int dss_spec_mean_dev(dss_spec *h, const double *d_x, long long n_rows, int ld, int C, int n_trials, const long long *first,
@@ -364,11 +318,7 @@ extern "C" int dss_spec_mean(dss_spec *h, const double *x, long long n_rows, int
     if (total == 0) { dss_set_error("mean spectrum: no trials"); return DSS_EINVAL; }
     if (!x || !out) { dss_set_error("bad arguments"); return DSS_EINVAL; }
     DSS_HIP_CHECK(hipSetDevice(h->device));
-    long long base = 0;
-    const size_t count = (size_t)C * h->d.bins;
-    int rc = spec_stage_rows(h, x, ld, C, n_trials, first, length, &base);
-    if (!rc) rc = h->blocks.grow_headroom(&h->d_out, &h->out_cap, count);
-    if (!rc) rc = spec_run_mean(h, h->d_x, base, ld, C, n_trials, first, length, total, h->d_out, nullptr);
-    if (rc) return rc;
-    return spec_fetch(h, out, count);
+    return (int)spec_host_form(h, x, ld, C, n_trials, first, length, out, (size_t)C * h->d.bins, [&](long long base) {
+        return spec_run_mean(h, h->d_x, base, ld, C, n_trials, first, length, total, h->d_out, nullptr);
+    });
 }

@@ -17,8 +17,7 @@ struct dss_vad {
     bool loaded = false;
     // trial lists (dss_vad_forward_trials_dev): the descriptor table of the last call, pinned staging and device
     DssPinnedStage tstage;
-    DssVadTrialDesc *d_tdesc = nullptr;
-    size_t tdesc_cap = 0;
+    DssDevArray<DssVadTrialDesc> d_tdesc;
 };
 
 int dss_vad_device_weights(dss_vad *v, int *device, int *n_inputs, int *hidden_units, float *w[6])
@@ -160,14 +159,12 @@ extern "C" int dss_vad_forward_trials_dev(dss_vad *v, const void *d_frames, int 
     if (!n_trials) return DSS_OK;
     DSS_HIP_CHECK(hipSetDevice(v->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    std::vector<long long> out_row((size_t)n_trials);
-    long long row = 0;
-    for (int i = 0; i < n_trials; ++i) { out_row[i] = row; row += len[i]; }
+    const std::vector<long long> out_row = trials_offsets(n_trials, [&](int i) { return len[i]; });
     const std::vector<int> order = trials_longest_first(n_trials, len);
     DssVadTrialDesc *desc = (DssVadTrialDesc *)v->tstage.acquire(sizeof(DssVadTrialDesc) * (size_t)n_trials);
     if (!desc) { dss_set_error("pinned staging for the trial table failed"); return DSS_ENOMEM; }
     for (int k = 0; k < n_trials; ++k) { const int i = order[k]; desc[k] = DssVadTrialDesc{first[i], out_row[i], len[i], 0}; }
-    rc = v->blocks.grow(&v->d_tdesc, &v->tdesc_cap, (size_t)n_trials);
+    rc = v->d_tdesc.grow(v->blocks, (size_t)n_trials);
     if (rc) return rc;
     DSS_HIP_CHECK(hipMemcpyAsync(v->d_tdesc, desc, sizeof(DssVadTrialDesc) * (size_t)n_trials, hipMemcpyHostToDevice, st));
     if ((rc = v->tstage.commit(st))) return rc;
