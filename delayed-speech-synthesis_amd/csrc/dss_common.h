@@ -194,7 +194,8 @@ struct DssVadDev {
 int dss_launch_vad(const DssVadDev &v, const void *d_frames, int frames_f64, int W, int *d_labels, float *d_logits, hipStream_t s);
 // trial lists (Part 8): one table entry and one workgroup per trial, in table order: rows in_row .. in_row + len of the (N, C)
 // frames go to rows out_row .. of the concatenated outputs; v.h / v.c are neither read nor written
-struct DssVadTrialDesc { long long in_row, out_row; int len, pad; };
+// (model: the member that runs the trial in the group form below; the single-model path writes 0)
+struct DssVadTrialDesc { long long in_row, out_row; int len, model; };
 int dss_launch_vad_trials(const DssVadDev &v, const void *d_frames, int frames_f64, const DssVadTrialDesc *d_desc, int n_trials, int *d_labels,
                           float *d_logits, hipStream_t s);
 // up to DSS_TRIAL_CHUNK consecutive trials of a concatenated (sum len, ...) array, handed to a reduction kernel by value: trial
@@ -246,6 +247,11 @@ struct DssVadGroupTrial {         // one model's entry of a step's trial table (
 // zeroed first, by one launch.
 int dss_launch_vad_train_group(const DssVadTrainDev *d_models, const DssVadGroupTrial *d_trials, int M, int C, int H, int n_windows,
                                int window, int reset, int frames_f64, hipStream_t s);
+// a trial list over the members of a group (Part 17; vad_lstm.hip): as dss_launch_vad_trials, but trial k runs on the packed
+// copies of d_models[d_desc[k].model] (the members' current weights: what their trainers' forward halves read); nothing of a
+// member is written
+int dss_launch_vad_trials_group(const DssVadTrainDev *d_models, int C, int H, const void *d_frames, int frames_f64,
+                                const DssVadTrialDesc *d_desc, int n_trials, int *d_labels, float *d_logits, hipStream_t s);
 
 // ---- bidirectional recurrent decoder (bilstm_decoder.hip) ----------------------------------------------------
 struct DssDecDev {
@@ -304,6 +310,23 @@ struct DssDecGroupTrial {         // one model's entry of a step's trial table (
 // one step of M trainers: d_models[M] and d_trials[M] are device tables; max_T is the longest T of the step (>= 1)
 int dss_launch_dec_train_group(const DssDecTrainDev *d_models, const DssDecGroupTrial *d_trials, int M, int C, int H, int O, int max_T,
                                int frames_f64, hipStream_t s);
+// A trial list over the members of a group (Part 17; bilstm_decoder.hip), one set of three launches.  Stream slot s is one trial:
+// frames in_row .. in_row + len of the (N, C) array, layer outputs at rows buf_row .. of the concatenated (rows, 2H) buffers
+// mid / top, features at rows out_row .. of d_feats.  A layer workgroup runs the n <= W streams slot0 .. of ONE model (both
+// directions: blockIdx.y); a regressor block takes the n <= DEC_RROWS buffer rows row0 .. of one model, whose first row lies in
+// stream slot `slot` (the rows of a model's streams follow each other in slot order).  Device tables, read in table order.
+#define DSS_DEC_RROWS 8           // rows of `top` per regressor block (bilstm_decoder.hip)
+struct DssDecGroupStream { long long in_row, out_row, buf_row; int len, model; };
+struct DssDecGroupWg { int model, slot0, n, pad; };
+struct DssDecGroupBlock { long long row0; int model, slot, n, pad; };
+static_assert(sizeof(DssDecGroupStream) == 32 && sizeof(DssDecGroupWg) == 16 && sizeof(DssDecGroupBlock) == 24,
+              "the tables are copied to the device as they stand");
+int dss_launch_decoder_trials_group(const DssDecTrainDev *d_models, int C, int H, int O, const void *d_frames, int frames_f64, int W,
+                                    const DssDecGroupStream *d_streams, const DssDecGroupWg *d_wgs, int n_wgs,
+                                    const DssDecGroupBlock *d_blocks, int n_blocks, float *d_mid, float *d_top, float *d_feats,
+                                    hipStream_t s);
+// the streams per layer workgroup that both trial-list forms choose for a list of S trials (dss_launch_decoder's rule)
+static inline int dss_dec_streams_per_wg(int S) { return 2 * S <= 256 ? 1 : (S <= 256 ? 2 : 4); }
 
 struct DssHgaDev {
     int S, C, fs, nsec;

@@ -1,7 +1,8 @@
 // csrc/dss_dec_group.cpp -- host side of Part 13 of include/dss_hip.h: several decoders of equal sizes trained side by side, one
 // set of seven launches per step (the group kernels of csrc/dec_train.hip).  A group owns M trainers of Part 10 -- so loading,
 // reading and publishing a member are Part 10's own functions on that member -- a device table of their M descriptors, written
-// once, and a ring of trial tables (DssGroupTables, dss_host.h).
+// once, and a ring of trial tables (DssGroupTables, dss_host.h).  At the end, the decoder half of Part 17: the members over one
+// trial list (the group kernels of csrc/bilstm_decoder.hip).
 #include <vector>
 
 #include "dss_host.h"
@@ -11,6 +12,12 @@ struct dss_dec_group {
     int M = 0, C = 0, H = 0, O = 0, Tmax = 0;
     std::vector<dss_dec_trainer *> tr;
     DssGroupTables<DssDecTrainDev, DssDecGroupTrial> tables;
+    // trial lists (dss_dec_group_forward_trials_dev): the stream, workgroup and block tables of the last call, pinned staging and
+    // device (8-byte words), and the two concatenated layer buffers, (rows, 2H) floats each, grown on demand
+    DssDevBlocks blocks;
+    DssPinnedStage tstage;
+    DssDevArray<long long> d_ttab;
+    DssDevArray<float> d_mid, d_top;
 };
 
 extern "C" int dss_dec_group_check(int n_models, int n_inputs, int hidden_units, int n_outputs, int max_frames)
@@ -30,6 +37,8 @@ extern "C" void dss_dec_group_destroy(dss_dec_group *g)
     hipSetDevice(g->device);
     hipDeviceSynchronize();
     g->tables.destroy();
+    g->blocks.free_all();
+    g->tstage.destroy();
     for (dss_dec_trainer *t : g->tr) dss_dec_trainer_destroy(t);
     delete g;
 }
@@ -134,4 +143,111 @@ extern "C" int dss_dec_group_step_dev(dss_dec_group *g, const dss_dec_group_tria
     // behind the launches, not only the copy: the device table of the slot is read until the step's last launch has run
     int rc2 = g->tables.commit_after_launch(st);
     return rc ? rc : rc2;
+}
+
+// Part 17: the members' decoders over a trial list, each trial on the member it names.  The list is cut, at trial borders and in
+// list order, into sets of launches whose frames fit max_rows rows of the two layer buffers.  Within a set every model's trials
+// are sorted longest first (ties in list order) and take consecutive stream slots and consecutive buffer rows, so a model's rows
+// are one range: its streams are dealt to layer workgroups of W (the model's remainder gets a partly filled one), its rows to
+// regressor blocks of DSS_DEC_RROWS.  The set's workgroups are then sorted by their longest stream, which is their first, across
+// the models: the long chains are dispatched first.  All sets' tables travel in one copy.
+#define DSS_DEC_GROUP_ROWS (1LL << 19)        // default max_rows: 2 x 400 MB of layer outputs at H = 100
+
+extern "C" int dss_dec_group_forward_trials_dev(dss_dec_group *g, const void *d_frames, int frames_are_f64, long long N, int n_trials,
+                                                const long long *first, const int *len, const int *model, long long max_rows, float *d_feats,
+                                                void *hip_stream)
+{
+    const char *who = "dss_dec_group_forward_trials_dev";
+    // (an empty list uses neither the frames nor the outputs: empty device arrays may have no address)
+    if (!g || (n_trials > 0 && (!d_frames || !d_feats || !model))) { dss_set_error("%s: null argument", who); return DSS_EINVAL; }
+    if (max_rows < 0) { dss_set_error("%s: max_rows = %lld: must be 0 (the default) or more", who, max_rows); return DSS_EINVAL; }
+    long long total = 0;
+    int rc = dss_trials_check(N, n_trials, first, len, &total);
+    if (rc) return rc;
+    if (!max_rows) max_rows = DSS_DEC_GROUP_ROWS;
+    std::vector<char> used((size_t)g->M, 0);
+    for (int i = 0; i < n_trials; ++i) {
+        if (model[i] < 0 || model[i] >= g->M) { dss_set_error("%s: trial %d names model %d of a group of %d", who, i, model[i], g->M); return DSS_EINVAL; }
+        if (first[i] > 0x7fffffffLL) { dss_set_error("%s: trial %d starts behind row 2^31 - 1", who, i); return DSS_EINVAL; }
+        if (len[i] > max_rows) { dss_set_error("%s: trial %d has %d frames, max_rows is %lld", who, i, len[i], max_rows); return DSS_EINVAL; }
+        used[(size_t)model[i]] = 1;
+    }
+    for (int m = 0; m < g->M; ++m) {
+        if (!used[(size_t)m]) continue;
+        DssDecTrainDev d;
+        int device = 0, loaded = 0;
+        dss_dec_trainer_view(g->tr[(size_t)m], &d, &device, &loaded);
+        if (!loaded) { dss_set_error("%s: model %d has no parameters loaded (dss_dec_group_load)", who, m); return DSS_EINVAL; }
+    }
+    if (!n_trials) return DSS_OK;
+    const int W = dss_dec_streams_per_wg(n_trials);
+    const std::vector<long long> out_row = trials_offsets(n_trials, [&](int i) { return len[i]; });
+    struct Set { size_t w0, w1, b0, b1; };
+    std::vector<Set> sets;
+    std::vector<DssDecGroupStream> streams;
+    std::vector<DssDecGroupWg> wgs;
+    std::vector<DssDecGroupBlock> rblocks;
+    streams.reserve((size_t)n_trials);
+    long long need_rows = 0;
+    for (int i0 = 0; i0 < n_trials;) {
+        int i1 = i0;
+        long long rows = 0;
+        while (i1 < n_trials && rows + len[i1] <= max_rows) rows += len[i1++];
+        std::vector<int> idx((size_t)(i1 - i0));
+        for (int i = i0; i < i1; ++i) idx[(size_t)(i - i0)] = i;
+        std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return model[a] != model[b] ? model[a] < model[b] : len[a] > len[b]; });
+        Set set{wgs.size(), 0, rblocks.size(), 0};
+        long long buf = 0;
+        for (size_t a = 0; a < idx.size();) {
+            const int m = model[idx[a]];
+            size_t b = a;
+            while (b < idx.size() && model[idx[b]] == m) ++b;
+            const long long row0 = buf;
+            const size_t slot0 = streams.size();
+            for (size_t k = a; k < b; ++k) {
+                const int i = idx[k];
+                streams.push_back(DssDecGroupStream{first[i], out_row[i], buf, len[i], m});
+                buf += len[i];
+            }
+            for (size_t k = a; k < b; k += (size_t)W)
+                wgs.push_back(DssDecGroupWg{m, (int)(slot0 + (k - a)), (int)std::min((size_t)W, b - k), 0});
+            size_t s = slot0;
+            for (long long r = row0; r < buf; r += DSS_DEC_RROWS) {
+                while (r >= streams[s].buf_row + streams[s].len) ++s;
+                rblocks.push_back(DssDecGroupBlock{r, m, (int)s, (int)std::min((long long)DSS_DEC_RROWS, buf - r), 0});
+            }
+            a = b;
+        }
+        std::stable_sort(wgs.begin() + (long)set.w0, wgs.end(),
+                         [&](const DssDecGroupWg &a, const DssDecGroupWg &b) { return streams[(size_t)a.slot0].len > streams[(size_t)b.slot0].len; });
+        set.w1 = wgs.size(); set.b1 = rblocks.size();
+        sets.push_back(set);
+        need_rows = std::max(need_rows, rows);
+        i0 = i1;
+    }
+    DSS_HIP_CHECK(hipSetDevice(g->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const size_t sb = streams.size() * sizeof(DssDecGroupStream), wb = wgs.size() * sizeof(DssDecGroupWg), bb = rblocks.size() * sizeof(DssDecGroupBlock);
+    char *stage = (char *)g->tstage.acquire(sb + wb + bb);
+    if (!stage) { dss_set_error("pinned staging for the trial tables failed"); return DSS_ENOMEM; }
+    memcpy(stage, streams.data(), sb);
+    memcpy(stage + sb, wgs.data(), wb);
+    memcpy(stage + sb + wb, rblocks.data(), bb);
+    const size_t lay = (size_t)need_rows * 2 * (size_t)g->H;
+    if ((rc = g->d_ttab.grow(g->blocks, (sb + wb + bb) / sizeof(long long))) || (rc = g->d_mid.grow(g->blocks, lay)) || (rc = g->d_top.grow(g->blocks, lay))) {
+        dss_set_error("%s: device allocation failed for the tables or for two layer buffers of %lld rows", who, need_rows);
+        return rc;
+    }
+    char *d_tab = (char *)(long long *)g->d_ttab;
+    DSS_HIP_CHECK(hipMemcpyAsync(d_tab, stage, sb + wb + bb, hipMemcpyHostToDevice, st));
+    if ((rc = g->tstage.commit(st))) return rc;
+    const DssDecGroupStream *d_streams = (const DssDecGroupStream *)d_tab;
+    const DssDecGroupWg *d_wgs = (const DssDecGroupWg *)(d_tab + sb);
+    const DssDecGroupBlock *d_blocks = (const DssDecGroupBlock *)(d_tab + sb + wb);
+    for (const Set &s : sets) {
+        rc = dss_launch_decoder_trials_group(g->tables.d_models, g->C, g->H, g->O, d_frames, frames_are_f64, W, d_streams, d_wgs + s.w0,
+                                             (int)(s.w1 - s.w0), d_blocks + s.b0, (int)(s.b1 - s.b0), g->d_mid, g->d_top, d_feats, st);
+        if (rc) return rc;
+    }
+    return DSS_OK;
 }

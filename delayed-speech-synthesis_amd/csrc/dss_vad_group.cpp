@@ -1,7 +1,8 @@
 // csrc/dss_vad_group.cpp -- host side of Part 15 of include/dss_hip.h: several detectors of equal sizes trained side by side, one
 // pair of launches per window (the group kernels of csrc/vad_train.hip).  A group owns M trainers of Part 9 -- so loading,
 // reading, state access and publishing a member are Part 9's own functions on that member -- a device table of their M
-// descriptors, written once, and a ring of trial tables (DssGroupTables, dss_host.h).
+// descriptors, written once, and a ring of trial tables (DssGroupTables, dss_host.h).  At the end, the detector half of Part 17:
+// the members over one trial list (the group kernel of csrc/vad_lstm.hip).
 #include <vector>
 
 #include "dss_host.h"
@@ -11,6 +12,10 @@ struct dss_vad_group {
     int M = 0, C = 0, H = 0, Tmax = 0;
     std::vector<dss_vad_trainer *> tr;
     DssGroupTables<DssVadTrainDev, DssVadGroupTrial> tables;
+    // trial lists (dss_vad_group_forward_trials_dev): the descriptor table of the last call, pinned staging and device
+    DssDevBlocks blocks;
+    DssPinnedStage tstage;
+    DssDevArray<DssVadTrialDesc> d_tdesc;
 };
 
 extern "C" int dss_vad_group_check(int n_models, int n_inputs, int hidden_units, int max_window)
@@ -30,6 +35,8 @@ extern "C" void dss_vad_group_destroy(dss_vad_group *g)
     hipSetDevice(g->device);
     hipDeviceSynchronize();
     g->tables.destroy();
+    g->blocks.free_all();
+    g->tstage.destroy();
     for (dss_vad_trainer *t : g->tr) dss_vad_trainer_destroy(t);
     delete g;
 }
@@ -157,4 +164,46 @@ extern "C" int dss_vad_group_trial_dev(dss_vad_group *g, const dss_vad_group_tri
         return DSS_EINVAL;
     }
     return group_step(g, trials, window, frames_are_f64, hip_stream, "dss_vad_group_trial_dev");
+}
+
+// Part 17: the members' detectors over a trial list, each trial on the member it names, in one launch.  The checks come first and
+// need no device beyond the one the group was created on; the table is Part 8's, sorted longest first across all models, with
+// the member in the entry.
+extern "C" int dss_vad_group_forward_trials_dev(dss_vad_group *g, const void *d_frames, int frames_are_f64, long long N, int n_trials,
+                                                const long long *first, const int *len, const int *model, int *d_labels, float *d_logits,
+                                                void *hip_stream)
+{
+    // (an empty list uses neither the frames nor the outputs: empty device arrays may have no address)
+    if (!g || (n_trials > 0 && (!d_frames || !d_labels || !model))) { dss_set_error("dss_vad_group_forward_trials_dev: null argument"); return DSS_EINVAL; }
+    long long total = 0;
+    int rc = dss_trials_check(N, n_trials, first, len, &total);
+    if (rc) return rc;
+    std::vector<char> used((size_t)g->M, 0);
+    for (int i = 0; i < n_trials; ++i) {
+        if (model[i] < 0 || model[i] >= g->M) {
+            dss_set_error("dss_vad_group_forward_trials_dev: trial %d names model %d of a group of %d", i, model[i], g->M);
+            return DSS_EINVAL;
+        }
+        used[(size_t)model[i]] = 1;
+    }
+    for (int m = 0; m < g->M; ++m) {
+        if (!used[(size_t)m]) continue;
+        DssVadTrainDev d;
+        int device = 0, loaded = 0;
+        dss_vad_trainer_view(g->tr[(size_t)m], &d, &device, &loaded);
+        if (!loaded) { dss_set_error("dss_vad_group_forward_trials_dev: model %d has no parameters loaded (dss_vad_group_load)", m); return DSS_EINVAL; }
+    }
+    if (!n_trials) return DSS_OK;
+    DSS_HIP_CHECK(hipSetDevice(g->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const std::vector<long long> out_row = trials_offsets(n_trials, [&](int i) { return len[i]; });
+    const std::vector<int> order = trials_longest_first(n_trials, len);
+    DssVadTrialDesc *desc = (DssVadTrialDesc *)g->tstage.acquire(sizeof(DssVadTrialDesc) * (size_t)n_trials);
+    if (!desc) { dss_set_error("pinned staging for the trial table failed"); return DSS_ENOMEM; }
+    for (int k = 0; k < n_trials; ++k) { const int i = order[k]; desc[k] = DssVadTrialDesc{first[i], out_row[i], len[i], model[i]}; }
+    rc = g->d_tdesc.grow(g->blocks, (size_t)n_trials);
+    if (rc) return rc;
+    DSS_HIP_CHECK(hipMemcpyAsync(g->d_tdesc, desc, sizeof(DssVadTrialDesc) * (size_t)n_trials, hipMemcpyHostToDevice, st));
+    if ((rc = g->tstage.commit(st))) return rc;
+    return dss_launch_vad_trials_group(g->tables.d_models, g->C, g->H, d_frames, frames_are_f64, g->d_tdesc, n_trials, d_labels, d_logits, st);
 }

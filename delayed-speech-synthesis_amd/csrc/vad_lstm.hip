@@ -181,6 +181,42 @@ int dss_launch_vad_trials(const DssVadDev &v, const void *d_frames, int frames_f
     return DSS_OK;
 }
 
+// ---- a trial list over the members of a group (dss_vad_group_forward_trials_dev; Part 17) --------------------------------------
+// The same launch with a model per trial: the workgroup takes its entry of the trial table, then the detector of the member the
+// entry names from the group's device table of trainer descriptors (DssVadTrainDev::v: the packed copies the trainer's forward
+// half reads, so the weights are the member's current ones, in stream order behind its steps), and runs the body vad_trials_kernel
+// runs -- a trial's bits are those of a VadLstmGPU holding that member's weights.  Both tables are constant while the launch
+// runs (dss_cp: scalar loads, as for a kernel argument) and the weight pointers read from them are global pointers (dss_gp), so
+// the weights' addresses stay in scalar registers.  v.h / v.c, the member's carried state, are not passed on: CARRY is off.
+template <typename FrameT>
+__global__ void __launch_bounds__(VAD_THREADS, 5)
+vad_trials_group_kernel(const DssVadTrainDev *__restrict__ models, const FrameT *__restrict__ frames, const DssVadTrialDesc *__restrict__ desc,
+                        int *__restrict__ labels, float *__restrict__ logits)
+{
+    const DssVadTrialDesc &d = *dss_cp(desc + blockIdx.x);
+    const DssVadDev &t = dss_cp(models + d.model)->v;
+    DssVadDev v;
+    v.S = 1; v.C = t.C; v.H = t.H;
+    v.wT0 = dss_gp(t.wT0); v.b0 = dss_gp(t.b0); v.wT1 = dss_gp(t.wT1); v.b1 = dss_gp(t.b1); v.wc = dss_gp(t.wc); v.bc = dss_gp(t.bc);
+    v.h = nullptr; v.c = nullptr;
+    vad_forward_body<FrameT, 1, false>(v, frames + (size_t)d.in_row * v.C, d.len, labels + d.out_row,
+                                       logits ? logits + (size_t)d.out_row * 2 : nullptr, 0, 1);
+}
+
+int dss_launch_vad_trials_group(const DssVadTrainDev *d_models, int C, int H, const void *d_frames, int frames_f64,
+                                const DssVadTrialDesc *desc, int n_trials, int *d_labels, float *d_logits, hipStream_t st)
+{
+    if (H < 1 || H > VAD_MAXH || 4 * H > VAD_THREADS || C < 1 || C > VAD_MAXC) {
+        dss_set_error("VAD kernel: hidden size %d / %d inputs out of range (<= %d / <= %d)", H, C, VAD_MAXH, VAD_MAXC);
+        return DSS_EINVAL;
+    }
+    if (n_trials < 1) return DSS_OK;
+    if (frames_f64) hipLaunchKernelGGL((vad_trials_group_kernel<double>), dim3(n_trials), dim3(VAD_THREADS), 0, st, d_models, (const double *)d_frames, desc, d_labels, d_logits);
+    else hipLaunchKernelGGL((vad_trials_group_kernel<float>), dim3(n_trials), dim3(VAD_THREADS), 0, st, d_models, (const float *)d_frames, desc, d_labels, d_logits);
+    DSS_HIP_CHECK(hipGetLastError());
+    return DSS_OK;
+}
+
 // ---- scoring a trial list (dss_vad_score_trials_dev): what the validation pass derives from the logits of a trial --------------
 // Per frame, in float64 from the float32 logits: loss = logsumexp(z) - z[target] (nn.CrossEntropyLoss), prob = softmax(z)[1].
 // Per trial: the mean of the losses, summed IN FRAME ORDER by one thread (tiles of 256 frames go through LDS), and the number of

@@ -207,6 +207,8 @@ def _declare(L):
         "dss_vad_group_publish": (i, [vp, i, vp, vp]),
         "dss_vad_group_window_dev": (i, [vp, vp, i, vp]),
         "dss_vad_group_trial_dev": (i, [vp, vp, i, i, vp]),
+        "dss_vad_group_forward_trials_dev": (i, [vp, vp, i, C.c_longlong, i, vp, vp, vp, vp, vp, vp]),
+        "dss_dec_group_forward_trials_dev": (i, [vp, vp, i, C.c_longlong, i, vp, vp, vp, C.c_longlong, vp, vp]),
         "dss_fenc_create": (vp, []),
         "dss_fenc_destroy": (None, [vp]),
         "dss_fenc_frame_offsets": (C.c_longlong, [vp, i, vp]),

@@ -606,6 +606,24 @@ def _per_model(v, n, what):
     return [float(e) for e in v]
 
 
+def _group_trial_list(group, frames, ranges, models):
+    """The arguments of a group's ``forward_trials_torch``, checked: (contiguous frames, first int64, len int32, model int32, sum
+    len).  The model indices are left to the library, which names the trial of a bad one."""
+    import torch
+    from .validation import _ranges
+    if frames.dtype not in (torch.float64, torch.float32):
+        raise TypeError("frames must be float64 or float32")
+    if frames.dim() != 2 or frames.shape[1] != group.C or not frames.is_cuda:
+        raise ValueError(f"frames must be a CUDA tensor of shape (N, {group.C})")
+    first, length, total = _ranges(group._L, int(frames.shape[0]), ranges)
+    model = np.ascontiguousarray(np.asarray(models, dtype=np.int64).ravel())
+    if len(model) != len(first):
+        raise ValueError(f"{len(model)} model indices for {len(first)} trials")
+    if len(model) and (model.min() < -2 ** 31 or model.max() >= 2 ** 31):
+        raise ValueError("a model index must fit 32 bits")
+    return frames.contiguous(), first, length, model.astype(np.int32), total
+
+
 class _MaskStage:
     """A group step's host masks on their way to the device: one page-locked buffer and one copy per step.  Two buffers take
     turns, each guarded by an event behind its copy, so filling the next step's masks does not wait for the step in flight."""
@@ -783,6 +801,21 @@ class DecoderGroupTrainerGPU:
         _lib.check(self._L.dss_dec_group_features(self._h, m, self._last[m], out.ctypes.data))
         return out
 
+    def forward_trials_torch(self, frames, ranges, models, max_rows: int = 0):
+        """The members' decoders on a trial list in one set of launches (``dss_dec_group_forward_trials_dev``): as
+        ``BiLstmDecoderGPU.forward_trials_torch`` with one model index per range -- trial i runs on member ``models[i]``'s current
+        weights, in stream order behind the steps enqueued so far, with nothing published and nothing of the members written.
+        ``max_rows`` (0: the default) bounds the rows of the two layer buffers; a longer list runs in several sets of launches.
+        Returns float32 CUDA features (sum len, n_outputs) in list order, a trial's bits those of a ``BiLstmDecoderGPU`` holding
+        that member's weights."""
+        import torch
+        frames, first, length, model, total = _group_trial_list(self, frames, ranges, models)
+        feats = torch.empty((total, self.O), dtype=torch.float32, device=frames.device)
+        _lib.check(self._L.dss_dec_group_forward_trials_dev(self._h, frames.data_ptr(), int(frames.dtype == torch.float64), int(frames.shape[0]),
+                                                            len(first), first.ctypes.data, length.ctypes.data, model.ctypes.data, int(max_rows),
+                                                            feats.data_ptr(), torch.cuda.current_stream().cuda_stream))
+        return feats
+
     def publish(self, m: int, decoder: "_decoder.BiLstmDecoderGPU"):
         """Copy model m's current weights device to device into an inference handle of the same sizes."""
         import torch
@@ -831,7 +864,8 @@ def _group_epoch(step, gens, n_trials, lengths, hidden_units, dropout, shuffle, 
 
 
 def train_decoders(state_dicts, train_corpora, valid_corpora, epochs: int = 8, dropout: float = 0.5, lr=LR, seeds=None, columns=None,
-                   shuffle: bool = True, alpha: float = ALPHA, eps: float = EPS, max_streams: int = 256, mask_source: str = "host"):
+                   shuffle: bool = True, alpha: float = ALPHA, eps: float = EPS, max_streams: int = 256, mask_source: str = "host",
+                   group_validation: bool = False):
     """M ``train_decoder`` loops in lock step on one ``DecoderGroupTrainerGPU``: the folds of train_bidirectional_model.py:65-68,
     seeds or learning rates as one run.  ``state_dicts[m]``, ``train_corpora[m]``, ``valid_corpora[m]`` and ``seeds[m]`` (default
     0 .. M - 1) are model m's arguments of ``train_decoder``; ``lr`` is a scalar or one per model; ``columns`` is shared.
@@ -844,9 +878,13 @@ def train_decoders(state_dicts, train_corpora, valid_corpora, epochs: int = 8, d
 
     ``mask_source="device"``: the permutations still come from those generators; model m's masks come from
     ``DeviceMaskSource(seeds[m])``, one draw per trial stepped, all masks of a step from one launch -- again what
-    ``train_decoder(..., mask_source="device", seed=seeds[m])`` computes alone, bit for bit."""
+    ``train_decoder(..., mask_source="device", seed=seeds[m])`` computes alone, bit for bit.
+
+    ``group_validation=True``: the validation corpora go to the device once, before the first epoch (``GroupValidationSet``), and
+    an epoch's M publish + validate calls become one ``decoder_validation_group`` call on the trainers' own weights; histories and
+    best weights are the same, bit for bit."""
     import torch
-    from .validation import _corpus_frames
+    from .validation import GroupValidationSet, _corpus_frames, decoder_validation_group
     state_dicts, train_corpora, valid_corpora = list(state_dicts), list(train_corpora), list(valid_corpora)
     M = len(state_dicts)
     seeds = list(range(M)) if seeds is None else list(seeds)
@@ -874,6 +912,7 @@ def train_decoders(state_dicts, train_corpora, valid_corpora, epochs: int = 8, d
     gens = [torch.Generator().manual_seed(int(s)) for s in seeds]
     dec = _decoder.BiLstmDecoderGPU(max(1, min(max(v[3] for v in valid), int(max_streams))), longest, state_dict=tr.state_dict(0))
     lengths = [[n for _, n in r] for r in ranges]
+    vset = GroupValidationSet(valid_corpora, "decoder", columns) if group_validation else None
 
     def step(trials, masks):
         sl = [None if k is None else slice(ranges[m][k][0], ranges[m][k][0] + ranges[m][k][1]) for m, k in enumerate(trials)]
@@ -885,12 +924,16 @@ def train_decoders(state_dicts, train_corpora, valid_corpora, epochs: int = 8, d
     for _ in range(int(epochs)):
         steps, losses = _group_epoch(step, gens, [len(r) for r in ranges], lengths, tr.H, dropout, shuffle, sources)
         losses = torch.stack(losses).cpu().numpy() if losses else np.zeros((0, M))     # the losses stay on the device until here
+        vs = decoder_validation_group(tr, vset) if group_validation else None
         for m in range(M):
             mine = np.array([losses[k, m] for k, trials in enumerate(steps) if trials[m] is not None])
             n_steps[m] += len(mine)
-            tr.publish(m, dec)
-            vx, vy, vid, _ = valid[m]
-            v = decoder_validation(dec, vx, vy, vid, columns=columns)
+            if group_validation:
+                v = vs[m]
+            else:
+                tr.publish(m, dec)
+                vx, vy, vid, _ = valid[m]
+                v = decoder_validation(dec, vx, vy, vid, columns=columns)
             keep = v["loss"] < best[m][1]                   # StoreBestModel.update: strictly less
             if keep:
                 best[m] = (tr.state_dict(m), v["loss"])
@@ -1094,6 +1137,22 @@ class VadGroupTrainerGPU:
         c = np.ascontiguousarray(c, dtype=np.float32).reshape(2, self.H)
         _lib.check(self._L.dss_vad_group_state(self._h, self._member(m), h.ctypes.data, c.ctypes.data, 1))
 
+    def forward_trials_torch(self, frames, ranges, models, want_logits: bool = False):
+        """The members' detectors on a trial list in one launch (``dss_vad_group_forward_trials_dev``): as
+        ``VadLstmGPU.forward_trials_torch`` with one model index per range -- trial i runs on member ``models[i]``'s current
+        weights, in stream order behind the trials enqueued so far, from the zero state; nothing is published and nothing of the
+        members (their carried state included) is written.  Returns int32 CUDA labels (sum len,) [, float32 logits (sum len, 2)]
+        in list order, a trial's bits those of a ``VadLstmGPU`` holding that member's weights."""
+        import torch
+        frames, first, length, model, total = _group_trial_list(self, frames, ranges, models)
+        labels = torch.empty((total,), dtype=torch.int32, device=frames.device)
+        logits = torch.empty((total, 2), dtype=torch.float32, device=frames.device) if want_logits else None
+        _lib.check(self._L.dss_vad_group_forward_trials_dev(self._h, frames.data_ptr(), int(frames.dtype == torch.float64), int(frames.shape[0]),
+                                                            len(first), first.ctypes.data, length.ctypes.data, model.ctypes.data,
+                                                            labels.data_ptr(), logits.data_ptr() if want_logits else None,
+                                                            torch.cuda.current_stream().cuda_stream))
+        return (labels, logits) if want_logits else labels
+
     def publish(self, m: int, detector: "_vad.VadLstmGPU"):
         """Copy model m's current weights device to device into an inference handle of the same sizes (``VadLstmGPU``)."""
         import torch
@@ -1103,7 +1162,8 @@ class VadGroupTrainerGPU:
 
 
 def train_vads(state_dicts, train_corpora, valid_corpora, epochs: int = 8, window: int = 50, dropout: float = 0.5, lr=LR, seeds=None,
-               columns=None, shuffle: bool = True, alpha: float = ALPHA, eps: float = EPS, mask_source: str = "host"):
+               columns=None, shuffle: bool = True, alpha: float = ALPHA, eps: float = EPS, mask_source: str = "host",
+               group_validation: bool = False):
     """M ``train_vad`` loops in lock step on one ``VadGroupTrainerGPU``: the day split of train_unidirectional_vad.py:81-93, seeds
     or learning rates as one run.  ``state_dicts[m]``, ``train_corpora[m]``, ``valid_corpora[m]`` and ``seeds[m]`` (default
     0 .. M - 1) are model m's arguments of ``train_vad``; ``lr`` is a scalar or one per model; ``columns`` is shared.
@@ -1117,9 +1177,13 @@ def train_vads(state_dicts, train_corpora, valid_corpora, epochs: int = 8, windo
 
     ``mask_source="device"``: the permutations still come from those generators; model m's masks come from
     ``DeviceMaskSource(seeds[m])``, one draw per trial stepped, all masks of a step from one launch -- again what
-    ``train_vad(..., mask_source="device", seed=seeds[m])`` computes alone, bit for bit."""
+    ``train_vad(..., mask_source="device", seed=seeds[m])`` computes alone, bit for bit.
+
+    ``group_validation=True``: the validation corpora go to the device once, before the first epoch (``GroupValidationSet``), and
+    an epoch's M publish + validate calls become one ``vad_validation_group`` call on the trainers' own weights; histories and
+    best weights are the same, bit for bit."""
     import torch
-    from .validation import _corpus_frames
+    from .validation import GroupValidationSet, _corpus_frames, vad_validation_group
     state_dicts, train_corpora, valid_corpora = list(state_dicts), list(train_corpora), list(valid_corpora)
     M = len(state_dicts)
     seeds = list(range(M)) if seeds is None else list(seeds)
@@ -1143,6 +1207,7 @@ def train_vads(state_dicts, train_corpora, valid_corpora, epochs: int = 8, windo
     gens = [torch.Generator().manual_seed(int(s)) for s in seeds]
     detector = _vad.VadLstmGPU(1, state_dict=tr.state_dict(0))
     lengths = [[n for _, n in r] for r in ranges]
+    vset = GroupValidationSet(valid_corpora, "vad", columns) if group_validation else None
 
     def step(trials, masks):
         sl = [None if k is None else slice(ranges[m][k][0], ranges[m][k][0] + ranges[m][k][1]) for m, k in enumerate(trials)]
@@ -1154,13 +1219,17 @@ def train_vads(state_dicts, train_corpora, valid_corpora, epochs: int = 8, windo
     for _ in range(int(epochs)):
         steps, out = _group_epoch(step, gens, [len(r) for r in ranges], lengths, tr.H, dropout, shuffle, sources, dropout_mask, tr.H)
         out = [(losses.cpu().numpy(), counts) for losses, counts in out]       # the losses stay on the device until here
+        vs = vad_validation_group(tr, vset) if group_validation else None
         for m in range(M):
             mine = [losses[m, :counts[m]] for (losses, counts), trials in zip(out, steps) if trials[m] is not None]
             mine = np.concatenate(mine) if mine else np.zeros(0)
             n_steps[m] += len(mine)
-            tr.publish(m, detector)
-            vx, vy, vid = _corpus(valid_corpora[m])
-            v = vad_validation(detector, vx, vy, vid, columns=columns)
+            if group_validation:
+                v = vs[m]
+            else:
+                tr.publish(m, detector)
+                vx, vy, vid = _corpus(valid_corpora[m])
+                v = vad_validation(detector, vx, vy, vid, columns=columns)
             keep = v["accuracy"] > best[m][1]               # StoreBestModel.update: strictly greater
             if keep:
                 best[m] = (tr.state_dict(m), v["accuracy"])

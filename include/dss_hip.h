@@ -19,7 +19,8 @@
  * reference's training scripts), Part 9 the training of the neural detector, Part 10 that of the decoder, Part 11 the
  * spectrograms behind the reference's spectral analyses, Part 13 several decoders trained side by side, Part 14 the trainers'
  * dropout masks drawn on the device, Part 15 several detectors trained side by side, Part 16 the LPC feature encoder behind a
- * training corpus' `lpc_coefficients`, each described at its declarations.
+ * training corpus' `lpc_coefficients`, Part 17 the models of a group of trainers over one trial list, each described at its
+ * declarations.
  *
  * Error convention: functions returning int return 0 on success and a negative DSS_E* code on failure;
  * dss_last_error() gives a thread-local message.  Creators return NULL on failure (the reference's
@@ -985,6 +986,34 @@ long long dss_fenc_tap_scores(dss_fenc *f, double *out, long long n);
  * `which`: 0 spectrum / cepstrum / LPC, 1 residual and scores, 2 pitch track.  Negative when there is no timed call. */
 int dss_fenc_enable_timing(dss_fenc *f, int on);
 double dss_fenc_kernel_ms(dss_fenc *f, int which);
+
+/* ------------------------------------------------------------------------------------------------
+ * Part 17 -- the models of a group of trainers (Parts 13 and 15) over one trial list: Part 8's forward calls with a model per
+ * trial, so that the validation passes of M models trained side by side are one set of launches and not M.  d_frames, first and
+ * len are Part 8's (checked by dss_trials_check; ranges may overlap, so the same trial may be listed once per model: a seed or
+ * learning-rate sweep over one corpus); model is a HOST array, model[i] in [0, M), and a model may own no trial.  Outputs are
+ * concatenated in LIST order whatever the models are, so Part 8's score functions (dss_vad_score_trials_dev,
+ * dss_dec_mse_trials_dev) take them as they are.  Every trial starts from the zero state; there are no dropout masks.
+ * The weights are the members' current ones, read in stream order behind any step enqueued on the same stream: nothing is
+ * published, no inference handle is involved, and nothing of the members -- gradients, square averages, workspaces, carried
+ * state -- is written.  A trial's outputs are bit-identical to Part 8's on an inference handle that holds that member's weights.
+ * Refused with a message: a NULL group and, unless the list is empty, NULL frames, outputs or model; a model index out of
+ * range; a member named by the list without parameters loaded; a decoder trial starting behind row 2^31 - 1.  An empty list
+ * returns DSS_OK and launches nothing.  On one group, trial-list calls are issued on one stream, or one after the other has
+ * finished: the group keeps the call's tables.
+ * ---------------------------------------------------------------------------------------------- */
+/* The detectors (csrc/vad_lstm.hip): one launch, a workgroup per trial, longest first across all models.  d_labels
+ * int32[sum len]; d_logits float32[sum len][2] or NULL. */
+int dss_vad_group_forward_trials_dev(dss_vad_group *g, const void *d_frames, int frames_are_f64, long long N, int n_trials,
+                                     const long long *first, const int *len, const int *model,
+                                     int *d_labels, float *d_logits /* or NULL */, void *hip_stream);
+/* The decoders (csrc/bilstm_decoder.hip): d_feats float32[sum len][n_outputs].  The layer outputs go to two buffers of
+ * min(sum len, max_rows) rows of 2H floats that the group owns and grows on demand; a list of more frames runs as several sets
+ * of three launches, cut at trial borders in list order, and a single trial longer than max_rows is refused.  max_rows == 0:
+ * 2^19 rows.  A trial's length is not bound by the group's max_frames: the trainers' workspaces are not used. */
+int dss_dec_group_forward_trials_dev(dss_dec_group *g, const void *d_frames, int frames_are_f64, long long N, int n_trials,
+                                     const long long *first, const int *len, const int *model, long long max_rows /* 0: default */,
+                                     float *d_feats, void *hip_stream);
 
 #ifdef __cplusplus
 }
