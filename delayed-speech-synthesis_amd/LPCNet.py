@@ -57,19 +57,46 @@ class LPCNet:
 
 
 class LPCFeatureEncoder:
-    """Feature *encoder* (lpcnet_compute_single_frame_features, cLPCNet.pxd:15-19).  The reference uses it
-    only offline in prepare_corpus.py:72-73; it is not on the synthesis path this library accelerates."""
+    """Feature *encoder* (lpcnet_compute_single_frame_features, cLPCNet.pxd:15-19), which the reference uses offline in
+    prepare_corpus.py:72-73.  Opt-in: the library binds the xiph encoder symbols to its own encoder (this project's statement
+    of the published method, parity with xiph unpinned) only with DSS_LPCNET_ENCODER=1 in the environment at construction;
+    without it lpcnet_encoder_create() returns NULL and this raises MemoryError, as LPCNet.pyx:53-56 does.  The state
+    carries across calls, as an xiph object's does."""
     NB_FEATURES: int = 20
     NB_TOTAL_FEATURES: int = 36
     LPCNET_FRAME_SIZE: int = 160
 
     def __init__(self):
-        # LPCNet.pyx:53-56: lpcnet_encoder_create() == NULL -> MemoryError.  libdss_hip.so exports the encoder symbols
-        # (cLPCNet.pxd:15-19) and its create returns NULL: corpus preparation is outside the accelerated path.
-        st = _dss.load().lpcnet_encoder_create()
-        if not st:
-            raise MemoryError(_dss.load().dss_last_error().decode())
-        raise MemoryError("unexpected encoder state from libdss_hip")
+        L = _dss.load()
+        self._st = L.lpcnet_encoder_create()
+        if not self._st:
+            raise MemoryError(L.dss_last_error().decode())      # LPCNet.pyx:55-56
+        self._L = L
+
+    def __del__(self):
+        st, self._st = getattr(self, "_st", None), None
+        if st:
+            self._L.lpcnet_encoder_destroy(st)                  # LPCNet.pyx:58-60
+
+    def reset_encoder(self):
+        self._L.lpcnet_encoder_init(self._st)                   # LPCNet.pyx:62-63
+
+    def compute_LPC_features(self, audio_samples):
+        """LPCNet.pyx:65-87: int16[n] -> float32[n // 160, 20]; all frames in one push (dss_lpcnet_encoder_frames), which gives
+        the bits of the reference's 160-sample loop over lpcnet_compute_single_frame_features."""
+        # the Cython signature is np.ndarray[np.int16_t, ndim=1]; mirror its buffer checks
+        if not isinstance(audio_samples, np.ndarray):
+            raise TypeError("Argument 'audio_samples' has incorrect type (expected numpy.ndarray, got %s)"
+                            % type(audio_samples).__name__)
+        if audio_samples.ndim != 1:
+            raise ValueError("Buffer has wrong number of dimensions (expected 1, got %d)" % audio_samples.ndim)
+        if audio_samples.dtype != np.int16:
+            raise ValueError("Buffer dtype mismatch, expected 'int16_t' but got '%s'" % audio_samples.dtype.name)
+        n_frames = len(audio_samples) // self.LPCNET_FRAME_SIZE
+        pcm = np.ascontiguousarray(audio_samples[:n_frames * self.LPCNET_FRAME_SIZE])
+        out = np.zeros((n_frames, self.NB_TOTAL_FEATURES), dtype=np.float32)
+        _dss.check(self._L.dss_lpcnet_encoder_frames(self._st, pcm.ctypes.data, n_frames, out.ctypes.data))
+        return np.ascontiguousarray(out[:, :self.NB_FEATURES])
 
 
 class LPCFeatureFile:

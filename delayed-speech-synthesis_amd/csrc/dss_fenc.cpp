@@ -56,7 +56,7 @@ extern "C" void dss_fenc_destroy(dss_fenc *f)
     dss_destroy_handle(f);
 }
 
-static int fenc_setup(dss_fenc *f)
+int dss_fenc_setup(DssDevBlocks &blocks, DssFencDev *d)
 {
     std::vector<float> win(FENC_WINDOW);
     const std::vector<double> tw = dss_twiddles(FENC_WINDOW);
@@ -67,14 +67,14 @@ static int fenc_setup(dss_fenc *f)
     const LpcTables T;
     float *p32 = nullptr;
     double *p64 = nullptr;
-    int rc = f->blocks.upload(win.data(), win.size(), &p32);             f->d.window = p32;
-    if (!rc) { rc = f->blocks.upload(tw.data(), tw.size(), &p64);         f->d.tw = p64; }
-    if (!rc) { rc = f->blocks.upload(T.dct, (size_t)324, &p32);           f->d.lpc.dct_table = p32; }
-    if (!rc) { rc = f->blocks.upload(T.cos_kl.data(), T.cos_kl.size(), &p32); f->d.lpc.cos_kl = p32; }
-    if (!rc) { rc = f->blocks.upload(T.ia, (size_t)160, &p32);            f->d.lpc.interp_a = p32; }
-    if (!rc) { rc = f->blocks.upload(T.ib, (size_t)160, &p32);            f->d.lpc.interp_b = p32; }
-    if (!rc) { rc = f->blocks.upload(T.lagw, (size_t)17, &p64);           f->d.lpc.lag_window = p64; }
-    f->d.idct_scale = sqrt(2. / DSS_NB_BANDS);
+    int rc = blocks.upload(win.data(), win.size(), &p32);             d->window = p32;
+    if (!rc) { rc = blocks.upload(tw.data(), tw.size(), &p64);         d->tw = p64; }
+    if (!rc) { rc = blocks.upload(T.dct, (size_t)324, &p32);           d->lpc.dct_table = p32; }
+    if (!rc) { rc = blocks.upload(T.cos_kl.data(), T.cos_kl.size(), &p32); d->lpc.cos_kl = p32; }
+    if (!rc) { rc = blocks.upload(T.ia, (size_t)160, &p32);            d->lpc.interp_a = p32; }
+    if (!rc) { rc = blocks.upload(T.ib, (size_t)160, &p32);            d->lpc.interp_b = p32; }
+    if (!rc) { rc = blocks.upload(T.lagw, (size_t)17, &p64);           d->lpc.lag_window = p64; }
+    d->idct_scale = sqrt(2. / DSS_NB_BANDS);
     return rc;
 }
 
@@ -83,7 +83,7 @@ extern "C" dss_fenc *dss_fenc_create(void)
     if (dss_ensure_device()) return nullptr;
     dss_fenc *f = new dss_fenc;
     hipGetDevice(&f->device);
-    if (fenc_setup(f)) { dss_fenc_destroy(f); return nullptr; }
+    if (dss_fenc_setup(f->blocks, &f->d)) { dss_fenc_destroy(f); return nullptr; }
     return f;
 }
 

@@ -558,28 +558,72 @@ extern "C" void lpcnet_synthesize(LPCNetState *st, const float *features, short 
 extern "C" int lpcnet_get_size(void) { return (int)sizeof(LPCNetState); }
 
 // ---- encoder half of the bound ABI (cLPCNet.pxd:15-19; LPCNet.pyx:43-87) -----------------------------------------
-// The feature ENCODER (pitch search, Bark cepstrum of a PCM frame) is corpus preparation (prepare_corpus.py:72-73),
-// outside the accelerated path.  The symbols exist so that the reference's own LPCNet.pyx links against this library
-// unchanged; lpcnet_encoder_create() returns NULL, which the reference's wrapper turns into MemoryError
-// (LPCNet.pyx:53-56), so a caller finds out at construction time, not from wrong features.
-struct LPCNetEncState;
+// The feature ENCODER (pitch search, Bark cepstrum of a PCM frame) is corpus preparation (prepare_corpus.py:72-73), which
+// drives it 160 samples at a time on one state.  The encoder this library has (Parts 16 and 18) is this project's statement
+// of the published method, with parity to xiph's code unpinned, so it never stands in for xiph's silently: the symbols are
+// bound to it only where the environment says DSS_LPCNET_ENCODER=1 when lpcnet_encoder_create() is called.  Otherwise create
+// returns NULL, which the reference's wrapper turns into MemoryError (LPCNet.pyx:53-56), so a caller finds out at
+// construction time, not from features of another method.  A state wraps a one-stream handle of Part 18.
+struct LPCNetEncState { dss_fenc_streams *h; };
+
+static bool encoder_opted_in()
+{
+    const char *e = getenv("DSS_LPCNET_ENCODER");
+    return e && !strcmp(e, "1");
+}
+
 extern "C" LPCNetEncState *lpcnet_encoder_create(void)
 {
-    dss_set_error("LPCNet feature encoder is not provided by libdss_hip (corpus preparation is outside the accelerated path)");
-    return nullptr;
+    if (!encoder_opted_in()) {
+        dss_set_error("LPCNet feature encoder is not provided by libdss_hip (corpus preparation is outside the accelerated path)");
+        return nullptr;
+    }
+    dss_fenc_streams *h = dss_fenc_streams_create(1);
+    if (!h) {
+        char why[400];
+        snprintf(why, sizeof(why), "%s", dss_last_error());
+        dss_set_error("LPCNet feature encoder (DSS_LPCNET_ENCODER=1): %s", why);
+        return nullptr;
+    }
+    return new LPCNetEncState{h};
 }
-extern "C" int lpcnet_encoder_init(LPCNetEncState *) { return -1; }
-extern "C" void lpcnet_encoder_destroy(LPCNetEncState *) {}
+extern "C" int lpcnet_encoder_init(LPCNetEncState *st)
+{
+    if (!st) return -1;
+    return dss_fenc_streams_reset(st->h, nullptr, 0, nullptr) ? -1 : 0;
+}
+extern "C" void lpcnet_encoder_destroy(LPCNetEncState *st)
+{
+    if (!st) return;
+    dss_fenc_streams_destroy(st->h);
+    delete st;
+}
+// The published form quantises four frames through packet codebooks that are not at hand, and the reference never calls it:
+// a failing stub whatever the environment says.
 extern "C" int lpcnet_compute_features(LPCNetEncState *, const short *, float (*features)[36])
 {
     if (features) memset(features, 0, sizeof(float) * 4 * 36);
     dss_set_error("lpcnet_compute_features: encoder not provided by libdss_hip");
     return -1;
 }
-extern "C" int lpcnet_compute_single_frame_features(LPCNetEncState *, const short *, float *features)
+extern "C" long long dss_lpcnet_encoder_frames(LPCNetEncState *st, const short *pcm, int n_frames, float *out36)
 {
+    if (!st || n_frames < 0 || (n_frames && (!pcm || !out36))) { dss_set_error("dss_lpcnet_encoder_frames: bad arguments"); return DSS_EINVAL; }
+    return dss_fenc_streams_push(st->h, pcm, n_frames, nullptr, out36);
+}
+extern "C" int lpcnet_compute_single_frame_features(LPCNetEncState *st, const short *pcm, float *features)
+{
+    if (!st) {
+        if (features) memset(features, 0, sizeof(float) * 36);
+        dss_set_error("lpcnet_compute_single_frame_features: encoder not provided by libdss_hip");
+        return -1;
+    }
+    if (pcm && features && dss_fenc_streams_push(st->h, pcm, 1, nullptr, features) == 1) return 0;
+    if (!pcm || !features) dss_set_error("lpcnet_compute_single_frame_features: null argument");
     if (features) memset(features, 0, sizeof(float) * 36);
-    dss_set_error("lpcnet_compute_single_frame_features: encoder not provided by libdss_hip");
+    const long k = g_synth_failures.fetch_add(1);
+    if (k == 0 || k % 1000 == 0)
+        fprintf(stderr, "libdss_hip: lpcnet_compute_single_frame_features failed (%ld so far), features zero-filled: %s\n", k + 1, dss_last_error());
     return -1;
 }
 // cLPCNet.pxd:22-23 declares decode_packet inside a stray header block; nothing calls it

@@ -217,6 +217,14 @@ def _declare(L):
         "dss_fenc_tap_scores": (C.c_longlong, [vp, vp, C.c_longlong]),
         "dss_fenc_enable_timing": (i, [vp, i]),
         "dss_fenc_kernel_ms": (C.c_double, [vp, i]),
+        "dss_lpcnet_encoder_frames": (C.c_longlong, [vp, vp, i, vp]),
+        "dss_fenc_streams_create": (vp, [i]),
+        "dss_fenc_streams_destroy": (None, [vp]),
+        "dss_fenc_streams_check": (C.c_longlong, [i, i, vp]),
+        "dss_fenc_streams_reset": (i, [vp, vp, i, vp]),
+        "dss_fenc_streams_push": (C.c_longlong, [vp, vp, i, vp, vp]),
+        "dss_fenc_streams_push_dev": (C.c_longlong, [vp, vp, i, vp, vp, vp]),
+        "dss_fenc_streams_frames_seen": (i, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -23,8 +23,8 @@ SOURCES = ["dss_core.cpp", "dss_host.cpp", "dss_lpcnet_model.cpp", "dss_lpcnet_b
            "dss_async.cpp", "dss_avad.cpp", "acoustic_vad.hip", "hga_kernels.hip", "lpcnet_frame.hip", "lpcnet_sample.hip", "lpcnet_sample_pair.hip",
            "lpcnet_sample_generic.hip", "speech_gate.hip", "vad_lstm.hip", "bilstm_decoder.hip", "dss_vad_train.cpp", "vad_train.hip",
            "dss_dec_train.cpp", "dec_train.hip", "dss_dec_group.cpp", "dss_vad_group.cpp", "dss_spec.cpp", "spectral.hip", "dss_contam.cpp", "contamination.hip", "dss_dropout.cpp", "dropout.hip",
-           "dss_fenc.cpp", "feature_encoder.hip"]
-HEADERS = ["dss_common.h", "dss_host.h", "acoustic_vad.h", "avad_gain.h", "spectral.h", "spectral_frame.h", "contamination.h", "dropout.h", "feature_encoder.h", "lpc_chain.h", "lpc_tables.h", "lpcnet_device.h", "lpcnet_sample_common.h", "lstm_blocks.h", "dss_global_ptr.h", "../../include/dss_hip.h",
+           "dss_fenc.cpp", "feature_encoder.hip", "dss_fenc_stream.cpp", "feature_encoder_stream.hip"]
+HEADERS = ["dss_common.h", "dss_host.h", "acoustic_vad.h", "avad_gain.h", "spectral.h", "spectral_frame.h", "contamination.h", "dropout.h", "feature_encoder.h", "fenc_blocks.h", "lpc_chain.h", "lpc_tables.h", "lpcnet_device.h", "lpcnet_sample_common.h", "lstm_blocks.h", "dss_global_ptr.h", "../../include/dss_hip.h",
            "../../include/dss_lpcnet_blob.h"]
 # -ffp-contract=off: the path's parity contract is "same products, same sums, same order" as the scalar C
 # reference; a fused multiply-add anywhere would change results.

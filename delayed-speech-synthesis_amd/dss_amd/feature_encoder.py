@@ -5,6 +5,9 @@ The method is this project's statement of the published encoder (DESIGN.md secti
 tests/feature_encoder_reference.py); parity with xiph's code is not pinned.  One fresh encoder per trial, no LPCNet model
 needed.  Per 160-sample frame: 18 Bark cepstral coefficients, the pitch feature and correlation as the decoder reads them
 (together the 20 values ``LPCNet.synthesize`` takes) and the 16 LPC taps the decoder derives from that cepstrum.
+
+``LpcFeatureStreamsGPU`` (Part 18) is the same encoder with its state carried from push to push, for audio that arrives in
+pieces: any chunking of a stream gives the bits of the whole signal as one trial.  Whole trials stay with ``features_trials``.
 """
 from __future__ import annotations
 
@@ -117,4 +120,99 @@ class LpcFeatureEncoderGPU:
         cross-correlations at lag 256 - column, column 255 the sub-frame's normalised weight."""
         out = np.zeros((self._subframes, N_LAGS), dtype=np.float64)
         _lib.check(self._L.dss_fenc_tap_scores(self._h, out.ctypes.data, out.size))
+        return out
+
+
+def streams_check(n_streams: int, frames_max: int, counts=None) -> int:
+    """The argument checks of a push (dss_fenc_streams_check; needs no GPU): the number of frames it would encode."""
+    c = None if counts is None else np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+    if c is not None and len(c) != n_streams:
+        raise ValueError("counts must hold one value per stream")
+    return _lib.check(_lib.load().dss_fenc_streams_check(int(n_streams), int(frames_max), None if c is None else c.ctypes.data))
+
+
+class LpcFeatureStreamsGPU:
+    """The same encoder on ``n_streams`` streams whose state is carried from push to push (Part 18 of include/dss_hip.h): any
+    chunking of a stream gives, bit for bit, what ``LpcFeatureEncoderGPU.features_trials`` gives on the whole signal as one
+    trial.  One launch per push."""
+    NB_FEATURES: int = NB_FEATURES
+    NB_TOTAL_FEATURES: int = NB_TOTAL_FEATURES
+    LPCNET_FRAME_SIZE: int = FRAME_SIZE
+
+    def __init__(self, n_streams: int):
+        L = _lib.load()
+        self._L = L
+        self._h = None
+        self.n_streams = int(n_streams)
+        _lib.check(L.dss_fenc_streams_check(self.n_streams, 0, None))
+        _lib.require_gpu()
+        self._h = L.dss_fenc_streams_create(self.n_streams)
+        if not self._h:
+            raise _lib.DssError(L.dss_last_error().decode())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.dss_fenc_streams_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _counts(self, counts):
+        if counts is None:
+            return None
+        c = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+        if len(c) != self.n_streams:
+            raise ValueError("counts must hold one value per stream")
+        return c
+
+    def _shape(self, shape) -> int:
+        if len(shape) != 2 or shape[0] != self.n_streams or shape[1] % FRAME_SIZE:
+            raise ValueError("audio must be int16 (n_streams, 160 k)")
+        return shape[1] // FRAME_SIZE
+
+    def push(self, audio: np.ndarray, counts=None, total: bool = False) -> np.ndarray:
+        """int16 (S, 160 K), ``counts`` (S,) frames per stream or None for K each -> float32 (S, K, 20 | 36); the rows past a
+        stream's count are zeros, and a count of 0 leaves that stream's state untouched."""
+        audio = np.asarray(audio)
+        if audio.ndim != 2 or audio.dtype != np.int16:
+            raise ValueError("audio must be a two-dimensional int16 array")
+        K = self._shape(audio.shape)
+        audio = np.ascontiguousarray(audio)
+        c = self._counts(counts)
+        out = np.zeros((self.n_streams, K, NB_TOTAL_FEATURES), dtype=np.float32)
+        _lib.check(self._L.dss_fenc_streams_push(self._h, audio.ctypes.data, K, None if c is None else c.ctypes.data, out.ctypes.data))
+        return out if total else np.ascontiguousarray(out[:, :, :NB_FEATURES])
+
+    def push_torch(self, audio, counts=None, total: bool = False, stream=None):
+        """Device-resident form: CUDA int16 (S, 160 K) -> CUDA float32 (S, K, 20 | 36), queued on the current (or the given)
+        stream, no synchronisation.  ``counts`` is a host sequence."""
+        import torch
+        if not (isinstance(audio, torch.Tensor) and audio.is_cuda and audio.dtype == torch.int16 and audio.dim() == 2):
+            raise ValueError("audio must be a two-dimensional CUDA int16 tensor")
+        K = self._shape(tuple(audio.shape))
+        audio = audio.contiguous()
+        c = self._counts(counts)
+        dev = audio.device
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        # the launch writes every row, zeros past the counts included, in the stream's order; a no-op writes nothing
+        out = torch.empty((self.n_streams, K, NB_TOTAL_FEATURES), dtype=torch.float32, device=dev)
+        got = _lib.check(self._L.dss_fenc_streams_push_dev(self._h, audio.data_ptr(), K, None if c is None else c.ctypes.data,
+                                                           out.data_ptr(), s))
+        if got == 0:
+            out.zero_()
+        return out if total else out[:, :, :NB_FEATURES].contiguous()
+
+    def reset(self, streams=None, stream=None) -> None:
+        """The listed streams (None: all) back to the fresh state, in order on the null (or the given raw) stream."""
+        if streams is None:
+            _lib.check(self._L.dss_fenc_streams_reset(self._h, None, 0, stream))
+            return
+        idx = np.ascontiguousarray(streams, dtype=np.int32).reshape(-1)
+        _lib.check(self._L.dss_fenc_streams_reset(self._h, idx.ctypes.data, len(idx), stream))
+
+    @property
+    def frames_seen(self) -> np.ndarray:
+        """int64 (S,): frames every stream has encoded since its reset."""
+        out = np.zeros(self.n_streams, dtype=np.int64)
+        _lib.check(self._L.dss_fenc_streams_frames_seen(self._h, out.ctypes.data))
         return out

@@ -19,8 +19,8 @@
  * reference's training scripts), Part 9 the training of the neural detector, Part 10 that of the decoder, Part 11 the
  * spectrograms behind the reference's spectral analyses, Part 13 several decoders trained side by side, Part 14 the trainers'
  * dropout masks drawn on the device, Part 15 several detectors trained side by side, Part 16 the LPC feature encoder behind a
- * training corpus' `lpc_coefficients`, Part 17 the models of a group of trainers over one trial list, each described at its
- * declarations.
+ * training corpus' `lpc_coefficients`, Part 17 the models of a group of trainers over one trial list, Part 18 that encoder on streams
+ * with its state carried between pushes, each described at its declarations.
  *
  * Error convention: functions returning int return 0 on success and a negative DSS_E* code on failure;
  * dss_last_error() gives a thread-local message.  Creators return NULL on failure (the reference's
@@ -114,15 +114,27 @@ int lpcnet_get_size(void);
  * incremented (first failure and every 1000th are also printed to stderr). */
 long dss_error_count(void);
 
-/* cLPCNet.pxd:15-19 -- feature encoder (used only by prepare_corpus.py:72-73).  NOT provided under these names: create
- * returns NULL (the reference's LPCFeatureEncoder.__cinit__ raises MemoryError, LPCNet.pyx:53-56), the others return -1 and
- * zero their output.  The encoder this library has is Part 16, under names of its own. */
+/* cLPCNet.pxd:15-19 -- feature encoder (prepare_corpus.py:72-73 drives it 160 samples at a time on one state).  Bound to the
+ * encoder of Parts 16 and 18 ONLY where the environment holds DSS_LPCNET_ENCODER=1 when lpcnet_encoder_create() is called: that
+ * encoder is this project's statement of the published method, its parity with xiph's code is unpinned, and it must not stand
+ * in for xiph's silently (the decoder likewise refuses to run without named weights).
+ *   Without the opt-in: create returns NULL with "encoder" in dss_last_error() (the reference's LPCFeatureEncoder.__cinit__
+ * raises MemoryError, LPCNet.pyx:53-56), the others return -1 and zero their output.
+ *   With it: create returns a state that wraps a one-stream handle of Part 18 (NULL, "encoder" in the message, when no device
+ * is usable); lpcnet_encoder_init resets it and returns 0; lpcnet_compute_single_frame_features pushes pcm[160] and writes 36
+ * floats, returning 0, or on failure -1 with the features zeroed and dss_error_count() incremented; the state carries from call
+ * to call, so a 160-sample loop gives the bits of Part 16 on the whole signal.
+ *   lpcnet_compute_features is a failing stub either way (-1, 4 x 36 zeros): its published form quantises four frames through
+ * packet codebooks that are not at hand, and the reference never calls it. */
 typedef struct LPCNetEncState LPCNetEncState;
 LPCNetEncState *lpcnet_encoder_create(void);
 int lpcnet_encoder_init(LPCNetEncState *st);
 void lpcnet_encoder_destroy(LPCNetEncState *st);
 int lpcnet_compute_features(LPCNetEncState *st, const short *pcm, float features[4][36]);
 int lpcnet_compute_single_frame_features(LPCNetEncState *st, const short *pcm, float features[36]);
+/* The batched form on the same xiph state: n_frames frames of pcm[160 n_frames] in one push, out36 (n_frames, 36).  Returns
+ * the number of frames, DSS_EINVAL for a NULL state or buffers.  Equal bits to n_frames single-frame calls. */
+long long dss_lpcnet_encoder_frames(LPCNetEncState *st, const short *pcm, int n_frames, float *out36);
 
 /* Weights are data in this build (include/dss_lpcnet_blob.h); xiph compiles them in (nnet_data.c,
  * extensions/lpcnet/setup.py:34-36). */
@@ -960,7 +972,8 @@ int dss_vad_group_trial_dev(dss_vad_group *g, const dss_vad_group_trial *trials,
  *
  * A trial list is an int16 concatenation and n_trials + 1 ascending offsets (a HOST array; what session_trial_audio
  * returns): trial i is samples offsets[i] .. offsets[i + 1] and gives (offsets[i + 1] - offsets[i]) / 160 frames; a trial
- * shorter than 160 samples gives none.  The five xiph encoder symbols of Part 1 stay failing stubs.
+ * shorter than 160 samples gives none.  Audio that arrives in pieces, and the xiph encoder symbols of Part 1, go through the
+ * state-carrying form of Part 18, which gives these bits for any chunking.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct dss_fenc dss_fenc;
 dss_fenc *dss_fenc_create(void);
@@ -1014,6 +1027,38 @@ int dss_vad_group_forward_trials_dev(dss_vad_group *g, const void *d_frames, int
 int dss_dec_group_forward_trials_dev(dss_dec_group *g, const void *d_frames, int frames_are_f64, long long N, int n_trials,
                                      const long long *first, const int *len, const int *model, long long max_rows /* 0: default */,
                                      float *d_feats, void *hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Part 18 -- the LPC feature encoder of Part 16 on streams: n_streams encoders whose state is carried from push to push, for
+ * audio that arrives in packets (a microphone beside 40 ms ECoG packets delivers 4 frames a packet) and for the xiph encoder
+ * symbols of Part 1.  The method is causal -- frame i reads samples up to 160 i + 159 -- so ANY chunking of a stream gives,
+ * bit for bit, the 36 values Part 16 gives on the whole signal as one trial.  Per stream the handle keeps on the device 480 raw
+ * samples, the taps of the two newest frames, the pitch track's state and a frame counter (about 3 KB); a fresh or reset
+ * stream is the all-zero state.  A push is ONE launch, a workgroup per stream, whatever the numbers of streams and frames
+ * (csrc/feature_encoder_stream.hip); scores never reach global memory, and there is no tap function for this path.
+ *   A push takes audio int16 (n_streams, 160 frames_max) and counts, a HOST int[n_streams] or NULL (every stream takes
+ * frames_max): stream s encodes its first counts[s] frames, 0 <= counts[s] <= frames_max; a count of 0 lets the stream sit the
+ * push out and leaves its state untouched.  out36 is float32 (n_streams, frames_max, 36); rows past a stream's count are written
+ * as zeros.  Returns the number of frames encoded.  frames_max == 0, or all counts 0, is a no-op that returns 0 and writes
+ * nothing.  Refused with a message before any launch: a NULL handle or NULL buffers, n_streams < 1, frames_max < 0 (or beyond
+ * 2^31 / 320), a count out of range, a stream index out of range in a reset.  On one handle, calls are issued on one stream, or
+ * one after the other has finished.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct dss_fenc_streams dss_fenc_streams;
+dss_fenc_streams *dss_fenc_streams_create(int n_streams);
+void dss_fenc_streams_destroy(dss_fenc_streams *h);
+/* The argument checks of a push on their own (no device needed): the number of frames it would encode, or DSS_EINVAL. */
+long long dss_fenc_streams_check(int n_streams, int frames_max, const int *counts /* or NULL */);
+/* The listed streams (a HOST int[n]; NULL: all of them) back to the fresh state, in stream order on hip_stream. */
+int dss_fenc_streams_reset(dss_fenc_streams *h, const int *streams /* or NULL */, int n, void *hip_stream);
+/* Host buffers; complete on return. */
+long long dss_fenc_streams_push(dss_fenc_streams *h, const short *audio, int frames_max, const int *counts /* or NULL */,
+                                float *out36);
+/* The same on device buffers, launched on hip_stream with no host synchronisation; counts is read before the call returns. */
+long long dss_fenc_streams_push_dev(dss_fenc_streams *h, const short *d_audio, int frames_max, const int *counts /* or NULL */,
+                                    float *d_out36, void *hip_stream);
+/* out[s] = frames stream s has encoded since its reset (host bookkeeping: includes pushes still queued). */
+int dss_fenc_streams_frames_seen(dss_fenc_streams *h, long long *out);
 
 #ifdef __cplusplus
 }
