@@ -9,10 +9,10 @@
 //                                         1 / (1 - p); the mask is an INPUT here, (T, 2H) multipliers or NULL
 // The steps of one direction of one layer are serial; the two directions of a layer are independent, and so are the frames
 // everywhere else.  Seven launches per trial on one stream ("Training the decoder"):
-//   dec_train_layer_kernel<0>, <1>   a workgroup per direction: bilstm_layer_kernel's chain for one stream (lstm_blocks.h: the
-//                                    dot products, the row of W_hh in registers, the cell update) with the stash the backward pass needs
-//   dec_train_head_kernel            a workgroup per 8 frames: features (dec_regress_kernel's dot product), dfeat, the per-frame
-//                                    loss terms, dtop = W_r^T dfeat
+//   dec_train_layer_kernel<0>, <1>   a workgroup per direction: bilstm_layer_body (lstm_blocks.h), the loop the inference kernels run,
+//                                    for one stream, keeping the stash the backward pass needs
+//   dec_train_head_kernel            a workgroup per 8 frames: features (dec_regress_rows, the inference kernels' regressor), dfeat,
+//                                    the per-frame loss terms, dtop = W_r^T dfeat
 //   dec_train_bptt_kernel<1>         a workgroup per direction: backward through time, the gate gradients dG1[dir][T][4H]; a
 //                                    third workgroup adds the per-frame loss terms in frame order
 //   dec_train_dmid_kernel            a workgroup per 8 frames: what layer 1 sends down through both W_ih_l1 and the mask
@@ -52,71 +52,31 @@ long dss_dec_train_param_count(int C, int H, int O) { return dec_train_off(C, H,
 // Every pointer read from the descriptor or from a trial table goes through dss_gp (dss_global_ptr.h): the group kernels at the end
 // of this file load them from a table, and must still address global memory, not the flat aperture.
 
-// ---- forward, one layer: bilstm_layer_kernel<., 1> for one stream, with the stash ---------------------------------------------
-// blockIdx.x is the direction; step s is frame s (forward) or T - 1 - s (backward).  The dot products, the bias add and the cell
-// update are the inference kernel's, term for term, so the features of a trial without a mask are its bits.
+// ---- forward, one layer: bilstm_layer_body (lstm_blocks.h) for one stream, keeping the stash -------------------------------------
+// The loop is the inference kernels', so the features of a trial without a mask are their bits.  dir is the direction; step s is
+// frame s (forward) or T - 1 - s (backward).  Kept of a step: the activated gates (row s of act), c and h behind it (row s + 1 of
+// the stashes; row 0 is the zero state), h at the step's frame -- times the mask in layer 0 (midm), as it is in layer 1 (top);
+// the unmasked h is what the direction carries to its own next step -- and, from layer 0's forward direction, the frames as
+// float32 (xs).
 template <typename InT, int LAYER>
 __device__ __forceinline__ void dec_train_layer_body(const DssDecTrainDev &d, const int dir, const InT *__restrict__ in, const int T,
                                                      const float *__restrict__ mask)
 {
-    typedef typename LstmVec<1>::type V;
-    __shared__ __attribute__((aligned(16))) V xin[DEC_TP][DEC_MAXC];
-    __shared__ __attribute__((aligned(16))) V hs[DEC_MAXH];               // units H .. Hp-1 stay zero
-    __shared__ __attribute__((aligned(16))) V gates[4 * DEC_MAXH];
-    const int tid = threadIdx.x, H = d.H, H4 = 4 * H;
-    const int Cin = LAYER ? 2 * H : d.C;
-    const int Cp = (Cin + 3) & ~3, Hp = (H + 3) & ~3;
-    const float *wT = dss_gp(d.wT[LAYER][dir]);
-    const bool own = tid < H, rowt = tid < H4;
+    const int tid = threadIdx.x, H = d.H, H4 = 4 * H, Cin = LAYER ? 2 * H : d.C;
     float *act = dss_gp(d.act[LAYER][dir]), *cst = dss_gp(d.c[LAYER][dir]), *hst = dss_gp(d.h[LAYER][dir]);
-    float c = 0.f;
-    for (int k = tid; k < DEC_MAXH; k += DEC_THREADS) hs[k].v = 0.f;
-    for (int k = tid; k < DEC_TP * DEC_MAXC; k += DEC_THREADS) reinterpret_cast<float *>(xin)[k] = 0.f;
-    if (own) { cst[tid] = 0.f; hst[tid] = 0.f; }           // row 0 of the stashes: the zero state
-    const float bias = rowt ? dss_gp(d.b[LAYER][dir])[tid] : 0.f;
-    f4 whh[DEC_MAXH / 4];                                  // this thread's row of W_hh, in registers for all steps
-    lstm_load_row<DEC_MAXH>(whh, wT + (size_t)Cp * H4, H4, tid, rowt, Hp);
-    __syncthreads();
-    for (int step0 = 0; step0 < T; step0 += DEC_TP) {
-        const int nst = min(DEC_TP, T - step0);
-        for (int idx = tid; idx < nst * Cin; idx += DEC_THREADS) {
-            const int tt = idx / Cin, k = idx - tt * Cin;
-            const int step = step0 + tt, t = dir ? T - 1 - step : step;
-            const float x = (float)in[(size_t)t * Cin + k];
-            xin[tt][k].v = x;
-            if (LAYER == 0 && dir == 0) dss_gp(d.xs)[(size_t)t * Cin + k] = x;
-        }
-        __syncthreads();
-        V pre[DEC_TP];
-#pragma unroll
-        for (int tt = 0; tt < DEC_TP; ++tt) pre[tt].v = 0.f;
-        if (rowt) lstm_dot_steps<1, V, DEC_MAXC, DEC_TP>(pre, wT, H4, tid, xin, Cp);   // (steps beyond nst: stale inputs, never used)
-#pragma unroll
-        for (int tt = 0; tt < DEC_TP; ++tt) {
-            if (tt >= nst) break;
-            const int step = step0 + tt, t = dir ? T - 1 - step : step;
-            if (rowt) {
-                V acc = pre[tt];
-                lstm_dot_row<1, V, DEC_MAXH>(acc, whh, hs, Hp);
-                acc.v += bias;
-                gates[tid] = acc;
-            }
-            __syncthreads();
-            if (own) {
-                float gi = gates[tid].v, gf = gates[H + tid].v, gg = gates[2 * H + tid].v, go = gates[3 * H + tid].v;
-                const float h = lstm_cell(gi, gf, gg, go, c);
-                hs[tid].v = h;                            // the unmasked h is what the direction carries to its own next step
-                float *a = act + (size_t)step * H4;
-                a[tid] = gi; a[H + tid] = gf; a[2 * H + tid] = gg; a[3 * H + tid] = go;
-                cst[(size_t)(step + 1) * H + tid] = c;
-                hst[(size_t)(step + 1) * H + tid] = h;
-                const size_t oi = (size_t)t * (2 * H) + dir * H + tid;
-                if (LAYER == 0) dss_gp(d.midm)[oi] = mask ? h * mask[oi] : h;
-                else dss_gp(d.top)[oi] = h;
-            }
-            __syncthreads();
-        }
-    }
+    float *xs = dss_gp(d.xs), *out = dss_gp(LAYER ? d.top : d.midm);
+    if (tid < H) { cst[tid] = 0.f; hst[tid] = 0.f; }
+    bilstm_layer_body<InT, 1>(in, Cin, H, dss_gp(d.wT[LAYER][dir]), dss_gp(d.b[LAYER][dir]), dir,
+                              [&](int, int &Ts, size_t &irow, size_t &orow) { Ts = T; irow = 0; orow = 0; },
+                              [&](size_t t, int k, float x) { if (LAYER == 0 && dir == 0) xs[t * Cin + k] = x; },
+                              [&](int step, size_t t, int u, float gi, float gf, float gg, float go, float c, float h) {
+        float *a = act + (size_t)step * H4;
+        a[u] = gi; a[H + u] = gf; a[2 * H + u] = gg; a[3 * H + u] = go;
+        cst[(size_t)(step + 1) * H + u] = c;
+        hst[(size_t)(step + 1) * H + u] = h;
+        const size_t oi = t * (2 * H) + dir * H + u;
+        out[oi] = LAYER == 0 && mask ? h * mask[oi] : h;
+    });
 }
 
 template <typename InT, int LAYER>
@@ -127,36 +87,28 @@ dec_train_layer_kernel(DssDecTrainDev d, const InT *__restrict__ in, int T, cons
 }
 
 // ---- head, loss terms, gradient of the features ---------------------------------------------------------------------------------
-// A workgroup takes DTH_ROWS frames.  feat[t][o] = b[o] + sum_k w[o][k] top[t][k], dec_regress_kernel's dot product term for term;
-// dfeat = 2 (feat - target) / (T O), evaluated in float64 and rounded once; lossf[t] = sum over o, in that order, of the squared
-// differences in float64; dtop[t][k] = sum over o, in that order, of w[o][k] dfeat[t][o].
-#define DTH_ROWS 8
+// A workgroup takes DEC_RROWS frames.  feat[t][o] = b[o] + sum_k w[o][k] top[t][k] is dec_regress_rows (lstm_blocks.h), the inference
+// kernels' regressor; dfeat = 2 (feat - target) / (T O), evaluated in float64 and rounded once; lossf[t] = sum over o, in that
+// order, of the squared differences in float64; dtop[t][k] = sum over o, in that order, of w[o][k] dfeat[t][o].
 __device__ __forceinline__ void dec_train_head_body(const DssDecTrainDev &d, const int blk, const int T, const float *__restrict__ targets)
 {
-    extern __shared__ __attribute__((aligned(16))) float rs[];             // [O][K + 1] weights, [DTH_ROWS][K] inputs, [DTH_ROWS][O] dfeat
-    __shared__ double es[DTH_ROWS][DSS_DEC_MAXO];
+    extern __shared__ __attribute__((aligned(16))) float rs[];             // dec_regress_rows' weights and inputs, then [DEC_RROWS][O] dfeat
+    __shared__ double es[DEC_RROWS][DSS_DEC_MAXO];
     const int tid = threadIdx.x, K = 2 * d.H, O = d.O;
     const DssDecTrainOff o = dec_train_off(d.C, d.H, O);
-    const float *w = dss_gp(d.p) + o.wr, *b = dss_gp(d.p) + o.br;
-    float *ws = rs, *xs = rs + (size_t)O * (K + 1), *dfs = xs + (size_t)DTH_ROWS * K;
-    const int t0 = blk * DTH_ROWS, nst = min(DTH_ROWS, T - t0);
-    for (int k = tid; k < O * K; k += 256) { const int oo = k / K, j = k - oo * K; ws[oo * (K + 1) + j] = w[k]; }
-    for (int k = tid; k < DTH_ROWS * K; k += 256) xs[k] = k / K < nst ? dss_gp(d.top)[(size_t)t0 * K + k] : 0.f;
-    __syncthreads();
-    for (int idx = tid; idx < nst * O; idx += 256) {
-        const int rr = idx / O, oo = idx - rr * O;
-        const float *x = xs + rr * K, *wr = ws + oo * (K + 1);
-        float a = 0.f;
-        for (int k = 0; k < K; ++k) a = __builtin_fmaf(wr[k], x[k], a);
-        const float f = a + b[oo];
+    const float *ws = rs, *top = dss_gp(d.top);
+    float *dfs = rs + dec_regress_lds_floats(K, O);
+    const int t0 = blk * DEC_RROWS, nst = min(DEC_RROWS, T - t0);
+    dec_regress_rows(rs, K, O, dss_gp(d.p) + o.wr, dss_gp(d.p) + o.br, [&](int rr) { return rr < nst ? top + (size_t)(t0 + rr) * K : nullptr; },
+                     [&](int rr, int oo, float f) {
         const size_t fi = (size_t)(t0 + rr) * O + oo;
         const double e = (double)f - (double)targets[fi];
         const float df = (float)(2.0 * e / ((double)T * (double)O));
         dss_gp(d.feat)[fi] = f;
         dss_gp(d.dfeat)[fi] = df;
-        dfs[idx] = df;
+        dfs[rr * O + oo] = df;
         es[rr][oo] = e;
-    }
+    });
     __syncthreads();
     if (tid < nst) {
         double acc = 0.0;
@@ -383,8 +335,7 @@ int dss_launch_dec_train_trial(const DssDecTrainDev &d, const void *d_frames, in
                                const float *d_mask, int apply_step, double lr, double alpha, double eps, double *d_loss, hipStream_t st)
 {
     const int H = d.H, C = d.C, O = d.O;
-    if (H < 1 || H > DEC_MAXH || 4 * H > DEC_THREADS || C < 1 || C > DEC_MAXC || 2 * H > DEC_MAXC || O < 1 || O > DSS_DEC_MAXO ||
-        d.Tmax > DSS_DEC_TRAIN_MAXT || T < 1 || T > d.Tmax) {
+    if (!dec_fits(C, H) || O < 1 || O > DSS_DEC_MAXO || d.Tmax > DSS_DEC_TRAIN_MAXT || T < 1 || T > d.Tmax) {
         dss_set_error("decoder training kernels: %d hidden units / %d inputs / %d outputs / %d frames out of range (<= %d / <= %d / <= %d / <= %d)",
                       H, C, O, T, DEC_MAXH, DEC_MAXC, DSS_DEC_MAXO, d.Tmax);
         return DSS_EINVAL;
@@ -394,8 +345,8 @@ int dss_launch_dec_train_trial(const DssDecTrainDev &d, const void *d_frames, in
     else hipLaunchKernelGGL((dec_train_layer_kernel<float, 0>), two, block, 0, st, d, (const float *)d_frames, T, d_mask);
     hipLaunchKernelGGL((dec_train_layer_kernel<float, 1>), two, block, 0, st, d, (const float *)d.midm, T, (const float *)nullptr);
     DSS_HIP_CHECK(hipGetLastError());
-    const size_t hlds = ((size_t)O * (2 * H + 1) + (size_t)DTH_ROWS * 2 * H + (size_t)DTH_ROWS * O) * sizeof(float);
-    hipLaunchKernelGGL(dec_train_head_kernel, dim3((T + DTH_ROWS - 1) / DTH_ROWS), dim3(256), hlds, st, d, T, d_targets);
+    const size_t hlds = (dec_regress_lds_floats(2 * H, O) + (size_t)DEC_RROWS * O) * sizeof(float);
+    hipLaunchKernelGGL(dec_train_head_kernel, dim3((T + DEC_RROWS - 1) / DEC_RROWS), dim3(256), hlds, st, d, T, d_targets);
     hipLaunchKernelGGL((dec_train_bptt_kernel<1>), dim3(3), block, 0, st, d, T, d_loss);
     DSS_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(dec_train_dmid_kernel, dim3((T + DTM_FR - 1) / DTM_FR), dim3(256), 0, st, d, T, d_mask);
@@ -429,7 +380,7 @@ __global__ void __launch_bounds__(256)
 dec_group_head_kernel(const DssDecTrainDev *__restrict__ models, const DssDecGroupTrial *__restrict__ trials)
 {
     const DssDecGroupTrial tr = trials[blockIdx.y];
-    if ((int)blockIdx.x * DTH_ROWS >= tr.T) return;
+    if ((int)blockIdx.x * DEC_RROWS >= tr.T) return;
     const DssDecTrainDev &d = models[blockIdx.y];
     dec_train_head_body(d, blockIdx.x, tr.T, dss_gp(tr.targets));
 }
@@ -474,8 +425,7 @@ dec_group_step_kernel(const DssDecTrainDev *__restrict__ models, const DssDecGro
 int dss_launch_dec_train_group(const DssDecTrainDev *d_models, const DssDecGroupTrial *d_trials, int M, int C, int H, int O, int max_T,
                                int frames_f64, hipStream_t st)
 {
-    if (M < 1 || M > DSS_DEC_GROUP_MAXM || H < 1 || H > DEC_MAXH || 4 * H > DEC_THREADS || C < 1 || C > DEC_MAXC || 2 * H > DEC_MAXC ||
-        O < 1 || O > DSS_DEC_MAXO || max_T < 1 || max_T > DSS_DEC_TRAIN_MAXT) {
+    if (M < 1 || M > DSS_DEC_GROUP_MAXM || !dec_fits(C, H) || O < 1 || O > DSS_DEC_MAXO || max_T < 1 || max_T > DSS_DEC_TRAIN_MAXT) {
         dss_set_error("decoder group kernels: %d models / %d hidden units / %d inputs / %d outputs / %d frames out of range (<= %d / <= %d / <= %d / <= %d / <= %d)",
                       M, H, C, O, max_T, DSS_DEC_GROUP_MAXM, DEC_MAXH, DEC_MAXC, DSS_DEC_MAXO, DSS_DEC_TRAIN_MAXT);
         return DSS_EINVAL;
@@ -485,8 +435,8 @@ int dss_launch_dec_train_group(const DssDecTrainDev *d_models, const DssDecGroup
     else hipLaunchKernelGGL((dec_group_layer_kernel<float, 0>), two, block, 0, st, d_models, d_trials);
     hipLaunchKernelGGL((dec_group_layer_kernel<float, 1>), two, block, 0, st, d_models, d_trials);
     DSS_HIP_CHECK(hipGetLastError());
-    const size_t hlds = ((size_t)O * (2 * H + 1) + (size_t)DTH_ROWS * 2 * H + (size_t)DTH_ROWS * O) * sizeof(float);
-    hipLaunchKernelGGL(dec_group_head_kernel, dim3((max_T + DTH_ROWS - 1) / DTH_ROWS, M), dim3(256), hlds, st, d_models, d_trials);
+    const size_t hlds = (dec_regress_lds_floats(2 * H, O) + (size_t)DEC_RROWS * O) * sizeof(float);
+    hipLaunchKernelGGL(dec_group_head_kernel, dim3((max_T + DEC_RROWS - 1) / DEC_RROWS, M), dim3(256), hlds, st, d_models, d_trials);
     hipLaunchKernelGGL((dec_group_bptt_kernel<1>), dim3(2, M + (M + 1) / 2), block, 0, st, d_models, d_trials, M);
     DSS_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(dec_group_dmid_kernel, dim3((max_T + DTM_FR - 1) / DTM_FR, M), dim3(256), 0, st, d_models, d_trials);

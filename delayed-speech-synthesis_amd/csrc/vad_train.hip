@@ -9,8 +9,8 @@
 //   nn.LSTM(dropout = p), train mode      layer 0's output, as layer 1 reads it, times a mask of 0 or 1 / (1 - p); the mask is an
 //                                         INPUT here, (T, H) multipliers or NULL -- the kernels hold no generator
 // Two launches per window ("Training the detector"):
-//   vad_train_window_kernel  one workgroup of 640 threads, everything that is serial in time: the forward pass (lstm_blocks.h: the
-//                            blocks of vad_lstm.hip's forward body) with the stash the backward pass needs, the loss, dlogits,
+//   vad_train_window_kernel  one workgroup of 640 threads, everything that is serial in time: the forward pass (vad_forward_body
+//                            of lstm_blocks.h, the loop the inference kernels run) keeping the stash the backward pass needs, the loss, dlogits,
 //                            and backward through time for layer 1, then layer 0 -- the gate gradients dG1[T][4H], dG0[T][4H]
 //   vad_train_step_kernel    one workgroup per gate row (and per class of the head): the weight gradients dG^T . inputs as sums
 //                            over t in frame order, the bias gradients, and, fused, the RMSprop update of the master parameters
@@ -112,107 +112,48 @@ __device__ __forceinline__ void vad_train_window_body(const DssVadTrainDev &d, c
                                                       const unsigned char *__restrict__ targets, const float *__restrict__ mask,
                                                       double *__restrict__ loss)
 {
-    typedef typename LstmVec<1>::type V;
-    __shared__ __attribute__((aligned(16))) V xin[VAD_TP][VAD_MAXC];
-    __shared__ __attribute__((aligned(16))) V h0s[VAD_TP][VAD_MAXH];      // layer 0's MASKED h of the chunk's frames (layer 1's inputs)
-    __shared__ __attribute__((aligned(16))) V hs[2][VAD_MAXH];            // the h each layer carries to its own next step (never masked)
-    __shared__ __attribute__((aligned(16))) V gates[4 * VAD_MAXH];
     __shared__ float dgs[4 * VAD_MAXH];                                   // the gate gradients of the step in hand
     __shared__ float part[4][VAD_MAXH];                                   // W^T dG per gate, before the owner adds them
     __shared__ __attribute__((aligned(16))) float dg4[4 * VAD_MAXH][VAD_TP];     // dG1 of a chunk of frames, frames side by side
     __shared__ __attribute__((aligned(16))) float part4[4][VAD_MAXH][VAD_TP];
-    const DssVadDev &v = d.v;
+    const DssVadDev v = vad_global_dev(d.v);
     const int tid = threadIdx.x, C = v.C, H = v.H, H4 = 4 * H;
-    const int Cp = (C + 3) & ~3, Hp = (H + 3) & ~3;
     const VadTrainOff o = vad_train_off(C, H);
     const bool own = tid < H, rowt = tid < H4;
-    const float *wT0 = dss_gp(v.wT0), *wT1 = dss_gp(v.wT1), *wc = dss_gp(v.wc), *bc = dss_gp(v.bc);
-    float *vh = dss_gp(v.h), *vc = dss_gp(v.c);
     float *sh0 = dss_gp(d.h0), *sh1 = dss_gp(d.h1), *sc0 = dss_gp(d.c0), *sc1 = dss_gp(d.c1), *act0 = dss_gp(d.act0), *act1 = dss_gp(d.act1);
-    float *xs = dss_gp(d.xs), *h0m = dss_gp(d.h0m), *logit = dss_gp(d.logit), *dl = dss_gp(d.dl), *dh0m = dss_gp(d.dh0m);
-    double *lossf = dss_gp(d.lossf);
-    const float *dg1 = dss_gp(d.dg1);
+    float *xs = dss_gp(d.xs), *h0m = dss_gp(d.h0m), *logit = dss_gp(d.logit);
 
-    // ---- forward: vad_forward_body's steps (vad_lstm.hip) for one stream from the carried state, the stash writes between them --
-    float c0 = 0.f, c1 = 0.f;
-    for (int k = tid; k < 2 * VAD_MAXH; k += VAD_THREADS) reinterpret_cast<float *>(hs)[k] = 0.f;
-    for (int k = tid; k < VAD_TP * VAD_MAXH; k += VAD_THREADS) reinterpret_cast<float *>(h0s)[k] = 0.f;
-    for (int k = tid; k < VAD_TP * VAD_MAXC; k += VAD_THREADS) reinterpret_cast<float *>(xin)[k] = 0.f;
-    __syncthreads();
+    // ---- forward: vad_forward_body (lstm_blocks.h), the loop the inference kernels run, for one stream from the carried state and
+    // without labels.  Kept of a step: the frames as float32 (xs), the activated gates (row t of act), c and h behind the frame
+    // (row t + 1 of the stashes; row 0 is the window's initial state) and layer 0's h times the mask (h0m), which is what layer 1
+    // reads; the h a layer carries to its own next step is never masked.
     if (own) {
-        const float ha = vh[tid], hb = vh[H + tid];
-        c0 = vc[tid]; c1 = vc[H + tid];
-        hs[0][tid].v = ha; hs[1][tid].v = hb;
-        sh0[tid] = ha; sh1[tid] = hb; sc0[tid] = c0; sc1[tid] = c1;         // row 0 of the stashes: the window's initial state
+        sh0[tid] = v.h[tid]; sh1[tid] = v.h[H + tid]; sc0[tid] = v.c[tid]; sc1[tid] = v.c[H + tid];
     }
-    const float bias0 = rowt ? dss_gp(v.b0)[tid] : 0.f, bias1 = rowt ? dss_gp(v.b1)[tid] : 0.f;
-    for (int w0 = 0; w0 < T; w0 += VAD_TP) {
-        const int nst = min(VAD_TP, T - w0);
-        for (int idx = tid; idx < nst * C; idx += VAD_THREADS) {
-            const int tt = idx / C, k = idx - tt * C;
-            const float x = (float)frames[(size_t)(w0 + tt) * C + k];
-            xin[tt][k].v = x;
-            xs[(size_t)(w0 + tt) * C + k] = x;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int layer = 0; layer < 2; ++layer) {
-            V pre[VAD_TP];
-#pragma unroll
-            for (int tt = 0; tt < VAD_TP; ++tt) pre[tt].v = 0.f;
-            if (rowt) {
-                if (layer == 0) lstm_dot_steps<1, V, VAD_MAXC, VAD_TP>(pre, wT0, H4, tid, xin, Cp);
-                else lstm_dot_steps<1, V, VAD_MAXH, VAD_TP>(pre, wT1, H4, tid, h0s, Hp);
-            }
-#pragma unroll
-            for (int tt = 0; tt < VAD_TP; ++tt) {
-                if (tt >= nst) break;
-                const int t = w0 + tt;
-                if (rowt) {
-                    V acc = pre[tt];
-                    if (layer == 0) lstm_dot<1, V>(acc, wT0 + (size_t)Cp * H4, H4, tid, hs[0], Hp);
-                    else lstm_dot<1, V>(acc, wT1 + (size_t)Hp * H4, H4, tid, hs[1], Hp);
-                    acc.v += layer == 0 ? bias0 : bias1;
-                    gates[tid] = acc;
-                }
-                __syncthreads();
-                if (own) {
-                    float gi = gates[tid].v, gf = gates[H + tid].v, gg = gates[2 * H + tid].v, go = gates[3 * H + tid].v;
-                    float &c = layer == 0 ? c0 : c1;
-                    const float h = lstm_cell(gi, gf, gg, go, c);
-                    hs[layer][tid].v = h;
-                    float *a = dss_uniform((layer == 0 ? act0 : act1) + (size_t)t * H4);
-                    a[tid] = gi; a[H + tid] = gf; a[2 * H + tid] = gg; a[3 * H + tid] = go;
-                    dss_uniform((layer == 0 ? sc0 : sc1) + (size_t)(t + 1) * H)[tid] = c;
-                    dss_uniform((layer == 0 ? sh0 : sh1) + (size_t)(t + 1) * H)[tid] = h;
-                    if (layer == 0) {
-                        const float hm = mask ? h * dss_uniform(mask + (size_t)t * H)[tid] : h;
-                        h0s[tt][tid].v = hm;
-                        dss_uniform(h0m + (size_t)t * H)[tid] = hm;
-                    }
-                }
-                __syncthreads();
-                if (layer == 1) {
-                    if (tid < 2) {
-                        float a = 0.f;
-                        for (int k = 0; k < H; ++k) a = __builtin_fmaf(wc[tid * H + k], hs[1][k].v, a);
-                        logit[2 * t + tid] = a + bc[tid];
-                    }
-                    // (the next step writes hs[1] only behind its own first barrier)
-                }
-            }
-        }
-    }
-    if (own) { vh[tid] = hs[0][tid].v; vh[H + tid] = hs[1][tid].v; vc[tid] = c0; vc[H + tid] = c1; }
+    vad_forward_body<FrameT, 1, true, false>(v, frames, T, nullptr, logit, 0, 1, [&](int, int t, int k, float x) { xs[(size_t)t * C + k] = x; },
+                                             [&](int layer, int, int t, int u, float gi, float gf, float gg, float go, float c, float h) {
+        float *a = dss_uniform((layer == 0 ? act0 : act1) + (size_t)t * H4);
+        a[u] = gi; a[H + u] = gf; a[2 * H + u] = gg; a[3 * H + u] = go;
+        dss_uniform((layer == 0 ? sc0 : sc1) + (size_t)(t + 1) * H)[u] = c;
+        dss_uniform((layer == 0 ? sh0 : sh1) + (size_t)(t + 1) * H)[u] = h;
+        if (layer != 0) return h;
+        const float hm = mask ? h * dss_uniform(mask + (size_t)t * H)[u] : h;
+        dss_uniform(h0m + (size_t)t * H)[u] = hm;
+        return hm;
+    });
     __syncthreads();
 
     // ---- loss and dlogits: per frame in float64 from the float32 logits, the mean summed in frame order ---------------------
+    // (what only this half uses is read from the descriptor here: read in front of the forward loop, these four pointers cost the
+    // group kernel, whose descriptor lives in scalar registers, 500 register reloads in that loop and 2 % of a step)
+    float *dl = dss_gp(d.dl), *dh0m = dss_gp(d.dh0m);
+    double *lossf = dss_gp(d.lossf);
+    const float *dg1 = dss_gp(d.dg1);
     for (int t = tid; t < T; t += VAD_THREADS) {
         const double z0 = logit[2 * t], z1 = logit[2 * t + 1];
         const int tg = targets[t] ? 1 : 0;
-        const double m = fmax(z0, z1);
-        const double lse = m + log(exp(z0 - m) + exp(z1 - m));
-        lossf[t] = lse - (tg ? z1 : z0);
+        double lse;
+        lossf[t] = lstm_cross_entropy(z0, z1, tg, lse);
         dl[2 * t] = (float)((exp(z0 - lse) - (tg ? 0.0 : 1.0)) / (double)T);
         dl[2 * t + 1] = (float)((exp(z1 - lse) - (tg ? 1.0 : 0.0)) / (double)T);
     }
@@ -326,7 +267,7 @@ int dss_launch_vad_train_window(const DssVadTrainDev &d, const void *d_frames, i
                                 const float *d_mask, int apply_step, double lr, double alpha, double eps, double *d_loss, hipStream_t st)
 {
     const int H = d.v.H, C = d.v.C;
-    if (H < 1 || H > VAD_MAXH || 4 * H > VAD_THREADS || C < 1 || C > VAD_MAXC || T < 1 || T > d.Tmax) {
+    if (!vad_fits(C, H) || T < 1 || T > d.Tmax) {
         dss_set_error("VAD training kernel: %d hidden units / %d inputs / %d frames out of range (<= %d / <= %d / <= %d)", H, C, T,
                       VAD_MAXH, VAD_MAXC, d.Tmax);
         return DSS_EINVAL;
@@ -390,8 +331,7 @@ vad_group_reset_kernel(const DssVadTrainDev *__restrict__ models, const DssVadGr
 int dss_launch_vad_train_group(const DssVadTrainDev *d_models, const DssVadGroupTrial *d_trials, int M, int C, int H, int n_windows,
                                int window, int reset, int frames_f64, hipStream_t st)
 {
-    if (M < 1 || M > DSS_VAD_GROUP_MAXM || H < 1 || H > VAD_MAXH || 4 * H > VAD_THREADS || C < 1 || C > VAD_MAXC || n_windows < 1 ||
-        window < 1 || window > DSS_VAD_TRAIN_MAXT) {
+    if (M < 1 || M > DSS_VAD_GROUP_MAXM || !vad_fits(C, H) || n_windows < 1 || window < 1 || window > DSS_VAD_TRAIN_MAXT) {
         dss_set_error("VAD group kernels: %d models / %d hidden units / %d inputs / %d windows of %d frames out of range (<= %d / <= %d / <= %d / >= 1 / <= %d)",
                       M, H, C, n_windows, window, DSS_VAD_GROUP_MAXM, VAD_MAXH, VAD_MAXC, DSS_VAD_TRAIN_MAXT);
         return DSS_EINVAL;

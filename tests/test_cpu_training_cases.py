@@ -155,7 +155,7 @@ def _define(header, name):
 def test_the_restated_constants_are_the_kernels():
     assert TC.DEC_THREADS == _define("lstm_blocks.h", "DEC_THREADS") and TC.VAD_THREADS == _define("lstm_blocks.h", "VAD_THREADS")
     assert TC.STEP_TILE == _define("dec_train.hip", "DTS_THREADS") == _define("vad_train.hip", "VTS_THREADS")
-    assert TC.FRAME_TILE == _define("dec_train.hip", "DTH_ROWS") == _define("dec_train.hip", "DTM_FR")
+    assert TC.FRAME_TILE == _define("lstm_blocks.h", "DEC_RROWS") == _define("dec_train.hip", "DTM_FR")
     assert TC.DEC_MAXO == _define("dss_common.h", "DSS_DEC_MAXO")
     assert max(e.H for e in TC.DECODER) <= _define("dss_common.h", "DSS_DEC_MAXH") and max(e.C for e in TC.DECODER) <= _define("dss_common.h", "DSS_DEC_MAXC")
     assert max(e.H for e in TC.DETECTOR) <= _define("dss_common.h", "DSS_VAD_MAXH") and max(e.C for e in TC.DETECTOR) <= _define("dss_common.h", "DSS_VAD_MAXC")

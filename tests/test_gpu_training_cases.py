@@ -5,7 +5,7 @@ beyond the 256-frame tile of the step kernels and beyond the loss loops' strides
 Per entry the gradients, the loss and the features / the carried state are held to float64 autograd with the helpers and bounds
 of tests/test_gpu_decoder_training.py and tests/test_gpu_vad_training.py (``D.check_trial``, ``V.check_window``: GRAD_BOUND per
 tensor, the loss bounds, lstm_reference.bound(scale), C_REL); tests/test_cpu_training_cases.py shows that the table fits that
-bound's definition.  The decoder's forward half is the inference kernel bit for bit at every entry.  After update steps at
+bound's definition.  Both trainers' forward halves are the inference kernels bit for bit at every entry.  After update steps at
 unaligned sizes the trainers are still the float64 model of the weights they read back, and what they publish is what loading
 their ``state_dict()`` gives.  A handle that ran a long trial computes a short one like a fresh handle.  The detector's trial in
 one call is its windows one by one at the window geometries no other test has, and the group forms equal their single trainers
@@ -98,7 +98,7 @@ def test_detector_gradients_loss_and_state_against_float64(T, e):
           f"h {worst[2]:.3g} (bound {R.bound(e.scale):g}), c {worst[3]:.3g} (bound {R.C_REL:g})")
 
 
-# ---- 2: the decoder's forward half is the inference kernel ------------------------------------------------------------------
+# ---- 2: the trainers' forward halves are the inference kernels --------------------------------------------------------------
 
 @pytest.mark.parametrize("e", TC.DECODER, ids=TC.ident)
 def test_decoder_forward_half_is_the_inference_kernel(T, e):
@@ -113,6 +113,34 @@ def test_decoder_forward_half_is_the_inference_kernel(T, e):
         want = dec(xs.cuda()[None])[0].cpu().numpy()
         assert want.shape == (e.T, e.O) and np.isfinite(want).all() and want.any()
         assert np.array_equal(tr.features(), want)
+
+
+@pytest.mark.parametrize("e", TC.DETECTOR, ids=TC.ident)
+def test_detector_forward_half_is_the_inference_kernel(T, e):
+    """Without a mask, two consecutive windows of a fresh trainer (the second from the state the first left) carry the bits of a
+    fresh ``VadLstmGPU`` loaded from the same state_dict and stepped through the same frames twice: the state after each window,
+    and the window's loss, which is what ``dss_vad_score_trials_dev`` makes of the detector's logits for those frames (the same
+    term per frame, added in the same order, in float64)."""
+    import torch
+    from dss_amd import _lib
+    from dss_amd.vad import VadLstmGPU
+    sd, x, y, _, _ = TC.detector_inputs(e, None)
+    L = _lib.require_gpu()
+    tg = torch.from_numpy(np.ascontiguousarray(y, dtype=np.uint8)).cuda()
+    length = np.array([e.T], np.int32)
+    for f64 in _frame_types(e):
+        tr, det, xs = T.VadTrainerGPU(sd, max_window=e.T), VadLstmGPU(1, state_dict=sd), _x(x, f64)
+        for k in range(2):
+            loss = tr.window(xs, y, mask=None, step=False)
+            pred, logits = det.step_torch(xs.cuda()[None], want_logits=True)
+            (h, c), (wh, wc) = tr.state(), det.state()
+            assert np.array_equal(h, wh[:, 0]) and np.array_equal(c, wc[:, 0]), (f64, k)
+            assert h.any() and c.any()
+            want = torch.empty((1,), dtype=torch.float64, device="cuda")
+            correct = torch.empty((1,), dtype=torch.int32, device="cuda")
+            _lib.check(L.dss_vad_score_trials_dev(logits.data_ptr(), pred.data_ptr(), tg.data_ptr(), 1, length.ctypes.data, want.data_ptr(),
+                                                  correct.data_ptr(), None, torch.cuda.current_stream().cuda_stream))
+            assert np.isfinite(loss) and loss == float(want.cpu()[0]), (f64, k, loss, float(want.cpu()[0]))
 
 
 # ---- 3: after a step, still the float64 model of the read-back weights; publish ------------------------------------------------

@@ -10,7 +10,7 @@ what the kernels do:
               W_ih_l1 pass (4-wide), the packed-copy index ``ki = Cp + (k - nA)`` of both step kernels; the decoder's layer 1 then
               has 2H = 2 modulo 4 inputs.  (127, 255) and (159, 127) are the largest odd sizes the kernels take
   smallest    H = C = 1
-  tiles       the 8-frame tiles of the decoder's head (``DTH_ROWS``) and dmid (``DTM_FR``) kernels at T = 8, 16 and 17: one full
+  tiles       the 8-frame tiles of the decoder's head (``DEC_RROWS``) and dmid (``DTM_FR``) kernels at T = 8, 16 and 17: one full
               tile, two, and two with one frame behind them (the ``tt < nst`` zero fill)
   long        the 256-frame tile of both step kernels (``DTS_THREADS``, ``VTS_THREADS``) at its edge, T = 256 and 257; the second
               pass of ``dec_train_loss_body``'s stride of ``DEC_THREADS`` = 512 (T = 513) and the third (1025); the second pass
@@ -43,7 +43,7 @@ import vad_training_reference as V
 DEC_THREADS = 512                # the stride of dec_train_loss_body
 VAD_THREADS = 640                # the stride of the detector's loss / dlogits loop
 STEP_TILE = 256                  # DTS_THREADS, VTS_THREADS: frames per pass of the step kernels' sum over t
-FRAME_TILE = 8                   # DTH_ROWS, DTM_FR: frames per workgroup of the decoder's head and dmid kernels
+FRAME_TILE = 8                   # DEC_RROWS, DTM_FR: frames per workgroup of the decoder's head and dmid kernels
 DEC_MAXO = 32                    # DSS_DEC_MAXO
 
 Entry = collections.namedtuple("Entry", "H C T scale O masks")

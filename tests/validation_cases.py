@@ -109,11 +109,12 @@ def source_constants():
 
     def define(src, name):
         return int(re.search(r"#define\s+%s\s+(\d+)" % name, src).group(1))
-    dec, vad, common = text("bilstm_decoder.hip"), text("vad_lstm.hip"), text("dss_common.h")
-    trials = dec[dec.index("int dss_launch_decoder_trials("):]
-    w = re.search(r"Wsel = 2 \* S <= (\d+) \? 1 : \(S <= (\d+) \? 2 : 4\)", trials)
+    dec, vad, common, blocks = text("bilstm_decoder.hip"), text("vad_lstm.hip"), text("dss_common.h"), text("lstm_blocks.h")
+    # both decoder launchers take the streams per workgroup from dss_dec_streams_per_wg
+    assert len(re.findall(r"const int W = dss_dec_streams_per_wg\(S\);", dec)) == 1 and "Wsel" not in dec
+    w = re.search(r"int dss_dec_streams_per_wg\(int S\) \{ return 2 \* S <= (\d+) \? 1 : \(S <= (\d+) \? 2 : 4\); \}", common)
     mse = dec[dec.index("dec_mse_trials_kernel(DssTrialLens"):]
-    return dict(WIDTH_1_UP_TO=int(w.group(1)) // 2, WIDTH_2_UP_TO=int(w.group(2)), REGRESS_ROWS=define(dec, "DEC_RROWS"),
+    return dict(WIDTH_1_UP_TO=int(w.group(1)) // 2, WIDTH_2_UP_TO=int(w.group(2)), REGRESS_ROWS=define(blocks, "DEC_RROWS"),
                 TRIAL_CHUNK=define(common, "DSS_TRIAL_CHUNK"), SCORE_TILE=define(vad, "SCORE_THREADS"),
                 MSE_STRIDE=int(re.search(r"i < n; i \+= (\d+)\)", mse).group(1)), DEC_MAXO=define(common, "DSS_DEC_MAXO"),
                 VAD_MAX=(define(common, "DSS_VAD_MAXH"), define(common, "DSS_VAD_MAXC")),
